@@ -13,7 +13,11 @@ data path.  --scaling weak (default): every rank decodes --frames frames; --scal
                                                        process, before this process touches a GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (the driver's form)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps (the headline `value`, `ms_per_step`,
+the error counters of the last step) and prints that line; --full adds the secondary measurements to it: the kernel-only
+region, per-kernel times alone and the roofline objects, the host-pointer leg, the leg with the list decoder forced, the
+configs[1] / [3] / [4] legs and the CPU baseline.  --dump-outputs DIR writes what the timed path returned in its last step
+(rank 0) as .npy files.
 """
 import argparse
 import hashlib
@@ -59,8 +63,8 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--noise-db", type=float, default=-30.0)
     ap.add_argument("--chunk", type=int, default=0, help="resident frames per pass (0 = library default)")
-    ap.add_argument("--cpu-frames", type=int, default=-1, help="cpu_baseline sample size (-1 auto, 0 off)")
-    ap.add_argument("--host-frames", type=int, default=-1, help="frames of the host-pointer leg value_host (-1 auto, 0 off)")
+    ap.add_argument("--cpu-frames", type=int, default=-1, help="cpu_baseline sample size (-1 auto, 0 off; --full)")
+    ap.add_argument("--host-frames", type=int, default=-1, help="frames of the host-pointer leg value_host (-1 auto, 0 off; --full)")
     ap.add_argument("--seed", type=int, default=2021)
     ap.add_argument("--unique", type=int, default=-1,
                     help="distinct payloads / clean frames made by the device transmitter (-1 = every frame distinct, "
@@ -76,9 +80,15 @@ def parse_args(argv=None):
                     help="configs[3]: every frame also goes through the device channel chain multipath -> CFO +234.567 Hz "
                          "-> SFO +147 ppm (README.md:49) before the AWGN")
     ap.add_argument("--scl-steps", type=int, default=-1,
-                    help="steps of the extra leg with the list decoder forced for every frame (value_scl_forced); -1 = min(steps, 5), 0 = off")
+                    help="steps of the extra leg with the list decoder forced for every frame (value_scl_forced; --full); -1 = min(steps, 5), 0 = off")
     ap.add_argument("--leg-steps", type=int, default=4,
-                    help="steps of each of the two extra legs value_config3 / value_noise_m20 (one GPU, headline workload; 0 = off)")
+                    help="steps of each of the two extra legs value_config3 / value_noise_m20 (one GPU, headline workload; 0 = off; --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (value_kernel_only, per-kernel times alone, roofline, value_host, "
+                         "value_scl_forced, the configs[1] / [3] / [4] legs, cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last timed step to DIR/<name>.npy (float32 / float64): "
+                         "the payload bytes of a fixed seeded sample of frames and the result record fields")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the ranks only rendezvous (gloo), shard the frames and reduce counters (launcher test)")
     return ap.parse_args(argv)
@@ -173,6 +183,30 @@ def cpu_baseline(pcm_sample, payload_ref, ch=2):
                       % (n, v["frames"] / float(max(v["threads"], 1)), n_short, rates[0], rates[-1], desc.get(best, best), v["threads"],
                          host_cores, v["payloads_correct"], v["frames"], v["wall_s"], one_tag, one["frames_per_s"]),
             "variants": variants}
+
+
+DUMP_PAYLOAD_FRAMES = 2048             # payload rows in a dump: 2048 x 5380 float32 = 44 MB
+DUMP_RESULT_FRAMES = 65536             # result records in a dump (every frame of the headline batch): 3.7 MB
+DUMP_SEED = 20211016
+
+
+def dump_outputs(out_dir, payload, results):
+    """--dump-outputs: what the caller of the timed path received in its last step - payload bytes (float32) of a fixed,
+    seeded sample of frames, and every field of the result records (float64 where float32 would round: sc_start, call_sign)
+    of a fixed, seeded sample of at most DUMP_RESULT_FRAMES frames; the frame indices of both samples as well"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = payload.shape[0]
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(n, min(n, DUMP_PAYLOAD_FRAMES), replace=False))
+    rows = np.arange(n) if n <= DUMP_RESULT_FRAMES else np.sort(rng.choice(n, DUMP_RESULT_FRAMES, replace=False))
+    arrays = {"payload": payload[pick].astype(np.float32), "payload_frames": pick.astype(np.float64),
+              "result_frames": rows.astype(np.float64)}
+    for name in results.dtype.names:
+        wide = results.dtype[name].itemsize == 8
+        arrays["result_" + name] = results[name][rows].astype(np.float64 if wide else np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def dry_run(args):
@@ -279,10 +313,10 @@ def main():
             if ch == 2 and impair:
                 source += ", device channel chain multipath(4 taps) -> CFO +234.567 Hz -> SFO +147 ppm (configs[3])"
             return d_pay, U, source
-        fx = np.load(os.path.join(ROOT, "tests", "golden", "base_frames_2ch.npz"))
-        base = fx["pcm"]
+        fx = [np.load(os.path.join(ROOT, "tests", "golden", "base_frames_2ch_%d.npz" % i)) for i in range(2)]
+        base = np.concatenate([f["pcm"] for f in fx])
         n_base = base.shape[0]
-        d_pay = torch.from_numpy(fx["payload"]).to(dev)
+        d_pay = torch.from_numpy(np.concatenate([f["payload"] for f in fx])).to(dev)
         d_base = torch.from_numpy(base).to(dev)
         if ch == 2:
             rxh.awgn_tile(d_base.data_ptr(), n_base, d_in.data_ptr(), B, spf, noise_db, args.seed, first)
@@ -290,7 +324,7 @@ def main():
             idx = torch.arange(B, device=dev) % n_base
             for lo_ in range(0, B, 4096):
                 d_in[lo_:lo_ + 4096, :, 0] = d_base[idx[lo_:lo_ + 4096], :, 0]
-        return d_pay, n_base, "%d committed fixture frames (tests/golden/base_frames_2ch.npz) tiled" % n_base
+        return d_pay, n_base, "%d committed fixture frames (tests/golden/base_frames_2ch_*.npz) tiled" % n_base
 
     d_pay, n_base, source = generate(rx, args.noise_db, args.impair)
     rx.synchronize()
@@ -298,7 +332,7 @@ def main():
     gen_s = time.perf_counter() - t_gen
     # cpu_baseline's sample: the first frames of THIS batch, taken now - the extra legs below regenerate d_in (round-5 verdict, weak 4)
     cpu_sample = cpu_ref = None
-    if rank == 0 and world == 1 and args.cpu_frames != 0 and B:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames != 0 and B:
         ncpu = min(CPU_FRAMES_DEFAULT if args.cpu_frames < 0 else args.cpu_frames, B)
         cpu_sample = d_in[:ncpu].cpu().numpy()
         cpu_ref = d_pay[torch.arange(ncpu, device=dev) % n_base].cpu().numpy()
@@ -354,11 +388,13 @@ def main():
     last = (args.steps - 1) & 1
     list_decoded = rx.list_decoded_frames() if B else 0      # of the last step; -1: no certificate on this handle
     sc_decided = rx.sc_decided_frames() if B else 0          # ... finished by the list-1 pass; -1: that pass is off
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, h_out.numpy()[:B], h_res.numpy().view(M.RESULT_DTYPE).reshape(-1)[:B])
     # one extra, untimed step with every kernel alone on the device (OFDMRX_NO_OVERLAP is read per call): under the pipeline a
     # stage's event span includes the time it shares the machine with others; the kernel that takes the most time ALONE is
     # the one the roofline object describes
     alone_ms = {}
-    if B:
+    if args.full and B:
         prev = os.environ.get("OFDMRX_NO_OVERLAP")
         os.environ["OFDMRX_NO_OVERLAP"] = "1"
         step(0, False)
@@ -367,12 +403,13 @@ def main():
             del os.environ["OFDMRX_NO_OVERLAP"]
         else:
             os.environ["OFDMRX_NO_OVERLAP"] = prev
-    # ---- timed region 2: the kernels alone (payloads stay in HBM)
-    t0 = time.perf_counter()
-    for s in range(args.steps):
-        step(s, False)
-    fence()
-    secs_k = time.perf_counter() - t0
+    # ---- timed region 2 (--full): the kernels alone (payloads stay in HBM)
+    if args.full:
+        t0 = time.perf_counter()
+        for s in range(args.steps):
+            step(s, False)
+        fence()
+        secs_k = time.perf_counter() - t0
 
     # ---- error counters from the HOST copy of the last timed step (that is what a consumer would see)
     res = h_res.numpy().view(M.RESULT_DTYPE).reshape(-1)[:B]
@@ -384,7 +421,7 @@ def main():
         be = pop[(d_last[lo_:lo_ + 8192] ^ ref).long()].sum(dim=1)
         frame_err += int((be > 0).sum().item())
         bit_err += int(be.sum().item())
-    assert B == 0 or bool((d_last == d_out[last][:B]).all().item()), "host copy differs from the device buffer"
+    assert B == 0 or not args.full or bool((d_last == d_out[last][:B]).all().item()), "host copy differs from the device buffer"
     ok_status = int((res["status"] == 0).sum())
 
     # ---- host-pointer leg: pinned host samples in -> payload bytes on the host (ofdmrx_decode_batch), bounded sample
@@ -393,7 +430,7 @@ def main():
     if nh < 0:
         nh = min(B, 16384)
     nh = min(nh, B)
-    if nh > 0 and ch == 2:
+    if args.full and nh > 0 and ch == 2:
         h_in = torch.empty((nh, spf, ch), dtype=torch.int16, pin_memory=True)
         h_in.copy_(d_in[:nh])
         torch.cuda.synchronize()
@@ -415,7 +452,7 @@ def main():
     rx = None
     scl = None
     scl_steps = min(args.steps, 5) if args.scl_steps < 0 else args.scl_steps
-    if scl_steps > 0 and not os.environ.get("OFDMRX_NO_CERT"):     # (the same decision on every rank: barriers inside)
+    if args.full and scl_steps > 0 and not os.environ.get("OFDMRX_NO_CERT"):     # (the same decision on every rank: barriers inside)
         sm2, sl2 = {}, {}
         same = True
         if B:
@@ -445,7 +482,7 @@ def main():
     # ---- two bounded legs outside `value` (one GPU, the headline workload only): what the README's own channel chain and a noise
     # level where the certificate decides nothing cost through the DEFAULT handle - configs[3] and one level of configs[4]
     extra = {}
-    if world == 1 and B and ch == 2 and args.unique != 0 and not args.impair and args.leg_steps > 0:
+    if args.full and world == 1 and B and ch == 2 and args.unique != 0 and not args.impair and args.leg_steps > 0:
         rx3 = modem_amd.Receiver(device=local_rank, chunk_frames=args.chunk, stream=stream.cuda_stream, sample_rate=args.rate,
                                  list_size=args.list)
         pop8 = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device=dev)
@@ -514,7 +551,7 @@ def main():
 
     secs_max, (frames_total, frame_err, bit_err, ok_status, ranks, frames_step) = shard.reduce_counters(
         (secs, [B * args.steps, frame_err, bit_err, ok_status, 1, B]), world, dist, dev)
-    secs_k_max, _ = shard.reduce_counters((secs_k, [0]), world, dist, dev)
+    secs_k_max = shard.reduce_counters((secs_k, [0]), world, dist, dev)[0] if args.full else None
     # which rank decoded how many frames, and what the process group says about itself (RCCL, the world size it sees)
     frames_by_rank, dist_info = [B], {"backend": None, "world_size": 1}
     if dist:
@@ -531,11 +568,13 @@ def main():
     if rank == 0:
         value = frames_total / secs_max
         b_frame = spf * 2 * ch + 5380          # compulsory input + output bytes per frame (386180 for the headline)
-        try:
-            with open(os.path.join(ROOT, "profiles", TRAFFIC_FILE)) as fh:
-                traffic_db = json.load(fh)
-        except (OSError, ValueError):
-            traffic_db = {}
+        traffic_db = {}
+        if args.full:
+            try:
+                with open(os.path.join(ROOT, "profiles", TRAFFIC_FILE)) as fh:
+                    traffic_db = json.load(fh)
+            except (OSError, ValueError):
+                pass
 
         def roofline(sm, sl, steps, alone=None, fps=None, bf=None, dbkey="kernels"):
             """the roofline object of the stage that takes the most time in a run: achieved = ALGORITHMIC bytes of the whole path
@@ -616,17 +655,9 @@ def main():
             "value_definition": "samples resident in HBM -> payload bytes + result records resident in pinned host memory (the device "
                                 "entry with pinned host output pointers: every chunk is copied out behind its flush, beside the next "
                                 "chunk's kernels); the library's default behaviour",
-            "value_kernel_only": frames_total / secs_k_max,
-            "value_scl_forced": (frames_step * scl["steps"] / secs2_max) if (scl and secs2_max) else None,
-            "value_scl_forced_definition": ("the same batch, OFDMRX_FLAG_SCL_ALWAYS: polar SCL for every frame (what the reference does), "
-                                            "%d steps, payloads left in HBM; outputs identical to the default path: %s"
-                                            % (scl["steps"], scl["identical"])) if scl else None,
             "list_decoded_frames_rank0": list_decoded,
             "routes_rank0": {"certified": B - max(list_decoded, 0) - max(sc_decided, 0) if list_decoded >= 0 else 0,
                              "sc_decided": max(sc_decided, 0), "list_decoded": list_decoded if list_decoded >= 0 else B},
-            "value_host": host_fps,
-            "value_host_definition": ("ofdmrx_decode_batch: %d frames from PINNED host memory -> payload bytes on the host, "
-                                      "PCIe both ways inside the time, rank 0 only" % nh) if host_fps else None,
             "config": {"workload": ("configs[%d]%s: batch %d analytic (2-ch int16) mode-%d %g kHz frames %s, AWGN noise "
                                     "level %g dB (a noise LEVEL: about +20 dB SNR), inputs resident in HBM; %s, on-device noise keyed "
                                     "by frame index%s"
@@ -639,14 +670,25 @@ def main():
                        "parallelism": "frames x%d" % ranks},
             "ber": bit_err / (43040.0 * max(frames_step, 1)), "fer": frame_err / float(max(frames_step, 1)),
             "frames_ok": ok_status, "frames": frames_step,
-            "roofline": roofline(stage_ms, stage_launches, args.steps, alone_ms, fps=value / max(ranks, 1), dbkey="kernels" if ch == 2 else "kernels_mono"),
-            "roofline_scl_forced": roofline(scl["stage_ms"], scl["stage_launches"], scl["steps"],
-                                            fps=frames_step * scl["steps"] / secs2_max / max(ranks, 1) if secs2_max else None) if scl else None,
             "stage_ms_per_step": {k: v / args.steps for k, v in stage_ms.items()},
-            "stage_ms_per_launch_alone": alone_ms,
-            "stage_ms_per_step_scl_forced": {k: v / scl["steps"] for k, v in scl["stage_ms"].items()} if scl else None,
             "input_generation_s": gen_s,
         }
+        if args.full:
+            line.update({
+                "value_kernel_only": frames_total / secs_k_max,
+                "value_scl_forced": (frames_step * scl["steps"] / secs2_max) if (scl and secs2_max) else None,
+                "value_scl_forced_definition": ("the same batch, OFDMRX_FLAG_SCL_ALWAYS: polar SCL for every frame (what the reference does), "
+                                                "%d steps, payloads left in HBM; outputs identical to the default path: %s"
+                                                % (scl["steps"], scl["identical"])) if scl else None,
+                "value_host": host_fps,
+                "value_host_definition": ("ofdmrx_decode_batch: %d frames from PINNED host memory -> payload bytes on the host, "
+                                          "PCIe both ways inside the time, rank 0 only" % nh) if host_fps else None,
+                "roofline": roofline(stage_ms, stage_launches, args.steps, alone_ms, fps=value / max(ranks, 1), dbkey="kernels" if ch == 2 else "kernels_mono"),
+                "roofline_scl_forced": roofline(scl["stage_ms"], scl["stage_launches"], scl["steps"],
+                                                fps=frames_step * scl["steps"] / secs2_max / max(ranks, 1) if secs2_max else None) if scl else None,
+                "stage_ms_per_launch_alone": alone_ms,
+                "stage_ms_per_step_scl_forced": {k: v / scl["steps"] for k, v in scl["stage_ms"].items()} if scl else None,
+            })
         line.update(extra)
         if ranks == 1 and cpu_sample is not None:
             line["cpu_baseline"] = cpu_baseline(cpu_sample, cpu_ref, ch)

@@ -5,6 +5,8 @@ Runs only in the build container (needs /root/reference).  Sources:
   * psk.hh          -> psk_vectors.json   (hard / soft / map of PhaseShiftKeying<8|4>,
                        evaluated through oracle/_ref/libref_psk.so which #includes the real header)
   * polar_tables.hh -> polar_tables.json  (SHA-256 + popcount + first/last landmarks of both masks)
+  * psk.hh + polar_tables.hh -> psk_live_points.npz (hard / soft of PhaseShiftKeying<8|4> on the 4000 seeded random
+                       points of tests/test_oracle_golden.py::test_psk_against_live_reference_build, both masks word for word)
 The fixtures are DATA (inputs + expected outputs); no reference source text is stored.
 """
 import ctypes as C
@@ -70,7 +72,25 @@ def main():
         }
     with open(os.path.join(HERE, "polar_tables.json"), "w") as f:
         json.dump(tabs, f, indent=1)
-    print("wrote psk_vectors.json (%d points) and polar_tables.json" % len(pts))
+
+    # the random points of test_psk_against_live_reference_build (the same generator calls as the test) through the real header
+    rng = np.random.default_rng(7)
+    pts = rng.normal(0, 1, size=(20000, 2)).astype(np.float32)[:4000]
+    pr = rng.uniform(0.1, 500, size=20000).astype(np.float32)[:4000]
+    live = {"points": pts, "precision": pr}
+    for order in (8, 4):
+        hard, soft = getattr(ref, "ref_psk%d_hard" % order), getattr(ref, "ref_psk%d_soft" % order)
+        h = np.zeros((len(pts), 3), np.float32)
+        s = np.zeros((len(pts), 3), np.float32)
+        for i, ((re, im), p) in enumerate(zip(pts, pr)):
+            hb, sb = f3(), f3()
+            hard(hb, C.c_float(re), C.c_float(im))
+            soft(sb, C.c_float(re), C.c_float(im), C.c_float(p))
+            h[i], s[i] = list(hb), list(sb)
+        live["hard%d" % order], live["soft%d" % order] = h, s
+    live["frozen"] = np.stack([np.ctypeslib.as_array(ref.ref_frozen(t), shape=(2048,)).astype("<u4") for t in (0, 1)])
+    np.savez_compressed(os.path.join(HERE, "psk_live_points.npz"), **live)
+    print("wrote psk_vectors.json (%d points), polar_tables.json and psk_live_points.npz" % (len(precs)))
 
 
 if __name__ == "__main__":

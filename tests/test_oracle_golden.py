@@ -61,23 +61,22 @@ def test_frozen_table_matches_reference_hash(table, name):
     assert [int(x) for x in w[:8]] == g["words_first8"] and int(w[1000]) == g["word_1000"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="real reference only in the build container")
 def test_psk_against_live_reference_build():
-    """oracle/_ref (the real psk.hh compiled from /root/reference) on 20k random points"""
-    O.build()
-    ref = C.CDLL(os.path.join(O.ORACLE_DIR, "_ref", "libref_psk.so"))
+    """the real psk.hh / polar_tables.hh, compiled and run by tests/golden/gen_golden.py, on 4000 seeded random points:
+    their outputs are stored in tests/golden/psk_live_points.npz; the oracle must give them bit for bit"""
+    g = np.load(os.path.join(HERE, "golden", "psk_live_points.npz"))
     rng = np.random.default_rng(7)
     pts = rng.normal(0, 1, size=(20000, 2)).astype(np.float32)
     pr = rng.uniform(0.1, 500, size=20000).astype(np.float32)
+    assert (g["points"].view(np.uint32) == pts[:4000].view(np.uint32)).all()
+    assert (g["precision"].view(np.uint32) == pr[:4000].view(np.uint32)).all()
     for order in (8, 4):
         hard, soft, _ = _psk(order)
-        rh = getattr(ref, "ref_psk%d_hard" % order)
-        rs = getattr(ref, "ref_psk%d_soft" % order)
-        for (re, im), p in zip(pts[:4000], pr):
-            a, b, c, d = ((C.c_float * 3)() for _ in range(4))
-            hard(a, CF(re, im)); rh(b, C.c_float(re), C.c_float(im))
-            soft(c, CF(re, im), p); rs(d, C.c_float(re), C.c_float(im), C.c_float(p))
-            assert list(a) == list(b) and [x.hex() for x in c] == [x.hex() for x in d]
-    ref.ref_frozen.restype = C.POINTER(C.c_uint32)
+        rh, rs = g["hard%d" % order], g["soft%d" % order]
+        for i, ((re, im), p) in enumerate(zip(pts[:4000], pr)):
+            a, c = ((C.c_float * 3)() for _ in range(2))
+            hard(a, CF(re, im))
+            soft(c, CF(re, im), p)
+            assert list(a) == [float(x) for x in rh[i]] and [x.hex() for x in c] == [float(x).hex() for x in rs[i]]
     for t in (0, 1):
-        assert (np.ctypeslib.as_array(ref.ref_frozen(t), shape=(2048,)) == O.frozen(t)).all()
+        assert (g["frozen"][t] == O.frozen(t)).all()

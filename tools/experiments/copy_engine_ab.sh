@@ -7,6 +7,6 @@ d=json.loads(sys.stdin.readline()); print("value", round(d["value"]), "kernel_on
 for rep in 1 2; do
 for cfg in "X=0" "HSA_ENABLE_SDMA=0" "GPU_FORCE_BLIT_COPY_SIZE=0" "HSA_ENABLE_SDMA=1 GPU_FORCE_BLIT_COPY_SIZE=0"; do
   echo -n "[$cfg] " >> $O
-  env $cfg python3 bench.py --steps 10 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+  env $cfg python3 bench.py --full --steps 10 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 done; done
 cat $O

@@ -7,7 +7,7 @@ d=json.loads(sys.stdin.readline()); s=d["stage_ms_per_step"]; print("value", rou
 for e in "" "$@"; do
 	for rep in 1 2; do
 		echo -n "[$e] overlapped: " >> $O
-		env $e timeout 300 python3 bench.py --steps 3 --warmup 1 --cpu-frames 0 --host-frames 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+		env $e timeout 300 python3 bench.py --full --steps 3 --warmup 1 --cpu-frames 0 --host-frames 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 	done
 done
 cat $O

@@ -9,7 +9,7 @@ for q in 4 8 16; do
 	echo "== GPU_MAX_HW_QUEUES=$q" >> $O
 	for x in "" "--noise-db -20" "--impair"; do
 		echo -n "bench $x: " >> $O
-		GPU_MAX_HW_QUEUES=$q timeout 300 python3 bench.py --steps 4 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 2 --leg-steps 0 $x 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+		GPU_MAX_HW_QUEUES=$q timeout 300 python3 bench.py --full --steps 4 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 2 --leg-steps 0 $x 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 	done
 	echo "two handles, -30 dB:" >> $O
 	GPU_MAX_HW_QUEUES=$q PROBE_NOISE_DB=-30 timeout 600 python3 tools/two_handles_probe.py 2>&1 | grep handles >> $O

@@ -6,7 +6,7 @@ d=json.loads(sys.stdin.readline()); s=d["stage_ms_per_step"]; print("value", rou
 for rep in 1 2; do
 for env in "OFDMRX_LANES=1" "OFDMRX_LANES=2"; do
 	echo -n "[$env] ${X:---noise-db -20}: " >> $O
-	env $env timeout 300 python3 bench.py --steps ${STEPS:-6} --warmup ${WARM:-3} --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 ${X:---noise-db -20} 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+	env $env timeout 300 python3 bench.py --full --steps ${STEPS:-6} --warmup ${WARM:-3} --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 ${X:---noise-db -20} 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 done
 done
 cat $O

@@ -9,7 +9,7 @@ for env in ${ENVS:-"OFDMRX_LANES=1 GPU_MAX_HW_QUEUES=4" "OFDMRX_LANES=2 GPU_MAX_
 	echo "== $env" >> $O
 	for x in "" "--noise-db -20" "--impair" "--noise-db -26"; do
 		echo -n "bench $x: " >> $O
-		env $env timeout 300 python3 bench.py --steps 4 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 $x 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+		env $env timeout 300 python3 bench.py --full --steps 4 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 $x 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 	done
 done
 cat $O

@@ -7,7 +7,7 @@ for rep in 1 2; do
 for lib in default $1; do
 	L=$PWD/modem_amd/lib/variants/libofdmrx_$lib.so; [ $lib = default ] && L=$PWD/modem_amd/lib/libofdmrx.so
 	echo -n "$lib ${X}: " >> $O
-	MODEM_AMD_LIB=$L timeout 300 python3 bench.py --steps 6 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 $X 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+	MODEM_AMD_LIB=$L timeout 300 python3 bench.py --full --steps 6 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 $X 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 done
 done
 cat $O

@@ -8,7 +8,7 @@ for lib in default $LIBS; do
 	L=$PWD/modem_amd/lib/variants/libofdmrx_$lib.so; [ $lib = default ] && L=$PWD/modem_amd/lib/libofdmrx.so
 	for m in ${MODES:-6 7 8 9 10 11 12 13}; do
 		echo -n "[$lib --mode $m] " >> $O
-		MODEM_AMD_LIB=$L timeout 600 python3 bench.py --steps 4 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --mode $m 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+		MODEM_AMD_LIB=$L timeout 600 python3 bench.py --full --steps 4 --warmup 2 --cpu-frames 0 --host-frames 0 --scl-steps 0 --mode $m 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 	done
 done
 cat $O

@@ -10,7 +10,7 @@ for lib in default polar4 polar3; do
 	for wpc in 16 12; do
 		[ $lib = polar3 ] && [ $wpc = 16 ] && continue
 		echo -n "$db dB $lib OFDMRX_POLAR_WPC=$wpc: " >> $O
-		MODEM_AMD_LIB=$L OFDMRX_POLAR_WPC=$wpc OFDMRX_NO_CERT=1 OFDMRX_NO_SC=1 timeout 300 python3 bench.py --noise-db $db --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+		MODEM_AMD_LIB=$L OFDMRX_POLAR_WPC=$wpc OFDMRX_NO_CERT=1 OFDMRX_NO_SC=1 timeout 300 python3 bench.py --full --noise-db $db --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 	done
 done
 done

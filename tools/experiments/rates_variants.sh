@@ -10,7 +10,7 @@ for lib in default $1; do
 	for rate in ${RATES:-8000 16000 44100 48000}; do
 		n=4096; [ $rate -le 16000 ] && n=8192
 		echo -n "$lib $rate one chunk ($n) alone: " >> $O
-		MODEM_AMD_LIB=$L OFDMRX_NO_OVERLAP=1 timeout 600 python3 bench.py --rate $rate --frames $n --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+		MODEM_AMD_LIB=$L OFDMRX_NO_OVERLAP=1 timeout 600 python3 bench.py --full --rate $rate --frames $n --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 	done
 done
 cat $O

@@ -14,6 +14,6 @@ for spec in default $1; do
 	lib=${spec%%:*}; envs=""; [ "$spec" != "$lib" ] && envs=${spec#*:}
 	L=$PWD/modem_amd/lib/variants/libofdmrx_$lib.so; [ $lib = default ] && L=$PWD/modem_amd/lib/libofdmrx.so
 	echo -n "$spec: " >> $O
-	env MODEM_AMD_LIB=$L $envs timeout 400 python3 bench.py --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 3 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
+	env MODEM_AMD_LIB=$L $envs timeout 400 python3 bench.py --full --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 3 2>&1 | tail -1 | python3 -c "$pick" >> $O 2>&1
 done
 cat $O

@@ -10,6 +10,6 @@ for k in ("value_config3", "value_noise_m20", "value_mono"):
     if isinstance(l, dict):
         t = l.get("value_two_lanes") or {}
         print(k, round(l["value"]), "two lanes", round(t.get("value", 0)), "routes", l.get("routes"), "stage ms", {a: round(b, 3) for a, b in l.get("stage_ms_per_step", {}).items()})'
-timeout 900 python3 bench.py --steps 4 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 2>&1 | tail -1 > gpurun_out/sc_quick_bench.json
-python3 -c "$pick" < gpurun_out/sc_quick_bench.json >> $O 2>&1
+timeout 900 python3 bench.py --full --steps 4 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 2>&1 | tail -1 > ${O%.txt}_bench.json
+python3 -c "$pick" < ${O%.txt}_bench.json >> $O 2>&1
 cat $O

@@ -18,14 +18,14 @@ echo "# pass A on the micro-benchmark: rocprofv3 --pmc $A -- /tmp/ubench_issue" 
 rocprofv3 --pmc $A -d /tmp/pmc_ub -o x -- /tmp/ubench_issue > /dev/null 2>&1
 python3 $R/tools/pmc_kernel.py $(find /tmp/pmc_ub -name "*.db" | head -1) "k<" | sed "s/^/[ubench] /" >> $S 2>&1
 export OFDMRX_NO_OVERLAP=1
-BN="python3 $R/bench.py --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 --frames 16384 --steps 1 --warmup 0"
+BN="python3 $R/bench.py --full --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 --frames 16384 --steps 1 --warmup 0"
 for mode in cert sc; do
 	X=""; [ $mode = sc ] && X="--noise-db -20"
 	i=0
 	for c in "$A" "$B" "GRBM_GUI_ACTIVE GRBM_COUNT" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_WRREQ_64B_sum" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_WRREQ_STALL_sum TCC_TAG_STALL_sum" "TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_WRREQ_LEVEL_sum TCC_BUSY_sum TCC_CYCLE_sum" "TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCR_TCP_STALL_CYCLES_sum"; do
 		i=$((i + 1))
 		[ $mode = cert ] && [ $i -gt 3 ] && continue          # (the memory-side passes: the -20 dB run only)
-		echo "# [$mode] rocprofv3 --pmc $c -- python3 bench.py --frames 16384 --steps 1 --warmup 0 $X (kernels back to back)" >> $S
+		echo "# [$mode] rocprofv3 --pmc $c -- python3 bench.py --full --frames 16384 --steps 1 --warmup 0 $X (kernels back to back)" >> $S
 		d=/tmp/pmc_${mode}_$i
 		rocprofv3 --pmc $c -d $d -o x -- $BN $X > /dev/null 2>&1
 		python3 $R/tools/pmc_kernel.py $(find $d -name "*.db" | head -1) rx:: | grep -E "k_theil_sen |k_demod|k_back|k_sync<|k_sc<|k_sc_finish|k_header" | sed "s/^/[$mode] /" >> $S 2>&1

@@ -5,8 +5,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import modem_amd
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
-fx = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "base_frames_2ch.npz"))
-base, pay = fx["pcm"], fx["payload"]
+fx = [np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "base_frames_2ch_%d.npz" % i)) for i in range(2)]
+base, pay = np.concatenate([f["pcm"] for f in fx]), np.concatenate([f["payload"] for f in fx])
 batch = np.ascontiguousarray(base[np.arange(n) % base.shape[0]])
 rx = modem_amd.Receiver(device=0)
 out, res = rx.decode(batch[:256])

@@ -13,8 +13,8 @@ S=$G/${TAG}_summary.txt; : > $S
 make -C modem_amd/csrc -q all && echo "# library up to date with sources" >> $S || echo "# STALE LIBRARY" >> $S
 cd /tmp; export TMPDIR=/tmp
 export OFDMRX_NO_TAIL_SPLIT=1     # (every launch of the profiled runs a whole chunk of 8192 frames: the per-launch figures below divide by the launches)
-B="python3 $R/bench.py --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0"
-echo "# $TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0   (default: pipeline, syndrome certificate on)" >> $S
+B="python3 $R/bench.py --full --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0"
+echo "# $TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 2 --warmup 1 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0   (default: pipeline, syndrome certificate on)" >> $S
 rocprofv3 --kernel-trace --stats -d /tmp/prof_e -o trace -- $B --steps 2 --warmup 1 > $G/${TAG}_bench_n1_under_profiler.json 2>/dev/null
 python3 $R/profiles/summarize.py $(find /tmp/prof_e -name "*.db" | head -1) >> $S 2>&1
 echo "# same with OFDMRX_NO_OVERLAP=1 (every kernel alone on the device)" >> $S
@@ -35,7 +35,7 @@ for mode in cert scl sc; do
 	unset OFDMRX_NO_CERT OFDMRX_NO_SC; X=""
 	[ $mode = scl ] && export OFDMRX_NO_CERT=1 OFDMRX_NO_SC=1
 	[ $mode = sc ] && X="--noise-db -20"
-	echo "# PMC passes [$mode]: rocprofv3 --pmc <counters> -- python3 bench.py --frames 16384 --steps 1 --warmup 0 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 $X (OFDMRX_NO_OVERLAP=1$([ $mode = scl ] && echo ' OFDMRX_NO_CERT=1 OFDMRX_NO_SC=1'))" >> $S
+	echo "# PMC passes [$mode]: rocprofv3 --pmc <counters> -- python3 bench.py --full --frames 16384 --steps 1 --warmup 0 --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 $X (OFDMRX_NO_OVERLAP=1$([ $mode = scl ] && echo ' OFDMRX_NO_CERT=1 OFDMRX_NO_SC=1'))" >> $S
 	for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_INSTS SQ_WAIT_INST_ANY"; do
 		d=/tmp/pmc_${mode}_$(echo $c | tr ' ' '_')
 		rocprofv3 --pmc $c -d $d -o x -- $B --frames 16384 --steps 1 --warmup 0 $X > /dev/null 2>&1
@@ -63,7 +63,7 @@ hipcc -w --offload-arch=gfx950 -O3 $R/tools/ubench_issue.hip -o /tmp/ubench_issu
 head -4 $G/${TAG}_issue_rates_ubench.txt >> $S
 cd $R
 unset OFDMRX_NO_TAIL_SPLIT
-python3 bench.py > $G/${TAG}_bench_n1.json 2>/dev/null
+python3 bench.py --full > $G/${TAG}_bench_n1.json 2>/dev/null
 R=$R python3 - "$S" "$G/${TAG}_traffic.json" "$G/${TAG}_issue_rates_ubench.txt" <<'PY'
 import hashlib, json, os, re, sys
 txt = open(sys.argv[1]).read()
@@ -89,7 +89,7 @@ ub = open(sys.argv[3]).read() if len(sys.argv) > 3 and os.path.exists(sys.argv[3
 mu = min(((float(a), float(g)) for w, a, g in re.findall(r"^v_fma_f32 x8 independent\s+waves/SIMD=(\d)\s+ns/valu/SIMD: in-kernel ([0-9.]+).*?clock=([0-9.]+) GHz", ub, re.M) if 2 <= int(w) <= 4), default=None)
 out = {"frames_per_launch": 8192, "valu_ns_per_inst_per_simd": mu[0] if mu else None, "sclk_GHz_measured": mu[1] if mu else None, "fetch_scale": 2097152.0 / calib("calib_read", "FETCH_SIZE"), "write_scale": 2097152.0 / calib("calib_write", "WRITE_SIZE"),
        "kernels": {},
-       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --frames 16384 --steps 1 --warmup 0 --cpu-frames 0 "
+       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --frames 16384 --steps 1 --warmup 0 --cpu-frames 0 "
                  "--host-frames 0 --scl-steps 0 --leg-steps 0, kernels back to back (k_polar: with OFDMRX_NO_CERT=1; k_sc: with --noise-db -20); KiB per launch of 8192 frames; scales = true bytes / counted "
                  "bytes of tools/pmc_calib.hip (2 GiB per kernel, one dword per lane) in the same session; valu_insts = SQ_INSTS_VALU (wave instructions) per launch"}
 for st, (mode, kern, src) in stages.items():

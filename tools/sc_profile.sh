@@ -3,7 +3,7 @@
 TAG=${1:-r05_sc}; DB=${2:--20}; R=$PWD; G=$R/gpurun_out; mkdir -p $G
 S=$G/${TAG}_sc_summary.txt; : > $S
 cd /tmp; export TMPDIR=/tmp
-B="python3 $R/bench.py --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 --noise-db $DB"
+B="python3 $R/bench.py --full --cpu-frames 0 --host-frames 0 --scl-steps 0 --leg-steps 0 --noise-db $DB"
 echo "# $TAG: rocprofv3 --kernel-trace --stats -- $B --steps 2 --warmup 1 (OFDMRX_NO_OVERLAP=1: kernels back to back)" >> $S
 OFDMRX_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats -d /tmp/prof_sc -o trace -- $B --steps 2 --warmup 1 > $G/${TAG}_sc_bench_under_profiler.json 2>/dev/null
 python3 $R/profiles/summarize.py $(find /tmp/prof_sc -name "*.db" | head -1) >> $S 2>&1
