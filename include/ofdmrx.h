@@ -47,8 +47,9 @@ extern "C" {
  *      that path (same outputs)
  *   6: ofdmrx_config.flags bit 3 (OFDMRX_FLAG_TWO_LANES): a device-entry call of four chunks or more runs its second half through a
  *      second pipeline beside the first (same outputs; the handle then holds the state of two pipelines); the list-1 pass takes whole
- *      residencies of its decoders and leaves the rest to the next chunk's run (same outputs) */
-#define OFDMRX_ABI_MINOR 6
+ *      residencies of its decoders and leaves the rest to the next chunk's run (same outputs)
+ *   7: ofdmrx_decode_stream, ofdmrx_decode_stream_device (every preamble of one recording in one call), ofdmrx_debug_stream_edges */
+#define OFDMRX_ABI_MINOR 7
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
 #define OFDMRX_CODE_LEN 65536         /* decode.cc:309  code_order 16 */
@@ -195,6 +196,40 @@ int ofdmrx_decode_batch(ofdmrx_handle *h, const void *samples, int sample_format
 int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_samples, int sample_format, int channels,
 	size_t samples_per_frame, size_t frame_stride_bytes, size_t n_frames,
 	const int32_t *d_skip_counts, uint8_t *d_payload_out, ofdmrx_frame_result *d_results);
+
+/*
+ * Stream decode (revision 1.7): every frame of ONE recording - n_samples sample frames of `channels` interleaved values, as a WAV
+ * body holds them (`encode OUT ... file1 .. fileN` writes up to 4096 payloads back to back, a receiver records minutes) - in one
+ * call.  Record k is what `decode OUT INPUT k` gives on the same samples: the payload and the result ofdmrx_decode_batch returns for
+ * that stream with skip_counts = {k}.  Record k belongs to the (k+1)-th preamble the Schmidl-Cox search accepts (decode.cc:390-448);
+ * a preamble whose header then fails is a record too (status OSD_ERROR .. BAD_CALLSIGN: the SKIP loop counts it).  sc_start is the
+ * preamble's stream index, n_sync_rejects counts the rejected triggers from the start of the stream.
+ * *n_preambles: the number of accepted preambles (the smallest k for which `decode` would report NO_SYNC); only
+ * min(*n_preambles, max_frames) records are written (payload_out: 5380 bytes each, results: one each) and nothing past them.
+ * payload_out / results may be NULL when max_frames is 0.  n_samples: 1 .. 0x7fffffff / 2; formats, channels, alignment and error
+ * codes as ofdmrx_decode_batch.  The handle's flags hold (KEEP_RAW_CONS, SCL_ALWAYS, NO_SC; TWO_LANES is ignored), Es/N0 rows
+ * (ofdmrx_set_esn0_rows) are written for each record; the attempt log is NOT written (each record is one preamble's outcome).
+ * ofdmrx_get_timing, ofdmrx_last_chunk_first_frame, the stage taps (frame = record index relative to the last chunk),
+ * ofdmrx_list_decoded_frames and ofdmrx_sc_decided_frames describe the call as they do a batch call; the stream-wide DC-blocker
+ * pass of mono input is OFDMRX_T_FRONT, the scan and accept OFDMRX_T_SYNC.
+ * The scan is tiled: its timing metric comes from window sums each tile of 4096 samples forms in double, where the
+ * batch scan carries running sums from the start of the frame - the fp32 metric values agree but for a last-bit rounding on a
+ * boundary (the reference's own serial fp32 sums differ from both by more).
+ * HOST pointers; blocks until done.
+ */
+int ofdmrx_decode_stream(ofdmrx_handle *h, const void *samples, int sample_format, int channels, size_t n_samples,
+	size_t max_frames, uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_preambles);
+/* the same with the samples in DEVICE memory, on the handle's stream; outputs in device memory or, both of them, pinned host memory
+ * (as ofdmrx_decode_batch_device).  The call reads the preamble count back to the host once, after the scan, to plan the records into
+ * chunks: that is its one host synchronisation, so it cannot be captured into a graph.  (A stream with more falling edges of the
+ * timing metric than the scan's edge buffer holds - about one per 2048 samples - is scanned once more after the buffer has grown.) */
+int ofdmrx_decode_stream_device(ofdmrx_handle *h, const void *d_samples, int sample_format, int channels, size_t n_samples,
+	size_t max_frames, uint8_t *d_payload_out, ofdmrx_frame_result *d_results, size_t *n_preambles);
+/* test entry: the trigger logic of the stream scan (decode.cc:93-116, as tiles and a scan over them) on a caller-given timing
+ * sequence of n values, with the thresholds and match_len of the handle's rate: the falling edges (t_edge), the first index of the
+ * maximum of each run (t_max) and index_max; at most max_edges of them are written, *n_edges counts all.  HOST pointers. */
+int ofdmrx_debug_stream_edges(ofdmrx_handle *h, const float *timing, size_t n, size_t max_edges,
+	int64_t *t_edge, int64_t *t_max, int32_t *index_max, size_t *n_edges);
 
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);

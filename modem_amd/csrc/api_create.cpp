@@ -158,7 +158,9 @@ extern "C" void ofdmrx_destroy(ofdmrx_handle *h)
 		}
 	for (DevBuf *b : { &h->st, &h->hdr_soft, &h->cons, &h->slope, &h->yint, &h->precision, &h->slot_of, &h->res, &h->payload, &h->payload2, &h->res2,
 			&h->chunk_flags, &h->soft, &h->s_ctl, &h->s_slots, &h->s_llr, &h->s_cw, &h->s_xw, &h->s_stat, &h->sc_soft, &h->q_ctl, &h->q_slots, &h->q_llr, &h->q_hard, &h->q_metric, &h->q_lane_mesg, &h->rot_tap, &h->tx_code, &h->tx_rowsym,
-			&h->tx_tdom, &h->tx_big, &h->esn0_dev, &h->esn0_dev2, &h->att_dev, &h->att_dev2, &h->attc_dev, &h->attc_dev2, &h->dc, &h->z, &h->in_stage, &h->in_stage2, &h->skip_stage, &h->carr, &h->sc_scratch })
+			&h->tx_tdom, &h->tx_big, &h->esn0_dev, &h->esn0_dev2, &h->att_dev, &h->att_dev2, &h->attc_dev, &h->attc_dev2, &h->dc, &h->z, &h->in_stage, &h->in_stage2, &h->skip_stage, &h->carr, &h->sc_scratch,
+			&h->sx_in, &h->sx_z, &h->sx_ck, &h->sx_dc_end, &h->sx_dc_in, &h->sx_fn, &h->sx_carry, &h->sx_edges, &h->sx_counts, &h->sx_rec, &h->sx_pay,
+			&h->sx_res, &h->sx_esn0, &h->sx_timing })
 		b->release();
 	for (void *p : h->table_allocs)
 		(void)hipFree(p);

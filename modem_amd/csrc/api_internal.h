@@ -190,6 +190,9 @@ struct ofdmrx_handle {
 	int lanes = 1;
 	size_t split_at = 0;      // frames of the last call that went through this handle's own pipeline (0: all of them)
 	hipEvent_t ev_lane_in = nullptr, ev_lane_done = nullptr;
+	// stream decode (api_stream.cpp): scratch kept between calls, grown on demand
+	DevBuf sx_in, sx_z, sx_ck, sx_dc_end, sx_dc_in, sx_fn, sx_carry, sx_edges, sx_counts, sx_rec, sx_pay, sx_res, sx_esn0, sx_timing;
+	long sx_edge_cap = 0;     // edges the edge buffer holds
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -210,3 +213,8 @@ static int upload(ofdmrx_handle *h, const std::vector<T> &v, const T **out)
 int ensure_capacity(ofdmrx_handle *h, int n, bool mono, long samples);                    // api_create.cpp
 int host_wait(ofdmrx_handle *h);                                                          // api_create.cpp
 void run_sc_pass(ofdmrx_handle *h, hipStream_t s, int n, bool force = true, int chunk_seq = 0);   // api_pipeline.cpp
+int ensure_events(ofdmrx_handle *h, size_t need);                                           // api_pipeline.cpp: the call's event pool
+size_t mark(ofdmrx_handle *h, hipStream_t on = nullptr);                                    // ... one event recorded on `on`
+// the chunk pipeline for n records of a stream decode: every frame is the whole stream fb (stride 0), record k starts from
+// d_records[k] (header, demod, ...); device or pinned host outputs like ofdmrx_decode_batch_device; keeps the call's events so far
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, uint8_t *d_payload, ofdmrx_frame_result *d_results);

@@ -3,7 +3,7 @@
 
 // Events come from a pool that is sized BEFORE a call enqueues anything (ensure_events), so recording one can never
 // allocate and an index is always valid; a failed hipEventRecord is remembered and fails the call at its end.
-static int ensure_events(ofdmrx_handle *h, size_t need)
+int ensure_events(ofdmrx_handle *h, size_t need)
 {
 	while (h->ev_pool.size() < need) {
 		hipEvent_t e;
@@ -12,7 +12,7 @@ static int ensure_events(ofdmrx_handle *h, size_t need)
 	}
 	return 0;
 }
-static size_t mark(ofdmrx_handle *h, hipStream_t on = nullptr)
+size_t mark(ofdmrx_handle *h, hipStream_t on)
 {
 	if (h->ev_used >= h->ev_pool.size()) {                // cannot happen: the pool was sized for the whole call
 		h->sticky = hipErrorOutOfMemory;
@@ -32,11 +32,18 @@ static size_t events_per_chunk(int max_skip) { return 32 + 16 * (size_t)(max_ski
 //   front2  Theil-Sen
 //   back    k_back: rotation, SNR, certificate / LLRs into the list decoder's queue; k_queue_snap
 // D9 + D10 for the queued frames = a flush (run_flush).
+static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const SyncState *seed, size_t *t_begin,
+	size_t wait_before_sync, size_t *ev_after_sync);
 // wait_before_sync (event index or -1): the first sync launch waits for it; *ev_after_sync (nullable) receives the event
 // recorded right after that launch - the pipeline gives the scan a slot of its own between two list-decoder launches.
+// seed (nullable, stream decode): the chunk's frames start from these SyncStates - preambles already found and accepted, as a
+// round with skip_left = 0 leaves them - instead of the sync rounds: header once, then demod.
 static int run_front1(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const int32_t *d_skip, int max_skip,
-	size_t *t_begin, Attempt *d_att, int32_t *d_att_counts, size_t wait_before_sync = (size_t)-1, size_t *ev_after_sync = nullptr)
+	size_t *t_begin, Attempt *d_att, int32_t *d_att_counts, size_t wait_before_sync = (size_t)-1, size_t *ev_after_sync = nullptr,
+	const SyncState *seed = nullptr)
 {
+	if (seed)
+		return run_front1_seeded(h, s, fb, n, seed, t_begin, wait_before_sync, ev_after_sync);
 	const bool mono = fb.channels == 1;
 	SyncState *st = h->st.as<SyncState>();
 	cf *z = mono ? h->z.as<cf>() : nullptr;
@@ -82,6 +89,41 @@ static int run_front1(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, con
 	HIP_OK(hipGetLastError());
 	h->last_n = n;
 	h->last_mono = mono;
+	h->last_spf = fb.samples_per_frame;
+	h->last_fb = fb;
+	return 0;
+}
+
+// run_front1 for a chunk of records of a stream decode (api_stream.cpp): the records' SyncStates, header + OSD, demod
+static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const SyncState *seed, size_t *t_begin,
+	size_t wait_before_sync, size_t *ev_after_sync)
+{
+	SyncState *st = h->st.as<SyncState>();
+	const MonoArgs ma = mono_args(h->host.front, nullptr, 0);
+	size_t e0 = mark(h, s);
+	launch_init_sync(s, n, st, nullptr, h->chunk_flags.as<int>(), nullptr);
+	HIP_OK(hipMemcpyAsync(st, seed, (size_t)n * sizeof(SyncState), hipMemcpyDeviceToDevice, s));
+	if (wait_before_sync != (size_t)-1)
+		HIP_OK(hipStreamWaitEvent(s, h->ev_pool[wait_before_sync], 0));
+	size_t b = mark(h, s);
+	if (ev_after_sync)
+		*ev_after_sync = b;
+	{
+		Range r("ofdmrx:header_osd");
+		launch_header(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->hdr_soft.as<int8_t>(), nullptr, nullptr);
+	}
+	size_t c = mark(h, s);
+	h->spans.push_back({ OFDMRX_T_HEADER, b, c });
+	{
+		Range r("ofdmrx:demod");
+		launch_demod(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
+	}
+	size_t d = mark(h, s);
+	h->spans.push_back({ OFDMRX_T_DEMOD, c, d });
+	*t_begin = e0;
+	HIP_OK(hipGetLastError());
+	h->last_n = n;
+	h->last_mono = false;
 	h->last_spf = fb.samples_per_frame;
 	h->last_fb = fb;
 	return 0;
@@ -263,7 +305,7 @@ struct PipeHooks {
 //   entry's output staging of that parity.
 // A call of one chunk (and OFDMRX_NO_OVERLAP=1, the profiler's setting: every kernel alone on the machine) runs all of it on A.
 static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &plan, int fmt, int channels, size_t spf, size_t stride,
-	const int32_t *d_skip, int max_skip)
+	const int32_t *d_skip, int max_skip, const SyncState *seed = nullptr)
 {
 	const size_t n_chunks = plan.count(), NONE = (size_t)-1;
 	int r = ensure_events(h, h->ev_used + n_chunks * events_per_chunk(max_skip) + 8);
@@ -315,7 +357,7 @@ static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &pla
 		if (att && overlap && c >= 2)                             // (host entry: the log's staging of this parity has left with chunk c - 2)
 			HIP_OK(hipStreamWaitEvent(sa, h->ev_pool[ev_fin[c - 2]], 0));
 		r = run_front1(h, sa, fb, n, d_skip ? d_skip + plan.first(c) : nullptr, max_skip, &t0s[c], att, att_counts,
-			(scan_slot && c >= 2) ? ev_polar[c - 2] : NONE, &ev_sync);
+			(scan_slot && c >= 2) ? ev_polar[c - 2] : NONE, &ev_sync, seed ? seed + plan.first(c) : nullptr);
 		h->last_first = plan.first(c);
 		if (!r && overlap && c >= 1)                              // flush(c - 1): its LLRs are in the queue, sync(c) is on its way
 			r = flush(c - 1, ev_sync);
@@ -368,8 +410,11 @@ static int finish_call(ofdmrx_handle *h, int r)
 	return r;
 }
 
+// seed (nullable): the frames are records of a stream decode that start from these SyncStates (run_front1_seeded); fresh = false:
+// the call's events and timing spans so far (the stream scan's) are kept
 static int decode_device_lane(ofdmrx_handle *h, const void *d_samples, int fmt, int channels,
-	size_t spf, size_t stride, size_t n_frames, const int32_t *d_skip, uint8_t *d_payload, ofdmrx_frame_result *d_results)
+	size_t spf, size_t stride, size_t n_frames, const int32_t *d_skip, uint8_t *d_payload, ofdmrx_frame_result *d_results,
+	const SyncState *seed = nullptr, bool fresh = true)
 {
 	int r = 0;
 	int max_skip = 0;
@@ -383,8 +428,10 @@ static int decode_device_lane(ofdmrx_handle *h, const void *d_samples, int fmt, 
 		if (max_skip < 0)
 			return max_skip;
 	}
-	h->ev_used = 0;
-	h->spans.clear();
+	if (fresh) {
+		h->ev_used = 0;
+		h->spans.clear();
+	}
 	const int out_kind = host_pinned(d_payload), res_kind = host_pinned(d_results);
 	if (out_kind < 0 || res_kind < 0 || out_kind != res_kind)
 		return OFDMRX_E_ARG;
@@ -462,7 +509,13 @@ static int decode_device_lane(ofdmrx_handle *h, const void *d_samples, int fmt, 
 		if (r)
 			return r;
 	}
-	return finish_call(h, run_pipeline(h, hooks, plan, fmt, channels, spf, stride, d_skip, max_skip));
+	return finish_call(h, run_pipeline(h, hooks, plan, fmt, channels, spf, stride, d_skip, max_skip, seed));
+}
+
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, uint8_t *d_payload, ofdmrx_frame_result *d_results)
+{
+	return decode_device_lane(h, fb.samples, fb.fmt, fb.channels, (size_t)fb.samples_per_frame, fb.frame_stride_bytes, n, nullptr,
+		d_payload, d_results, d_records, false);
 }
 
 extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels,

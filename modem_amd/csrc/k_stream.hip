@@ -1,0 +1,510 @@
+// k_stream.hip -- the stream scan: every Schmidl-Cox preamble of one long recording (decode.cc:84-151 over the whole stream), with
+// all CUs on it.  No stage walks the stream in one wave or one workgroup:
+//   k_sdc_tile / k_sdc_scan   mono input: the DC blocker's kept states (k_mono_carries' layout) by tiles from a zero state, a scan of
+//                             the tile carries with the a^4096 weights, and a fix-up
+//   k_stream_tile<.., false>  per tile of STREAM_TILE sample times: the timing metric (decode.cc:86-90) from window sums the tile
+//                             forms itself in double, then what the tile does to the trigger state for either incoming Schmitt state
+//   k_stream_fn_scan          one workgroup scans those per-tile functions (a tile is 4096 samples: 1/4096 of the stream)
+//   k_stream_tile<.., true>   the tiles again, now with their incoming state: falling edges, t_max, index_max, in stream order
+//   k_stream_accept           decode.cc:110-151 for every edge (sc_accept_wg, shared with k_sync_accept)
+//   k_stream_records          a scan over accept / reject: record indices, cumulative rejects, the SyncState of every record
+#include "dev_common.h"
+#include "kernels.h"
+#include "mono_front.h"
+#include "sync_accept.h"
+
+namespace rx {
+
+// inclusive Hillis-Steele scan over NT threads in LDS (sh: NT entries); returns this thread's inclusive value, sh holds them all
+// afterwards (the caller synchronises before reusing sh)
+template <int NT, class T, class Op>
+__device__ __forceinline__ T block_scan_incl(T v, T *sh, int tid, Op op)
+{
+	sh[tid] = v;
+	__syncthreads();
+	for (int k = 1; k < NT; k <<= 1) {
+		T o = sh[tid >= k ? tid - k : 0];
+		__syncthreads();
+		if (tid >= k) {
+			v = op(o, v);
+			sh[tid] = v;
+		}
+		__syncthreads();
+	}
+	return v;
+}
+
+// ---------------------------------------------------------------- mono: the DC blocker over the whole stream
+struct Affine { double v, w; };                               // x -> w x + v
+__device__ __forceinline__ Affine aff_then(Affine l, Affine r) { return Affine{ r.v + r.w * l.v, l.w * r.w }; }
+
+// PASS 0: the state each tile ends on from a zero state; PASS 1: the kept states from the tile's true entry state tile_in[t]
+template <int PASS>
+__global__ __launch_bounds__(256) void k_sdc_tile(FrameBatch fb, FrontCoef co, double *__restrict__ tile_end, const double *__restrict__ tile_in,
+	double *__restrict__ ck, int ck_n)
+{
+	const int tid = threadIdx.x;
+	const long t = blockIdx.x;
+	MonoFrame fr{ (const char *)fb.samples, fb.fmt, fb.samples_per_frame, nullptr };
+	__shared__ Affine sh[256];
+	const double a = (double)co.dc_a, g = (double)co.dc_b * (1.0 - a) * (double)fr.scale();
+	const long s0 = t * 4096 + (long)tid * 16;
+	double sl = 0.0;
+	float x8[8];
+	fr.load8(s0, x8);
+	for (int i = 0; i < 8; ++i)
+		sl = a * sl + g * (double)x8[i];
+	fr.load8(s0 + 8, x8);
+	for (int i = 0; i < 8; ++i)
+		sl = a * sl + g * (double)x8[i];
+	const Affine me = block_scan_incl<256>(Affine{ sl, mono_pow(a, 16) }, sh, tid, aff_then);
+	if (PASS == 0) {
+		if (tid == 255)
+			tile_end[t] = me.v;
+	} else {
+		const double s_true = me.v + mono_pow(a, 16 * (tid + 1)) * tile_in[t];
+		const long m = t * (4096 / MONO_CK) + (tid >> 2);    // this thread ends sample 16 tid + 15 of its tile
+		if ((tid & 3) == 3 && m < ck_n)
+			ck[m] = s_true;
+	}
+}
+
+// the tiles' entry states C_0 = 0, C_{t+1} = tile_end[t] + a^4096 C_t: one workgroup, a range of tiles per thread composed as an
+// affine map, an exclusive scan of the maps, then each range in turn
+__global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *__restrict__ tile_end, double *__restrict__ tile_in, long ntiles)
+{
+	const int tid = threadIdx.x;
+	__shared__ Affine sh[1024];
+	const double A = mono_pow((double)co.dc_a, 4096);
+	const long per = (ntiles + 1023) / 1024, k0 = (long)tid * per, k1 = k0 + per < ntiles ? k0 + per : ntiles;
+	Affine f{ 0.0, 1.0 };
+	for (long k = k0; k < k1; ++k)
+		f = aff_then(f, Affine{ tile_end[k], A });
+	block_scan_incl<1024>(f, sh, tid, aff_then);
+	double c = tid ? sh[tid - 1].v : 0.0;                     // the maps applied to C_0 = 0
+	for (long k = k0; k < k1; ++k) {
+		tile_in[k] = c;
+		c = tile_end[k] + A * c;
+	}
+}
+
+void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck)
+{
+	const long ntiles = (fb.samples_per_frame + 4095) / 4096;
+	const int ck_n = mono_ck_per_frame(fb.samples_per_frame);
+	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
+	hipLaunchKernelGGL(k_sdc_scan, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles);
+	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
+}
+
+// ---------------------------------------------------------------- the trigger as a scan
+// comb: the running maximum of decode.cc:99-102 - the earlier one (l) keeps a tie
+__device__ __forceinline__ void comb(float &m, long long &i, float m2, long long i2)
+{
+	if (m < m2) {
+		m = m2;
+		i = i2;
+	}
+}
+struct Seg { int has; float m; long long i; };                // since the last falling edge (has: there was one)
+__device__ __forceinline__ Seg seg_then(Seg l, Seg r)
+{
+	if (r.has)
+		return r;
+	Seg o = l;
+	comb(o.m, o.i, r.m, r.i);
+	return o;
+}
+__device__ __forceinline__ int last_then(int l, int r) { return r >= 0 ? r : l; }
+__device__ __forceinline__ long long add_ll(long long l, long long r) { return l + r; }
+
+struct TrigShared {
+	int last[256];
+	Seg seg[256];
+	long long cnt[256];
+};
+constexpr int SPT = STREAM_TILE / 256;                        // sample times per thread
+
+// The tile's trigger given the state entering it (s_in, running maximum m_in / i_in).  cls: +1 above hi (sets), -1 below lo (clears),
+// 0 holds (and every time at or past the end of the stream).  Out: the state entering this thread, the running maximum entering it,
+// the falling edges of the threads before it; tile totals in *s_out / *seg_out / *n_out (every thread).
+__device__ __forceinline__ void tile_trigger(TrigShared &sh, const int (&cls)[SPT], const float (&v)[SPT], long long t0, int tid,
+	int s_in, float m_in, long long i_in, int &s_thr, Seg &seg_thr, long long &edges_before, int &s_out, Seg &seg_out, long long &n_out)
+{
+	int last = -1;
+	for (int j = 0; j < SPT; ++j)
+		if (cls[j])
+			last = cls[j] > 0;
+	const int incl = block_scan_incl<256>(last, sh.last, tid, last_then);
+	const int excl = tid ? sh.last[tid - 1] : -1;
+	s_thr = excl >= 0 ? excl : s_in;
+	const int tile_last = sh.last[255];
+	s_out = tile_last >= 0 ? tile_last : s_in;
+	(void)incl;
+	__syncthreads();
+	int s = s_thr;
+	Seg mine{ 0, -INFINITY, -1 };
+	long long ne = 0;
+	for (int j = 0; j < SPT; ++j) {
+		if (cls[j] < 0 && s == 1) {                               // a falling edge: its run ends here (the edge sample belongs to it)
+			++ne;
+			mine = Seg{ 1, -INFINITY, -1 };
+		} else {
+			comb(mine.m, mine.i, v[j], t0 + j);
+		}
+		if (cls[j])
+			s = cls[j] > 0;
+	}
+	block_scan_incl<256>(mine, sh.seg, tid, seg_then);
+	const Seg before = tid ? sh.seg[tid - 1] : Seg{ 0, -INFINITY, -1 };
+	seg_thr = seg_then(Seg{ 0, m_in, i_in }, before);
+	seg_out = seg_then(Seg{ 0, m_in, i_in }, sh.seg[255]);
+	__syncthreads();
+	block_scan_incl<256>(ne, sh.cnt, tid, add_ll);
+	edges_before = tid ? sh.cnt[tid - 1] : 0;
+	n_out = sh.cnt[255];
+	__syncthreads();
+}
+
+// EMIT = false: the timing metric of the tile and its function (StreamFn) for both incoming states; EMIT = true: the same metric and
+// the tile's falling edges from its incoming StreamCarry.  GIVEN: the metric is a caller's sequence (ofdmrx_debug_stream_edges).
+template <int RATE, bool GIVEN, bool EMIT>
+__global__ __launch_bounds__(256) void k_stream_tile(FrameBatch fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
+	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap)
+{
+	typedef RateCfg<RATE> RC;
+	constexpr int HS = RC::HS, GL = RC::GL, ML = RC::MATCH_LEN, MD = RC::MATCH_DEL;
+	constexpr int D = RC::BUFFER_LEN - 1 - (RC::SEARCH_POS + HS);   // P at time t: its newest pair is (t - D, t - D + HS)
+	constexpr int L = STREAM_TILE + ML - 1, PM = (L + 255) / 256;
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const long long T0 = (long long)blockIdx.x * STREAM_TILE;
+	const float lo = (float)(0.17 * ML), hi = (float)(0.19 * ML);   // decode.cc:76
+	__shared__ TrigShared tsh;
+	float v[SPT];
+	if constexpr (GIVEN) {
+		for (int j = 0; j < SPT; ++j) {
+			const long long t = T0 + tid * SPT + j;
+			v[j] = t < n ? given[t] : 0.f;
+		}
+	} else {
+		// decode.cc:86-90 at the times tm0 .. T0 + STREAM_TILE - 1: P and R as window sums in double - direct sums at tm0 - 1, then the
+		// (in - out) differences, prefix-summed over the tile - and m = |P|^2 / R^2 in the reference's fp32 expression; timing = the
+		// sum of the last ML values of m in double, rounded once
+		__shared__ double Sd[L];
+		__shared__ double red[3][4];
+		__shared__ double3 sc3[256];
+		const SampleSrc src{ fb.samples, fb.fmt, fb.channels, n, nullptr };
+		const long long tm0 = T0 - (ML - 1);
+		double p0r = 0.0, p0i = 0.0, r0 = 0.0;
+		{
+			const long long a = tm0 - 1 - D;
+			for (int k = tid; k < HS; k += 256) {
+				const cf x = src.at(a - k), y = src.at(a - k + HS);
+				p0r += (double)x.re * y.re + (double)x.im * y.im;
+				p0i += (double)x.im * y.re - (double)x.re * y.im;
+			}
+			for (int k = tid; k < 2 * HS; k += 256) {
+				const cf x = src.at(a + HS - k);
+				r0 += (double)x.re * x.re + (double)x.im * x.im;
+			}
+			p0r = wave_sum_d(p0r);
+			p0i = wave_sum_d(p0i);
+			r0 = wave_sum_d(r0);
+			if (lane == 0) {
+				red[0][wave] = p0r;
+				red[1][wave] = p0i;
+				red[2][wave] = r0;
+			}
+			__syncthreads();
+			p0r = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+			p0i = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+			r0 = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+		}
+		double dr[PM], di[PM], dp[PM];
+		for (int e = 0; e < PM; ++e) {
+			const int idx = tid * PM + e;
+			double pr = 0.0, pi = 0.0, pp = 0.0;
+			if (idx < L) {
+				const long long a = tm0 + idx - D;
+				const cf zA = src.at(a - HS), zB = src.at(a), zC = src.at(a + HS);
+				const double inr = (double)zB.re * zC.re + (double)zB.im * zC.im;
+				const double ini = (double)zB.im * zC.re - (double)zB.re * zC.im;
+				const double outr = (double)zA.re * zB.re + (double)zA.im * zB.im;
+				const double outi = (double)zA.im * zB.re - (double)zA.re * zB.im;
+				const double pin = (double)zC.re * zC.re + (double)zC.im * zC.im;
+				const double pout = (double)zA.re * zA.re + (double)zA.im * zA.im;
+				pr = inr - outr;
+				pi = ini - outi;
+				pp = pin - pout;
+			}
+			dr[e] = (e ? dr[e - 1] : 0.0) + pr;
+			di[e] = (e ? di[e - 1] : 0.0) + pi;
+			dp[e] = (e ? dp[e - 1] : 0.0) + pp;
+		}
+		block_scan_incl<256>(make_double3(dr[PM - 1], di[PM - 1], dp[PM - 1]), sc3, tid,
+			[](double3 l, double3 r) { return make_double3(l.x + r.x, l.y + r.y, l.z + r.z); });
+		const double3 o = tid ? sc3[tid - 1] : make_double3(0.0, 0.0, 0.0);
+		__syncthreads();
+		const float min_R = 0.0001f * HS;                          // decode.cc:88
+		double cm = 0.0;
+		for (int e = 0; e < PM; ++e) {
+			const float Pre = (float)((p0r + o.x) + dr[e]), Pim = (float)((p0i + o.y) + di[e]);
+			float R = 0.5f * (float)((r0 + o.z) + dp[e]);
+			R = fmaxf(R, min_R);
+			const float mf = __fdiv_rn(__fadd_rn(__fmul_rn(Pre, Pre), __fmul_rn(Pim, Pim)), __fmul_rn(R, R));
+			cm += tid * PM + e < L ? (double)mf : 0.0;
+			dr[e] = cm;
+		}
+		block_scan_incl<256>(make_double3(cm, 0.0, 0.0), sc3, tid,
+			[](double3 l, double3 r) { return make_double3(l.x + r.x, 0.0, 0.0); });
+		const double om = tid ? sc3[tid - 1].x : 0.0;
+		for (int e = 0; e < PM; ++e)
+			if (tid * PM + e < L)
+				Sd[tid * PM + e] = om + dr[e];
+		__syncthreads();
+		for (int j = 0; j < SPT; ++j) {
+			const int idx = ML - 1 + tid * SPT + j;                 // t - tm0
+			v[j] = (float)(Sd[idx] - (idx >= ML ? Sd[idx - ML] : 0.0));
+		}
+	}
+	int cls[SPT];
+	const long long t0 = T0 + tid * SPT;
+	for (int j = 0; j < SPT; ++j)
+		cls[j] = t0 + j >= n ? 0 : v[j] > hi ? 1 : v[j] < lo ? -1 : 0;
+	int s_thr, s_out;
+	Seg seg_thr, seg_out;
+	long long before, n_out;
+	if constexpr (!EMIT) {
+		StreamFn f;
+		for (int s = 0; s < 2; ++s) {
+			tile_trigger(tsh, cls, v, t0, tid, s, -INFINITY, -1, s_thr, seg_thr, before, s_out, seg_out, n_out);
+			f.s_out[s] = s_out;
+			f.has[s] = n_out > 0;
+			f.n[s] = n_out;
+			f.m[s] = seg_out.m;
+			f.i[s] = seg_out.i;
+		}
+		if (tid == 0)
+			fn[blockIdx.x] = f;
+	} else {
+		const StreamCarry c = carry[blockIdx.x];
+		tile_trigger(tsh, cls, v, t0, tid, c.s, c.m, c.i, s_thr, seg_thr, before, s_out, seg_out, n_out);
+		int s = s_thr;
+		float m = seg_thr.m;
+		long long im = seg_thr.i, pos = c.count + before;
+		for (int j = 0; j < SPT; ++j) {
+			const long long t = t0 + j;
+			if (cls[j] < 0 && s == 1) {                               // decode.cc:103-116
+				comb(m, im, v[j], t);
+				if (pos < cap) {
+					StreamEdge e;
+					e.g = t;
+					e.t_max = im;
+					const long long age = MD + (t - im);
+					e.index_max = (int)(age < HS + GL + MD ? age : HS + GL + MD);
+					e.accept = 0;
+					e.symbol_pos = 0;
+					e.cfo_rad = 0.f;
+					edges[pos] = e;
+				}
+				++pos;
+				m = -INFINITY;
+				im = -1;
+			} else {
+				comb(m, im, v[j], t);
+			}
+			if (cls[j])
+				s = cls[j] > 0;
+		}
+	}
+}
+
+// the per-tile functions composed (l first, then r)
+__device__ __forceinline__ StreamFn fn_then(const StreamFn &l, const StreamFn &r)
+{
+	StreamFn o;
+	for (int s = 0; s < 2; ++s) {
+		const int q = l.s_out[s];
+		o.s_out[s] = r.s_out[q];
+		o.has[s] = l.has[s] | r.has[q];
+		o.n[s] = l.n[s] + r.n[q];
+		if (r.has[q]) {
+			o.m[s] = r.m[q];
+			o.i[s] = r.i[q];
+		} else {
+			o.m[s] = l.m[s];
+			o.i[s] = l.i[s];
+			comb(o.m[s], o.i[s], r.m[q], r.i[q]);
+		}
+	}
+	return o;
+}
+__device__ __forceinline__ StreamCarry fn_apply(const StreamFn &f, StreamCarry c)
+{
+	const int s = c.s;
+	StreamCarry o;
+	o.s = f.s_out[s];
+	o.count = c.count + f.n[s];
+	if (f.has[s]) {
+		o.m = f.m[s];
+		o.i = f.i[s];
+	} else {
+		o.m = c.m;
+		o.i = c.i;
+		comb(o.m, o.i, f.m[s], f.i[s]);
+	}
+	return o;
+}
+
+__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts)
+{
+	const int tid = threadIdx.x;
+	__shared__ StreamFn sh[1024];
+	const long per = (ntiles + 1023) / 1024, k0 = (long)tid * per, k1 = k0 + per < ntiles ? k0 + per : ntiles;
+	StreamFn f;
+	for (int s = 0; s < 2; ++s) {
+		f.s_out[s] = s;
+		f.has[s] = 0;
+		f.n[s] = 0;
+		f.m[s] = -INFINITY;
+		f.i[s] = -1;
+	}
+	for (long k = k0; k < k1; ++k)
+		f = fn_then(f, fn[k]);
+	block_scan_incl<1024>(f, sh, tid, fn_then);
+	StreamCarry c{ 0, -INFINITY, -1, 0 };                     // the stream starts with the trigger off (decode.cc:68-74)
+	if (tid)
+		c = fn_apply(sh[tid - 1], c);
+	for (long k = k0; k < k1; ++k) {
+		carry[k] = c;
+		c = fn_apply(fn[k], c);
+	}
+	if (k0 < ntiles && k1 == ntiles)
+		counts[0] = c.count;
+}
+
+void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
+	StreamEdge *edges, long cap, long long *counts)
+{
+	const long ntiles = (n + STREAM_TILE - 1) / STREAM_TILE;
+	if (given) {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+	} else {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+	}
+	hipLaunchKernelGGL(k_stream_fn_scan, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts);
+	if (given) {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+	} else {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+	}
+}
+
+// ---------------------------------------------------------------- accept, records
+constexpr int ACCEPT_GRID = 2048;
+template <int RATE>
+__global__ __launch_bounds__(256) void k_stream_accept(FrameBatch fb, const cf *__restrict__ tw, const cf *__restrict__ kern,
+	StreamEdge *__restrict__ edges, long cap, const long long *__restrict__ counts)
+{
+	typedef RateCfg<RATE> RC;
+	constexpr int BUFFER_LEN = RC::BUFFER_LEN, SEARCH_POS = RC::SEARCH_POS, HALF_LEN = RC::HS, MATCH_DEL = RC::MATCH_DEL, NT = 256;
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const long long ne = counts[0] < cap ? counts[0] : cap;
+	const SampleSrc src{ fb.samples, fb.fmt, fb.channels, fb.samples_per_frame, nullptr };
+	__shared__ cf buf[HALF_LEN], xr[HALF_LEN];
+	__shared__ cf rot[(HALF_LEN + NT - 1) / NT];
+	__shared__ float red_p[4];
+	__shared__ int red_i[4];
+	__shared__ float phase_sh;
+	for (long long e = blockIdx.x; e < ne; e += gridDim.x) {
+		__syncthreads();
+		StreamEdge ed = edges[e];
+		if (wave == 0) {                                          // decode.cc:91: arg(P) delayed by match_del (k_sync: direct_P)
+			float phase = 0.f;
+			const long long tp = ed.t_max - MATCH_DEL;
+			if (tp >= 0) {
+				double pr, pi;
+				direct_P<RATE>(src, (long)tp, lane, pr, pi);
+				phase = atan2f((float)pi, (float)pr);
+			}
+			if (lane == 0)
+				phase_sh = phase;
+		}
+		__syncthreads();
+		const float phase_max = phase_sh;
+		const float frac_cfo = phase_max / (float)HALF_LEN;       // decode.cc:110
+		int symbol_pos = SEARCH_POS - ed.index_max;               // decode.cc:114
+		const long base = (long)ed.g - (BUFFER_LEN - 1);
+		int shift, pos_err;
+		const bool accept = sc_accept_wg<RATE>(buf, xr, rot, red_p, red_i, src, tw, kern, base, symbol_pos, frac_cfo, tid, lane, wave, shift, pos_err);
+		if (tid == 0) {
+			ed.accept = accept ? 1 : 0;
+			if (accept) {
+				symbol_pos -= pos_err;
+				float cfo_rad = (float)shift * (TWO_PI_F / (float)HALF_LEN) - frac_cfo;   // decode.cc:148
+				if (cfo_rad >= PI_F)
+					cfo_rad -= TWO_PI_F;
+				ed.symbol_pos = symbol_pos;
+				ed.cfo_rad = cfo_rad;
+			}
+			edges[e] = ed;
+		}
+	}
+}
+
+void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, const long long *counts)
+{
+	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL(k_stream_accept<RATE>, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts));
+}
+
+__global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
+	SyncState *__restrict__ rec, long max_rec)
+{
+	const int tid = threadIdx.x;
+	__shared__ long long sh[1024];
+	const long long ne = counts[0] < cap ? counts[0] : cap;
+	long long base = 0;
+	for (long long e0 = 0; e0 < ne; e0 += 1024) {
+		const long long e = e0 + tid;
+		const int acc = e < ne ? edges[e].accept : 0;
+		block_scan_incl<1024>((long long)acc, sh, tid, add_ll);
+		const long long k = base + (tid ? sh[tid - 1] : 0);
+		const long long total = sh[1023];
+		__syncthreads();
+		if (acc && k < max_rec) {
+			const StreamEdge ed = edges[e];
+			SyncState st;                                         // what k_header finds after an accepted round with skip_left = 0
+			st.t_next = (long)ed.g + 1;
+			st.sc_start = (long)ed.g - (buffer_len - 1) + ed.symbol_pos;
+			st.active = 1;
+			st.found = 1;
+			st.symbol_pos = ed.symbol_pos;
+			st.cfo_rad = ed.cfo_rad;
+			st.rejects = (int)(e - k);                            // the edges before it that decode.cc:140-145 rejected
+			st.skip_left = 0;
+			st.status = 1;
+			st.oper_mode = 0;
+			st.call_sign = 0;
+			st.hdr_rounds = (int)k;
+			st.okay = 0;
+			st.pend_g = 0;
+			st.pend_index_max = 0;
+			st.pend_phase = 0.f;
+			st.pending = 0;
+			rec[k] = st;
+		}
+		base += total;
+	}
+	if (tid == 0)
+		counts[1] = base;
+}
+
+void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec)
+{
+	int buffer_len = 0;
+	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
+	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec);
+}
+
+}  // namespace rx

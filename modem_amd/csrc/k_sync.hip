@@ -15,6 +15,7 @@
 #include "dev_common.h"
 #include "kernels.h"
 #include "mono_front.h"
+#include "sync_accept.h"
 
 // Decision-critical fp32 expressions (cfo_rad = shift*2pi/640 - frac_cfo sits at magnitude ~6 before the
 // wrap, so ONE ulp there is 5e-7 rad/sample = 7e-4 rad per symbol): no FMA contraction in this file, like
@@ -162,24 +163,6 @@ __device__ __forceinline__ int first_index(const float *timing, int T0, int lane
 	return wave_min_i(best);
 }
 
-// P at time t by direct summation (decode.cc:86), double accumulate
-template <int RATE>
-__device__ __forceinline__ void direct_P(const SampleSrc &src, long t, int lane, double &re, double &im)
-{
-	constexpr int BUFFER_LEN = RateCfg<RATE>::BUFFER_LEN, SEARCH_POS = RateCfg<RATE>::SEARCH_POS, HALF_LEN = RateCfg<RATE>::HS;
-	double sr = 0.0, si = 0.0;
-	long a0 = t - (BUFFER_LEN - 1 - (SEARCH_POS + HALF_LEN));   // newest u
-	for (int q = 0; q < (HALF_LEN + 63) / 64; ++q) {
-		if (q * 64 + lane >= HALF_LEN)
-			break;
-		long u = a0 - (q * 64 + lane);
-		cf x = src.at(u), y = src.at(u + HALF_LEN);
-		sr += (double)x.re * y.re + (double)x.im * y.im;
-		si += (double)x.im * y.re - (double)x.re * y.im;
-	}
-	re = wave_sum_d(sr);
-	im = wave_sum_d(si);
-}
 template <int RATE>
 __device__ __forceinline__ double direct_R(const SampleSrc &src, long t, int lane)
 {
@@ -498,12 +481,13 @@ __global__ __launch_bounds__(64, SPLIT ? (MONO ? SYNC_WAVES_SPLIT_MONO : SYNC_WA
 
 // decode.cc:110-151 for a pending trigger, one workgroup per frame: the same arithmetic as sc_process (the transforms
 // are the same Stockham stages, butterfly by butterfly - only shared among 256 threads, in LDS), bit-identical results.
+// The arithmetic is sc_accept_wg (sync_accept.h), which the stream scan's accept kernel (k_stream.hip) shares.
 template <int RATE, bool MONO>
 __global__ __launch_bounds__(256) void k_sync_accept(FrameBatch fb, cf *__restrict__ z_all, const cf *__restrict__ tw,
 	const cf *__restrict__ kern, SyncState *__restrict__ st_all, MonoArgs ma)
 {
 	typedef RateCfg<RATE> RC;
-	constexpr int BUFFER_LEN = RC::BUFFER_LEN, SEARCH_POS = RC::SEARCH_POS, HALF_LEN = RC::HS, GUARD_LEN = RC::GL, NT = 256;
+	constexpr int BUFFER_LEN = RC::BUFFER_LEN, SEARCH_POS = RC::SEARCH_POS, HALF_LEN = RC::HS, NT = 256;
 	const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	SyncState st = st_all[f];
 	if (!st.active || st.found || !st.pending)
@@ -526,65 +510,8 @@ __global__ __launch_bounds__(256) void k_sync_accept(FrameBatch fb, cf *__restri
 		mc.init(mono_frame(fb, ma.ck, ma.ck_per_frame, f), ma, &msh, z_all + (size_t)f * fb.samples_per_frame, tid);
 		mc.cover(ma, base + symbol_pos + HALF_LEN, base + symbol_pos + 2 * HALF_LEN, tid);
 	}
-	if (tid < (HALF_LEN + NT - 1) / NT)
-		rot[tid] = phasor(frac_cfo, (long)NT * tid);
-	const cf p_thread = phasor(frac_cfo, tid);
-	__syncthreads();
-	for (int i = tid; i < HALF_LEN; i += NT)                   // decode.cc:117-118
-		buf[i] = cmul(src.at(base + i + symbol_pos + HALF_LEN), cmul(p_thread, rot[i / NT]));
-	__syncthreads();
-	fft_fwd<HALF_LEN, NT, RC::SL>(buf, tw, tid);
-	for (int i = tid; i < HALF_LEN; i += NT)                   // decode.cc:120-121
-		xr[i] = demod_or_erase(buf[i], buf[(i + HALF_LEN - 1) % HALF_LEN]);
-	__syncthreads();
-	fft_fwd<HALF_LEN, NT, RC::SL>(xr, tw, tid);
-	// x kern, then backward transform as conj(FFT(conj(.)))
-	for (int i = tid; i < HALF_LEN; i += NT)
-		xr[i] = cconj(cmul(xr[i], kern[i]));
-	__syncthreads();
-	fft_fwd<HALF_LEN, NT, RC::SL>(xr, tw, tid);
-	// decode.cc:127-139: peak = max, shift = first index of it, next = runner-up
-	float pk = -1.f;
-	int sh_i = 0x7fffffff;
-	for (int i = tid; i < HALF_LEN; i += NT) {
-		float p = cnorm(xr[i]);
-		if (p > pk) { pk = p; sh_i = i; }
-	}
-	#pragma unroll
-	for (int m = 32; m; m >>= 1) {
-		float op = __shfl_xor(pk, m);
-		int oi = __shfl_xor(sh_i, m);
-		if (op > pk || (op == pk && oi < sh_i)) { pk = op; sh_i = oi; }
-	}
-	if (lane == 0) { red_p[wave] = pk; red_i[wave] = sh_i; }
-	__syncthreads();
-	pk = red_p[0]; sh_i = red_i[0];
-	#pragma unroll
-	for (int w = 1; w < 4; ++w)
-		if (red_p[w] > pk || (red_p[w] == pk && red_i[w] < sh_i)) { pk = red_p[w]; sh_i = red_i[w]; }
-	__syncthreads();
-	float nx = 0.f;
-	for (int i = tid; i < HALF_LEN; i += NT) {
-		float p = cnorm(xr[i]);
-		if (i != sh_i && p > nx) nx = p;
-	}
-	#pragma unroll
-	for (int m = 32; m; m >>= 1)
-		nx = fmaxf(nx, __shfl_xor(nx, m));
-	if (lane == 0)
-		red_p[wave] = nx;
-	__syncthreads();
-	nx = fmaxf(fmaxf(red_p[0], red_p[1]), fmaxf(red_p[2], red_p[3]));
-	const float peak = fmaxf(pk, 0.f);
-	const int shift = peak > 0.f ? sh_i : 0;
-	bool accept = peak > nx * 4.f;                             // decode.cc:140-141
-	int pos_err = 0;
-	if (accept) {
-		cf v = cconj(xr[shift]);
-		pos_err = (int)nearbyintf(atan2f(v.im, v.re) * (float)HALF_LEN / TWO_PI_F);
-		if (abs(pos_err) > GUARD_LEN / 2)                      // decode.cc:144-145
-			accept = false;
-	}
+	int shift, pos_err;
+	const bool accept = sc_accept_wg<RATE>(buf, xr, rot, red_p, red_i, src, tw, kern, base, symbol_pos, frac_cfo, tid, lane, wave, shift, pos_err);
 	if (tid == 0) {
 		st.pending = 0;
 		if (accept) {

@@ -219,4 +219,36 @@ void launch_tx(hipStream_t s, int rate, int n, const uint8_t *payload, Tables tb
 // chunk_flags (nullable): per-chunk device flags cleared here ([0]: the largest row count k_theil_sen met, when above 50)
 void launch_init_sync(hipStream_t s, int n, SyncState *st, const int32_t *skip_counts, int *chunk_flags = nullptr, int32_t *attempt_counts = nullptr);
 
+// ---- stream decode (k_stream.hip, api_stream.cpp): one recording, every preamble in it.  The timing metric is formed tile by tile
+// (STREAM_TILE sample times per workgroup), the trigger (decode.cc:93-116) resolved by a scan over the tiles: each tile publishes
+// what it does to an incoming (Schmitt state, running maximum since the last falling edge, edge count) for either incoming state,
+// one workgroup scans those functions, and the tiles then emit their falling edges in stream order.
+constexpr int STREAM_TILE = 4096;
+struct StreamFn {                  // a tile (or a run of tiles) as a function of the incoming Schmitt state s = 0 / 1
+	int s_out[2];                  // the state after it
+	int has[2];                    // it holds a falling edge
+	long long n[2];                // falling edges in it
+	float m[2];                    // maximum of the timing metric since its last falling edge (all of it if none), first index of it
+	long long i[2];
+};
+struct StreamCarry { int s; float m; long long i; long long count; };   // what enters a tile
+struct StreamEdge {                // one falling edge, in stream order
+	long long g, t_max;            // the edge sample, the first index of the maximum of its run
+	int index_max;                 // decode.cc:99-105
+	int accept;                    // decode.cc:110-151 (k_stream_accept)
+	int symbol_pos;                // window coordinate after pos_err, when accepted
+	float cfo_rad;
+};
+// mono input: the DC blocker's kept states of the whole stream (the layout of k_mono_carries, one frame) by a scan over tiles of
+// 4096 samples; tile_end / tile_in: one double per tile
+void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
+// the trigger scan over n sample times of the 2-channel stream fb (given != nullptr: over that timing sequence instead); counts[0]:
+// falling edges; edges: the first `cap` of them.  fn / carry: one per tile
+void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
+	StreamEdge *edges, long cap, long long *counts);
+// decode.cc:110-151 for every edge (of the min(counts[0], cap) written), then the records: counts[1] = accepted edges, rec[k] = the
+// SyncState that k_header finds for the (k+1)-th accepted edge after a round with skip_left = 0 (k < max_rec)
+void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, const long long *counts);
+void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec);
+
 }  // namespace rx

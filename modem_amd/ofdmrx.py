@@ -24,7 +24,7 @@ EXPORTS = [
     "ofdmrx_debug_dump", "ofdmrx_debug_polar", "ofdmrx_debug_sc_path", "ofdmrx_debug_decode_cons", "ofdmrx_debug_theil_sen", "ofdmrx_debug_osd", "ofdmrx_debug_fft",
     "ofdmrx_util_awgn_tile", "ofdmrx_util_channel", "ofdmrx_frame_samples", "ofdmrx_tx_frame_samples",
     "ofdmrx_tx_encode_device", "ofdmrx_stream_samples", "ofdmrx_tx_encode_stream_device", "ofdmrx_tx_encode_stream",
-    "ofdmrx_callsign_value",
+    "ofdmrx_callsign_value", "ofdmrx_decode_stream", "ofdmrx_decode_stream_device", "ofdmrx_debug_stream_edges",
 ]
 
 
@@ -108,6 +108,11 @@ def load_library():
     batch = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ofdmrx_decode_batch.argtypes = batch
     L.ofdmrx_decode_batch_device.argtypes = batch
+    stream = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.ofdmrx_decode_stream.argtypes = stream
+    L.ofdmrx_decode_stream_device.argtypes = stream
+    L.ofdmrx_debug_stream_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_size_t)]
     L.ofdmrx_synchronize.argtypes = [C.c_void_p]
     L.ofdmrx_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.ofdmrx_chunk_frames.argtypes = [C.c_void_p]
@@ -230,6 +235,50 @@ class Receiver:
                 self._lib.ofdmrx_set_attempt_log(self._h, None, None)
         ret = (out, res) + ((rows,) if esn0_rows else ()) + (((alog, acnt),) if attempts else ())
         return ret
+
+    def decode_stream(self, pcm, max_frames=None, esn0_rows=False):
+        """one recording [samples, channels] (or [samples] mono) -> (payloads [k, 5380], results [k], n_preambles[, esn0 rows]),
+        k = min(n_preambles, max_frames); max_frames None: every preamble (the call is made twice when the first guess is short)"""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.ndim == 1:
+            pcm = pcm[:, None]
+        n, ch = pcm.shape
+        cap = max_frames if max_frames is not None else max(16, n // 20000)
+        while True:
+            out = np.zeros((max(cap, 1), PAYLOAD_BYTES), np.uint8)
+            res = np.zeros(max(cap, 1), RESULT_DTYPE)
+            rows = np.zeros((max(cap, 1), 126), np.float32) if esn0_rows else None
+            npre = C.c_size_t(0)
+            if esn0_rows:
+                self._check(self._lib.ofdmrx_set_esn0_rows(self._h, _ptr(rows)))
+            try:
+                self._check(self._lib.ofdmrx_decode_stream(self._h, _ptr(pcm), self._fmt(pcm.dtype), ch, n, cap, _ptr(out), _ptr(res),
+                                                           C.byref(npre)))
+            finally:
+                if esn0_rows:
+                    self._lib.ofdmrx_set_esn0_rows(self._h, None)
+            if max_frames is not None or npre.value <= cap:
+                break
+            cap = npre.value
+        k = min(npre.value, cap)
+        return (out[:k], res[:k], npre.value) + ((rows[:k],) if esn0_rows else ())
+
+    def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
+        """device pointers (ints), or pinned host outputs; -> n_preambles (the call synchronises once, after the scan)"""
+        npre = C.c_size_t(0)
+        self._check(self._lib.ofdmrx_decode_stream_device(self._h, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results,
+                                                          C.byref(npre)))
+        return npre.value
+
+    def debug_stream_edges(self, timing, max_edges=None):
+        """the stream scan's trigger on a timing sequence -> (t_edge, t_max, index_max) of every falling edge"""
+        timing = np.ascontiguousarray(timing, dtype=np.float32)
+        cap = max_edges if max_edges is not None else max(1, len(timing) // 2 + 1)
+        te, tm, im = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        ne = C.c_size_t(0)
+        self._check(self._lib.ofdmrx_debug_stream_edges(self._h, _ptr(timing), len(timing), cap, _ptr(te), _ptr(tm), _ptr(im), C.byref(ne)))
+        k = min(ne.value, cap)
+        return te[:k], tm[:k], im[:k], ne.value
 
     def set_esn0_rows(self, d_rows):
         """device pointer (int) to n x 126 floats for the decode_device calls that follow, or None"""

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""stream_bench.py -- ofdmrx_decode_stream_device on long recordings, against the batch entry on the same payloads.
+
+Input (made on the device): --streams streams of --count mode-6 payloads each, 8 kHz, 2-channel int16, by the device transmitter
+(ofdmrx_tx_encode_stream_device) + ofdmrx_util_awgn_tile at --noise-db.  Timed: one decode_stream_device call per stream per step
+(host clock around a synchronise), warm-up first.  Compared in the same process: the batch entry on the same payloads as single-payload
+frames (ofdmrx_tx_encode_device, what bench.py runs), and today's route to the payloads of one --skip-count-payload stream (that many
+copies of it with skip counts 0 .. n-1).  Every payload is checked.  Prints one JSON line (and writes it to --out).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=2)
+    ap.add_argument("--count", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--noise-db", type=float, default=-30.0)
+    ap.add_argument("--skip-count", type=int, default=64)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import torch
+    import modem_amd
+    import modem_amd.ofdmrx as M
+    dev = torch.device("cuda:0")
+    rx = modem_amd.Receiver(device=0)
+    L = rx._lib
+    L.ofdmrx_tx_encode_stream_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
+    L.ofdmrx_stream_samples.restype = C.c_long
+    S, K = a.streams, a.count
+    n = int(L.ofdmrx_stream_samples(8000, 6, K))
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    pay = torch.randint(0, 256, (S, K, 5380), dtype=torch.uint8, device=dev, generator=g)
+    clean = torch.empty((n, 2), dtype=torch.int16, device=dev)
+    pcm = [torch.empty((n, 2), dtype=torch.int16, device=dev) for _ in range(S)]
+    for s in range(S):
+        rc = L.ofdmrx_tx_encode_stream_device(rx._h, pay[s].data_ptr(), 1, K, 6, 2000, b"ANONYMOUS", 2, 16, clean.data_ptr())
+        assert rc == 0, rc
+        rx.awgn_tile(clean.data_ptr(), 1, pcm[s].data_ptr(), 1, n, a.noise_db, 11 + s, 0)
+    rx.synchronize()
+    del clean
+    out = torch.zeros((S, K, 5380), dtype=torch.uint8, device=dev)
+    res = torch.zeros((S, K, M.RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+
+    def stream_step():
+        for s in range(S):
+            npre = rx.decode_stream_device(pcm[s].data_ptr(), 0, 2, n, K, out[s].data_ptr(), res[s].data_ptr())
+            assert npre == K, npre
+        rx.synchronize()
+
+    for _ in range(a.warmup):
+        stream_step()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        stream_step()
+    dt = (time.perf_counter() - t0) / a.steps
+    tm = rx.timing()
+    ok = int((out == pay).all(dim=2).sum().item())
+    status = res.cpu().numpy().reshape(S * K, -1).view(M.RESULT_DTYPE).ravel()["status"]
+    stream_fps = S * K / dt
+    # the batch entry on the same payloads as single-payload frames
+    spf = int(L.ofdmrx_tx_frame_samples(6))
+    clean = torch.empty((S * K, spf, 2), dtype=torch.int16, device=dev)
+    rx.tx_encode(pay.reshape(S * K, 5380).data_ptr(), S * K, clean.data_ptr(), mode=6, channels=2)
+    frames = torch.empty_like(clean)
+    rx.awgn_tile(clean.data_ptr(), S * K, frames.data_ptr(), S * K, spf, a.noise_db, 11, 0)
+    del clean
+    bout = torch.zeros((S * K, 5380), dtype=torch.uint8, device=dev)
+    bres = torch.zeros((S * K, M.RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    for _ in range(a.warmup):
+        rx.decode_device(frames.data_ptr(), 0, 2, spf, spf * 4, S * K, bout.data_ptr(), bres.data_ptr())
+        rx.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        rx.decode_device(frames.data_ptr(), 0, 2, spf, spf * 4, S * K, bout.data_ptr(), bres.data_ptr())
+        rx.synchronize()
+    bdt = (time.perf_counter() - t0) / a.steps
+    bok = int((bout == pay.reshape(S * K, 5380)).all(dim=1).sum().item())
+    del frames, bout, bres
+    # today's route to the payloads of one stream: copies of it with skip counts 0 .. n-1
+    J = a.skip_count
+    nj = int(L.ofdmrx_stream_samples(8000, 6, J))
+    clean = torch.empty((nj, 2), dtype=torch.int16, device=dev)
+    L.ofdmrx_tx_encode_stream_device(rx._h, pay[0, :J].contiguous().data_ptr(), 1, J, 6, 2000, b"ANONYMOUS", 2, 16, clean.data_ptr())
+    one = torch.empty_like(clean)
+    rx.awgn_tile(clean.data_ptr(), 1, one.data_ptr(), 1, nj, a.noise_db, 11, 0)
+    copies = one[None].repeat(J, 1, 1).contiguous()
+    skips = torch.arange(J, dtype=torch.int32, device=dev)
+    sout = torch.zeros((J, 5380), dtype=torch.uint8, device=dev)
+    sres = torch.zeros((J, M.RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    rx.decode_device(copies.data_ptr(), 0, 2, nj, nj * 4, J, sout.data_ptr(), sres.data_ptr(), d_skip=skips.data_ptr())
+    rx.synchronize()
+    t0 = time.perf_counter()
+    rx.decode_device(copies.data_ptr(), 0, 2, nj, nj * 4, J, sout.data_ptr(), sres.data_ptr(), d_skip=skips.data_ptr())
+    rx.synchronize()
+    sdt = time.perf_counter() - t0
+    sok = int((sout == pay[0, :J]).all(dim=1).sum().item())
+    sstat = np.bincount(sres.cpu().numpy().view(M.RESULT_DTYPE).ravel()["status"], minlength=7).tolist()
+    t1 = time.perf_counter()
+    npre = rx.decode_stream_device(one.data_ptr(), 0, 2, nj, J, sout.data_ptr(), sres.data_ptr())
+    rx.synchronize()
+    s1dt = time.perf_counter() - t1
+    s1ok = int((sout == pay[0, :J]).all(dim=1).sum().item())
+    rec = {
+        "metric": "stream decode, mode-6 8 kHz 2-channel int16, AWGN %g dB" % a.noise_db,
+        "streams": S, "payloads_per_stream": K, "samples_per_stream": n, "steps": a.steps,
+        "stream_ms_per_step": dt * 1e3, "stream_frames_per_s": stream_fps, "stream_payloads_ok": ok, "stream_status_ok": int((status == 0).sum()),
+        "stream_stage_ms_last_call": {k: round(v[0], 3) for k, v in tm.items()},
+        "batch_ms_per_step": bdt * 1e3, "batch_frames_per_s": S * K / bdt, "batch_payloads_ok": bok,
+        "stream_vs_batch": stream_fps / (S * K / bdt),
+        "skip_route_payloads": J, "skip_route_ms": sdt * 1e3, "skip_route_frames_per_s": J / sdt, "skip_route_payloads_ok": sok, "skip_route_status_counts": sstat,
+        "stream_route_same_payloads_ms": s1dt * 1e3, "stream_route_preambles": npre, "stream_route_payloads_ok": s1ok,
+        "input_bytes_per_step": S * n * 4,
+    }
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    rx.close()
+
+
+if __name__ == "__main__":
+    main()
