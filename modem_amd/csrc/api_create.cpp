@@ -156,12 +156,6 @@ extern "C" void ofdmrx_destroy(ofdmrx_handle *h)
 			(void)hipStreamSynchronize(sx);
 			(void)hipStreamDestroy(sx);
 		}
-	for (DevBuf *b : { &h->st, &h->hdr_soft, &h->cons, &h->slope, &h->yint, &h->precision, &h->slot_of, &h->res, &h->payload, &h->payload2, &h->res2,
-			&h->chunk_flags, &h->soft, &h->s_ctl, &h->s_slots, &h->s_llr, &h->s_cw, &h->s_xw, &h->s_stat, &h->sc_soft, &h->q_ctl, &h->q_slots, &h->q_llr, &h->q_hard, &h->q_metric, &h->q_lane_mesg, &h->rot_tap, &h->tx_code, &h->tx_rowsym,
-			&h->tx_tdom, &h->tx_big, &h->esn0_dev, &h->esn0_dev2, &h->att_dev, &h->att_dev2, &h->attc_dev, &h->attc_dev2, &h->dc, &h->z, &h->in_stage, &h->in_stage2, &h->skip_stage, &h->carr, &h->sc_scratch,
-			&h->sx_in, &h->sx_z, &h->sx_ck, &h->sx_dc_end, &h->sx_dc_in, &h->sx_fn, &h->sx_carry, &h->sx_edges, &h->sx_counts, &h->sx_rec, &h->sx_pay,
-			&h->sx_res, &h->sx_esn0, &h->sx_timing })
-		b->release();
 	for (void *p : h->table_allocs)
 		(void)hipFree(p);
 	for (void *p : h->out_stage)
@@ -171,7 +165,7 @@ extern "C" void ofdmrx_destroy(ofdmrx_handle *h)
 		(void)hipEventDestroy(e);
 	if (h->own_stream && h->stream)
 		(void)hipStreamDestroy(h->stream);
-	delete h;
+	delete h;                                                     // and with it every DevBuf: nothing runs on the device any more
 }
 
 extern "C" int ofdmrx_chunk_frames(ofdmrx_handle *h) { return h ? h->chunk : OFDMRX_E_ARG; }
@@ -260,8 +254,8 @@ int ensure_capacity(ofdmrx_handle *h, int n, bool mono, long samples)
 		r = r ? r : h->precision.ensure(N * ROWS_MAX * sizeof(float));
 		r = r ? r : h->slot_of.ensure(N * sizeof(int));
 		r = r ? r : h->chunk_flags.ensure(256);
-		r = r ? r : h->res.ensure(N * sizeof(Result));
-		r = r ? r : h->payload.ensure(N * PAYLOAD_BYTES);
+		r = r ? r : h->res[0].ensure(N * sizeof(Result));
+		r = r ? r : h->payload[0].ensure(N * PAYLOAD_BYTES);
 		r = r ? r : h->rot_tap.ensure(CONS_MAX * sizeof(cf));
 		// one 2 MiB level store per RESIDENT decoder, not per frame
 		r = r ? r : h->soft.ensure((size_t)(std::min<long>((long)N, (long)h->polar_grid) + 8) * 8 * CODE_LEN * sizeof(float));

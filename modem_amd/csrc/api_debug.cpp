@@ -92,9 +92,9 @@ extern "C" int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr, size_t n, 
 	if ((r = host_wait(h)))
 		return r;
 	HIP_OK(hipMemcpy(h->q_llr.p, llr, n * CODE_LEN * sizeof(float), hipMemcpyHostToDevice));
-	HIP_OK(hipMemsetAsync(h->res.p, 0, n * sizeof(Result), h->stream));
+	HIP_OK(hipMemsetAsync(h->res[0].p, 0, n * sizeof(Result), h->stream));
 	launch_queue_reset(h->stream, h->queue(), h->q_cap);
-	launch_queue_fill(h->stream, h->queue(), h->q_slots.as<ListSlot>(), (int)n, h->payload.as<uint8_t>(), h->res.as<Result>(), 6);
+	launch_queue_fill(h->stream, h->queue(), h->q_slots.as<ListSlot>(), (int)n, h->payload[0].as<uint8_t>(), h->res[0].as<Result>(), 6);
 	queue_run_all(h, h->list);
 	launch_finish(h->stream, h->list, (int)n, h->queue(), 0, h->q_slots.as<ListSlot>(), h->q_llr.as<float>(), h->q_hard.as<uint8_t>(), h->dev, 0,
 		lm.as<uint8_t>());
@@ -104,7 +104,6 @@ extern "C" int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr, size_t n, 
 		e = hipMemcpy(lane_mesg, lm.p, n * LIST * MESG_BYTES, hipMemcpyDeviceToHost);
 	if (e == hipSuccess && metric)
 		e = hipMemcpy(metric, h->q_metric.p, n * LIST * sizeof(float), hipMemcpyDeviceToHost);
-	lm.release();
 	if (e != hipSuccess) {
 		g_last_error = hipGetErrorString(e);
 		return OFDMRX_E_HIP;
@@ -141,7 +140,7 @@ extern "C" int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr, size_t n
 	if (!r && (r = host_wait(h)) == 0) {
 		hipError_t e = hipMemcpy(dl.p, llr, n * CODE_LEN * sizeof(float), hipMemcpyHostToDevice);
 		launch_queue_reset(h->stream, ctl.as<ListQueue>(), (unsigned)n);
-		launch_queue_fill(h->stream, ctl.as<ListQueue>(), slots.as<ListSlot>(), (int)n, h->payload.as<uint8_t>(), h->res.as<Result>(), 6);
+		launch_queue_fill(h->stream, ctl.as<ListQueue>(), slots.as<ListSlot>(), (int)n, h->payload[0].as<uint8_t>(), h->res[0].as<Result>(), 6);
 		if (oper_modes && e == hipSuccess) {                      // (the slots' modes decide the frozen table and who sits beside whom)
 			e = hipStreamSynchronize(h->stream);
 			std::vector<ListSlot> ls(n);
@@ -172,8 +171,6 @@ extern "C" int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr, size_t n
 				if (rule_ok) rule_ok[i] = st[i].ok;
 			}
 	}
-	for (DevBuf *b : { &ctl, &slots, &dl, &cw, &xw, &stat, &soft })
-		b->release();
 	h->last_n = 0;
 	return r;
 }
@@ -201,14 +198,14 @@ extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, siz
 		return r;
 	HIP_OK(hipMemcpy(h->st.p, st.data(), n * sizeof(SyncState), hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy2D(h->cons.p, CONS_MAX * sizeof(cf), cons, 21600 * sizeof(cf), 21600 * sizeof(cf), n, hipMemcpyHostToDevice));
-	HIP_OK(hipMemsetAsync(h->res.p, 0, n * sizeof(Result), h->stream));
+	HIP_OK(hipMemsetAsync(h->res[0].p, 0, n * sizeof(Result), h->stream));
 	HIP_OK(hipMemsetAsync(h->slope.p, 0, n * ROWS_MAX * sizeof(float), h->stream));
 	HIP_OK(hipMemsetAsync(h->yint.p, 0, n * ROWS_MAX * sizeof(float), h->stream));
 	launch_queue_reset(h->stream, h->queue(), h->q_cap);
 	if (with_sc)
 		launch_queue_reset(h->stream, h->sc_queue(), h->s_cap);
 	launch_back(h->stream, h->rate, (int)n, (use_cert == 1 || use_cert == 2) ? 1 : 0, h->st.as<SyncState>(), h->cons.as<cf>(), h->slope.as<float>(), h->yint.as<float>(),
-		h->precision.as<float>(), h->res.as<Result>(), nullptr, h->dev, h->cfg.descramble, h->payload.as<uint8_t>(), h->queue(),
+		h->precision.as<float>(), h->res[0].as<Result>(), nullptr, h->dev, h->cfg.descramble, h->payload[0].as<uint8_t>(), h->queue(),
 		h->q_slots.as<ListSlot>(), h->q_llr.as<float>(), h->slot_of.as<int>(), nullptr, nullptr, with_sc ? h->sc_ring() : ScRing{ nullptr, nullptr, nullptr });
 	if (with_sc)
 		run_sc_pass(h, h->stream, (int)n);
@@ -218,8 +215,8 @@ extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, siz
 		h->cfg.descramble, nullptr);
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipStreamSynchronize(h->stream));
-	HIP_OK(hipMemcpy(payload, h->payload.p, n * PAYLOAD_BYTES, hipMemcpyDeviceToHost));
-	HIP_OK(hipMemcpy(results, h->res.p, n * sizeof(Result), hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(payload, h->payload[0].p, n * PAYLOAD_BYTES, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(results, h->res[0].p, n * sizeof(Result), hipMemcpyDeviceToHost));
 	if (cert_out) {
 		std::vector<int> slot(n);
 		HIP_OK(hipMemcpy(slot.data(), h->slot_of.p, n * sizeof(int), hipMemcpyDeviceToHost));
@@ -250,7 +247,6 @@ extern "C" int ofdmrx_debug_theil_sen(ofdmrx_handle *h, const float *y, size_t r
 			r = OFDMRX_E_HIP;
 		}
 	}
-	dy.release(); ds.release(); di.release();
 	return r;
 }
 
@@ -274,7 +270,6 @@ extern "C" int ofdmrx_debug_osd(ofdmrx_handle *h, const int8_t *soft, size_t n, 
 			r = OFDMRX_E_HIP;
 		}
 	}
-	dsf.release(); dh.release(); du.release();
 	return r;
 }
 
@@ -297,6 +292,5 @@ extern "C" int ofdmrx_debug_fft(ofdmrx_handle *h, const float *in, size_t n, int
 			r = OFDMRX_E_HIP;
 		}
 	}
-	di.release(); dout.release();
 	return r;
 }

@@ -26,17 +26,18 @@ static_assert(sizeof(Attempt) == sizeof(ofdmrx_attempt) && ATTEMPTS_MAX == OFDMR
 
 extern thread_local std::string g_last_error;   // (api_create.cpp)
 
-struct DevBuf {
+struct DevBuf {                    // owns its device memory: a buffer of the handle goes with the handle, a local one with its scope
 	void *p = nullptr;
 	size_t bytes = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	~DevBuf() { release(); }
 	int ensure(size_t need)
 	{
 		if (need <= bytes)
 			return 0;
-		if (p)
-			(void)hipFree(p);
-		p = nullptr;
-		bytes = 0;
+		release();
 		hipError_t e = hipMalloc(&p, need);
 		if (e != hipSuccess) {
 			g_last_error = std::string("hipMalloc: ") + hipGetErrorString(e);
@@ -54,6 +55,32 @@ struct DevBuf {
 	}
 	template <typename T> T *as() const { return (T *)p; }
 };
+
+// Where a decode call's outputs go: the arrays of include/ofdmrx.h for its frames, all in ONE memory space (HBM, or pinned host
+// memory).  The public entries build it once, from their arguments and what ofdmrx_set_esn0_rows / ofdmrx_set_attempt_log left in
+// the handle; everything below takes it by value.
+struct Outputs {
+	uint8_t *payload = nullptr;    // n x PAYLOAD_BYTES
+	Result *res = nullptr;
+	float *esn0 = nullptr;         // n x ROWS_MAX, or null: off
+	Attempt *att = nullptr;        // n x ATTEMPTS_MAX and n counts, or both null: off
+	int32_t *att_counts = nullptr;
+	Outputs from(size_t first) const   // the same arrays, starting at frame `first`
+	{
+		return { payload + first * PAYLOAD_BYTES, res + first, esn0 ? esn0 + first * ROWS_MAX : nullptr,
+			att ? att + first * ATTEMPTS_MAX : nullptr, att ? att_counts + first : nullptr };
+	}
+};
+
+inline size_t sample_bytes(int fmt) { return fmt == OFDMRX_FMT_S16 ? 2 : fmt == OFDMRX_FMT_U8 ? 1 : 4; }
+// what every decode entry asks of its samples: a known format, one or two channels (decode.cc:578), and a start on a sample-frame
+// boundary - the kernels load I/Q pairs with one access
+inline int check_samples(const void *samples, int fmt, int channels)
+{
+	if (!samples || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channels < 1 || channels > 2)
+		return OFDMRX_E_ARG;
+	return (size_t)samples % (sample_bytes(fmt) * (size_t)channels) ? OFDMRX_E_ARG : 0;
+}
 
 // ---- optional roctx ranges around the stage launches (OFDMRX_ROCTX=1): markers for rocprofv3 --marker-trace.
 // The library is looked up at run time, so libofdmrx.so keeps its single dependency (libamdhip64).
@@ -125,8 +152,8 @@ struct ofdmrx_handle {
 	// chunk; what crosses to the list decoder's streams goes through the queue below
 	int cap = 0;              // frames the buffers below are sized for
 	long cap_samples = 0;     // samples per frame the mono buffers are sized for
-	DevBuf st, hdr_soft, cons, slope, yint, precision, slot_of, res, payload;
-	DevBuf payload2, res2;    // second parity of the device-side output staging (host-pointer entry)
+	DevBuf st, hdr_soft, cons, slope, yint, precision, slot_of;
+	DevBuf payload[2], res[2];   // device-side output staging by chunk parity (host-pointer entry, pinned outputs); [0]: the debug entries' outputs
 	DevBuf chunk_flags;       // per-chunk device flags (k_theil_sen: the largest row count met)
 	DevBuf soft;              // the level stores of the resident list decoders (2 MiB each)
 	// the list decoder's work queue (kernels.h: ListQueue): control block + one slot per entry
@@ -154,14 +181,14 @@ struct ofdmrx_handle {
 	int polar_grid = 0;       // resident list decoders
 	int cert_mode = 1;        // 1: syndrome certificate (adaptive), 0: every frame with a header is list-decoded
 	float *esn0_user = nullptr;   // ofdmrx_set_esn0_rows: n x OFDMRX_ROWS_MAX floats in the memory space of the results (NULL = off)
-	DevBuf esn0_dev, esn0_dev2;   // host-pointer entry: per-chunk device staging of the row values, by parity
+	DevBuf esn0_dev[2];           // host-pointer entry: per-chunk device staging of the row values, by parity
 	ofdmrx_attempt *att_user = nullptr;   // ofdmrx_set_attempt_log: n x (OFDMRX_MAX_SKIP + 1) records and n counts, same memory space (NULL = off)
 	int32_t *att_counts_user = nullptr;
-	DevBuf att_dev, att_dev2, attc_dev, attc_dev2;   // host-pointer entry: their device staging, by parity
+	DevBuf att_dev[2], attc_dev[2];   // host-pointer entry: their device staging, by parity
 	ListQueue *queue() const { return q_ctl.as<ListQueue>(); }
 	DevBuf dc, z;             // mono front end only
 	long last_spf = 0;
-	DevBuf in_stage, in_stage2, skip_stage;
+	DevBuf in_stage[2], skip_stage;   // host-pointer entry: the samples of a chunk, by parity; the call's SKIP counts
 	void *out_stage[2] = { nullptr, nullptr };   // pinned host staging of payloads + results (host-pointer entry)
 	size_t out_stage_cap[2] = { 0, 0 };
 	DevBuf carr;                   // payload carriers of every symbol (demod -> Theil-Sen) at the rates whose demodulator does not form the rows
@@ -215,6 +242,14 @@ int host_wait(ofdmrx_handle *h);                                                
 void run_sc_pass(ofdmrx_handle *h, hipStream_t s, int n, bool force = true, int chunk_seq = 0);   // api_pipeline.cpp
 int ensure_events(ofdmrx_handle *h, size_t need);                                           // api_pipeline.cpp: the call's event pool
 size_t mark(ofdmrx_handle *h, hipStream_t on = nullptr);                                    // ... one event recorded on `on`
+// a call begins: its events and timing spans start over, and it has not been split between two lanes
+inline void begin_call(ofdmrx_handle *h)
+{
+	h->ev_used = 0;
+	h->spans.clear();
+	h->split_at = 0;
+}
+int finish_call(ofdmrx_handle *h, int r);                                                   // api_pipeline.cpp: a call ends: r, or the sticky event error
 // the chunk pipeline for n records of a stream decode: every frame is the whole stream fb (stride 0), record k starts from
 // d_records[k] (header, demod, ...); device or pinned host outputs like ofdmrx_decode_batch_device; keeps the call's events so far
-int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, uint8_t *d_payload, ofdmrx_frame_result *d_results);
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out);

@@ -32,18 +32,24 @@ static size_t events_per_chunk(int max_skip) { return 32 + 16 * (size_t)(max_ski
 //   front2  Theil-Sen
 //   back    k_back: rotation, SNR, certificate / LLRs into the list decoder's queue; k_queue_snap
 // D9 + D10 for the queued frames = a flush (run_flush).
-static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const SyncState *seed, size_t *t_begin,
-	size_t wait_before_sync, size_t *ev_after_sync);
-// wait_before_sync (event index or -1): the first sync launch waits for it; *ev_after_sync (nullable) receives the event
-// recorded right after that launch - the pipeline gives the scan a slot of its own between two list-decoder launches.
-// seed (nullable, stream decode): the chunk's frames start from these SyncStates - preambles already found and accepted, as a
-// round with skip_left = 0 leaves them - instead of the sync rounds: header once, then demod.
-static int run_front1(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const int32_t *d_skip, int max_skip,
-	size_t *t_begin, Attempt *d_att, int32_t *d_att_counts, size_t wait_before_sync = (size_t)-1, size_t *ev_after_sync = nullptr,
-	const SyncState *seed = nullptr)
+
+// what the debug taps and ofdmrx_last_chunk_first_frame ask about the chunk front1 has just enqueued
+static int front1_done(ofdmrx_handle *h, FrameBatch fb, int n)
 {
-	if (seed)
-		return run_front1_seeded(h, s, fb, n, seed, t_begin, wait_before_sync, ev_after_sync);
+	HIP_OK(hipGetLastError());
+	h->last_n = n;
+	h->last_mono = fb.channels == 1;
+	h->last_spf = fb.samples_per_frame;
+	h->last_fb = fb;
+	return 0;
+}
+
+// front1 with the sync rounds of the batch entries.
+// wait_before_sync (event index or -1): the first sync launch waits for it; *ev_after_sync receives the event recorded right
+// after that launch - the pipeline gives the scan a slot of its own between two list-decoder launches.
+static int run_front1_rounds(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const int32_t *d_skip, int max_skip,
+	size_t *t_begin, Attempt *d_att, int32_t *d_att_counts, size_t wait_before_sync, size_t *ev_after_sync)
+{
 	const bool mono = fb.channels == 1;
 	SyncState *st = h->st.as<SyncState>();
 	cf *z = mono ? h->z.as<cf>() : nullptr;
@@ -67,7 +73,7 @@ static int run_front1(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, con
 			launch_sync(s, h->rate, n, fb, z, h->dev, st, h->sc_scratch.as<cf>(), ma);
 		}
 		size_t b = mark(h, s);
-		if (round == 0 && ev_after_sync)
+		if (round == 0)
 			*ev_after_sync = b;
 		{
 			Range r("ofdmrx:header_osd");
@@ -86,15 +92,12 @@ static int run_front1(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, con
 	h->spans.push_back({ OFDMRX_T_DEMOD, last, d });
 	h->spans.push_back({ OFDMRX_T_FRONT, e0, e1 });
 	*t_begin = e0;
-	HIP_OK(hipGetLastError());
-	h->last_n = n;
-	h->last_mono = mono;
-	h->last_spf = fb.samples_per_frame;
-	h->last_fb = fb;
-	return 0;
+	return front1_done(h, fb, n);
 }
 
-// run_front1 for a chunk of records of a stream decode (api_stream.cpp): the records' SyncStates, header + OSD, demod
+// front1 for a chunk of records of a stream decode (api_stream.cpp): the chunk's frames start from the SyncStates `seed` -
+// preambles already found and accepted, as a round with skip_left = 0 leaves them - instead of the sync rounds: header + OSD
+// once, then demod.  The header launch stands where the first sync launch would (wait_before_sync, *ev_after_sync as above).
 static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const SyncState *seed, size_t *t_begin,
 	size_t wait_before_sync, size_t *ev_after_sync)
 {
@@ -106,8 +109,7 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 	if (wait_before_sync != (size_t)-1)
 		HIP_OK(hipStreamWaitEvent(s, h->ev_pool[wait_before_sync], 0));
 	size_t b = mark(h, s);
-	if (ev_after_sync)
-		*ev_after_sync = b;
+	*ev_after_sync = b;
 	{
 		Range r("ofdmrx:header_osd");
 		launch_header(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->hdr_soft.as<int8_t>(), nullptr, nullptr);
@@ -121,12 +123,7 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 	size_t d = mark(h, s);
 	h->spans.push_back({ OFDMRX_T_DEMOD, c, d });
 	*t_begin = e0;
-	HIP_OK(hipGetLastError());
-	h->last_n = n;
-	h->last_mono = false;
-	h->last_spf = fb.samples_per_frame;
-	h->last_fb = fb;
-	return 0;
+	return front1_done(h, fb, n);
 }
 
 static int run_front2(ofdmrx_handle *h, hipStream_t s, int n)
@@ -160,7 +157,7 @@ void run_sc_pass(ofdmrx_handle *h, hipStream_t s, int n, bool force, int chunk_s
 // D5's rotation + D6-D8 + the certificate: frames it finishes get payload + result here, the others a queue slot and their LLRs
 // sc_force: the list-1 pass takes everything that waits in its ring (else whole residencies); chunk_seq: which chunk of its call
 static int run_back(ofdmrx_handle *h, hipStream_t s, int par, int n, Result *d_res, float *d_esn0, uint8_t *d_payload,
-	uint8_t *payload_later = nullptr, Result *res_later = nullptr, bool sc_force = true, int chunk_seq = 0)
+	uint8_t *payload_later, Result *res_later, bool sc_force, int chunk_seq)
 {
 	size_t e5 = mark(h, s);
 	{
@@ -211,20 +208,14 @@ static int run_flush(ofdmrx_handle *h, hipStream_t s_polar, hipStream_t s_fin, i
 	return 0;
 }
 
-static int check_args(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t spf, size_t stride,
-	size_t n, const void *payload, const void *results)
+static int check_args(ofdmrx_handle *h, FrameBatch fb, size_t n, const void *payload, const void *results)
 {
-	if (!h || !samples || !payload || !results || n == 0)
+	if (!h || !payload || !results || n == 0 || check_samples(fb.samples, fb.fmt, fb.channels))
 		return OFDMRX_E_ARG;
-	if (fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channels < 1 || channels > 2)   // decode.cc:578
+	const size_t spf = (size_t)fb.samples_per_frame, frame_bytes = sample_bytes(fb.fmt) * (size_t)fb.channels;
+	if (spf == 0 || spf > (size_t)0x7fffffff / 2 || fb.frame_stride_bytes < spf * frame_bytes)
 		return OFDMRX_E_ARG;
-	size_t bps = fmt == OFDMRX_FMT_S16 ? 2 : fmt == OFDMRX_FMT_U8 ? 1 : 4;
-	if (spf == 0 || spf > (size_t)0x7fffffff / 2 || stride < spf * bps * (size_t)channels)
-		return OFDMRX_E_ARG;
-	const size_t frame_bytes = bps * (size_t)channels;        // one sample frame: the kernels load I/Q pairs with one access
-	if ((stride % frame_bytes) || ((size_t)samples % frame_bytes))   // whole sample frames between the frames, frames on such a boundary
-		return OFDMRX_E_ARG;
-	return 0;
+	return fb.frame_stride_bytes % frame_bytes ? OFDMRX_E_ARG : 0;   // whole sample frames between the frames: every frame on such a boundary
 }
 
 // decode.cc:583-585,448: SKIP = number of preambles to pass over.  0..OFDMRX_MAX_SKIP per frame; anything else is an
@@ -258,7 +249,7 @@ struct ChunkPlan {
 // halves when it is large enough for half-sized kernels to fill the machine: the second half's kernels run beside the first half's
 // copies (8192 frames: 1.49 -> 1.57 M frames/s; four quarters: 1.40 M, profiles/r04_v25_one_chunk_split.txt).  With the outputs
 // left in HBM one chunk is the faster form (1.86 against 1.77 M).
-static ChunkPlan plan_chunks(const ofdmrx_handle *h, size_t n_frames, bool host_side = false)
+static ChunkPlan plan_chunks(const ofdmrx_handle *h, size_t n_frames, bool host_side)
 {
 	ChunkPlan p;
 	size_t step = (size_t)h->chunk;
@@ -304,12 +295,14 @@ struct PipeHooks {
 // * k_back(c) waits for flush(c - 2) to have ended, copies included: that bounds the queue (ensure_capacity) and frees the host
 //   entry's output staging of that parity.
 // A call of one chunk (and OFDMRX_NO_OVERLAP=1, the profiler's setting: every kernel alone on the machine) runs all of it on A.
-static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &plan, int fmt, int channels, size_t spf, size_t stride,
-	const int32_t *d_skip, int max_skip, const SyncState *seed = nullptr)
+// batch: the call's frames but for where chunk c's are (before_front1).  seed (nullable, stream decode): the frames are records
+// that start from these SyncStates instead of the sync rounds (run_front1_seeded).
+static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &plan, FrameBatch batch, const int32_t *d_skip, int max_skip,
+	const SyncState *seed)
 {
 	const size_t n_chunks = plan.count(), NONE = (size_t)-1;
 	int r = ensure_events(h, h->ev_used + n_chunks * events_per_chunk(max_skip) + 8);
-	r = r ? r : ensure_capacity(h, (int)plan.largest(), channels == 1, (long)spf);
+	r = r ? r : ensure_capacity(h, (int)plan.largest(), batch.channels == 1, batch.samples_per_frame);
 	if (r)
 		return r;
 	const bool overlap = n_chunks > 1 && !std::getenv("OFDMRX_NO_OVERLAP");
@@ -341,7 +334,7 @@ static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &pla
 	};
 	for (size_t c = 0; c < n_chunks && !r; ++c) {
 		const int n = (int)plan.size(c);
-		FrameBatch fb{ nullptr, stride, (long)spf, fmt, channels };
+		FrameBatch fb = batch;
 		size_t ready = NONE, ev_sync = NONE;
 		uint8_t *pay;
 		Result *res;
@@ -356,8 +349,9 @@ static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &pla
 			HIP_OK(hipStreamWaitEvent(sa, h->ev_pool[ready], 0));
 		if (att && overlap && c >= 2)                             // (host entry: the log's staging of this parity has left with chunk c - 2)
 			HIP_OK(hipStreamWaitEvent(sa, h->ev_pool[ev_fin[c - 2]], 0));
-		r = run_front1(h, sa, fb, n, d_skip ? d_skip + plan.first(c) : nullptr, max_skip, &t0s[c], att, att_counts,
-			(scan_slot && c >= 2) ? ev_polar[c - 2] : NONE, &ev_sync, seed ? seed + plan.first(c) : nullptr);
+		const size_t slot_free = (scan_slot && c >= 2) ? ev_polar[c - 2] : NONE;
+		r = seed ? run_front1_seeded(h, sa, fb, n, seed + plan.first(c), &t0s[c], slot_free, &ev_sync)
+			: run_front1_rounds(h, sa, fb, n, d_skip ? d_skip + plan.first(c) : nullptr, max_skip, &t0s[c], att, att_counts, slot_free, &ev_sync);
 		h->last_first = plan.first(c);
 		if (!r && overlap && c >= 1)                              // flush(c - 1): its LLRs are in the queue, sync(c) is on its way
 			r = flush(c - 1, ev_sync);
@@ -400,7 +394,7 @@ static int host_pinned(const void *p)
 	return a.type == hipMemoryTypeHost ? 1 : 0;
 }
 
-static int finish_call(ofdmrx_handle *h, int r)
+int finish_call(ofdmrx_handle *h, int r)
 {
 	if (!r && h->sticky != hipSuccess) {
 		g_last_error = std::string("hipEventRecord: ") + hipGetErrorString(h->sticky);
@@ -410,13 +404,65 @@ static int finish_call(ofdmrx_handle *h, int r)
 	return r;
 }
 
-// seed (nullable): the frames are records of a stream decode that start from these SyncStates (run_front1_seeded); fresh = false:
-// the call's events and timing spans so far (the stream scan's) are kept
-static int decode_device_lane(ofdmrx_handle *h, const void *d_samples, int fmt, int channels,
-	size_t spf, size_t stride, size_t n_frames, const int32_t *d_skip, uint8_t *d_payload, ofdmrx_frame_result *d_results,
-	const SyncState *seed = nullptr, bool fresh = true)
+// What the hooks of every entry know of their call: its chunks, its samples (batch.samples: frame 0, wherever the entry's
+// samples are), where its outputs go.  Which buffer of a staging pair chunk c uses and where chunk c's part of the call's
+// arrays begins are written here, once.
+struct CallHooks : PipeHooks {
+	ofdmrx_handle *const h;
+	const ChunkPlan &plan;
+	const FrameBatch batch;
+	const Outputs out;
+	CallHooks(ofdmrx_handle *h, const ChunkPlan &plan, FrameBatch batch, Outputs out) : h(h), plan(plan), batch(batch), out(out) {}
+	static size_t par(size_t c) { return c & 1; }             // chunk c - 2, the last user of that buffer, has left it (run_pipeline)
+	size_t n_of(size_t c) const { return plan.size(c); }
+	const char *samples_of(size_t c) const { return (const char *)batch.samples + plan.first(c) * batch.frame_stride_bytes; }
+	Outputs out_of(size_t c) const { return out.from(plan.first(c)); }
+	Outputs staged(size_t c) const { return { h->payload[par(c)].as<uint8_t>(), h->res[par(c)].as<Result>() }; }   // the chunk's payloads + records in HBM
+};
+// both buffers of a staging pair (one, for a call of one chunk) for `bytes` each
+static int ensure_pair(DevBuf (&pair)[2], size_t bytes, size_t n_chunks)
 {
-	int r = 0;
+	int r = pair[0].ensure(bytes);
+	return (r || n_chunks < 2) ? r : pair[1].ensure(bytes);
+}
+
+// Device entry, outputs in HBM: every kernel writes into the caller's arrays.
+struct DeviceHooks : CallHooks {
+	using CallHooks::CallHooks;
+	int before_front1(size_t c, FrameBatch *fb, size_t *) override { fb->samples = samples_of(c); return 0; }
+	void dst(size_t c, uint8_t **p, Result **r) override { *p = out_of(c).payload; *r = out_of(c).res; }
+	float *esn0(size_t c) override { return out_of(c).esn0; }
+	void attempts(size_t c, Attempt **l, int32_t **n) override { *l = out_of(c).att; *n = out_of(c).att_counts; }
+};
+// Device entry, outputs in pinned HOST memory (hipHostMalloc / a registered range): every chunk's payloads and records leave for
+// them on the copy queue right behind the chunk's flush - beside the next chunk's kernels - instead of one copy of the whole batch
+// that the caller hangs behind the call.  (Samples stay where they are: in HBM; the row values and the attempt log are written
+// where they go, over PCIe.)
+struct PinnedOutHooks : DeviceHooks {
+	using DeviceHooks::DeviceHooks;
+	int prepare()
+	{
+		int r = ensure_pair(h->payload, plan.largest() * PAYLOAD_BYTES, plan.count());
+		return r ? r : ensure_pair(h->res, plan.largest() * sizeof(Result), plan.count());
+	}
+	void dst(size_t c, uint8_t **p, Result **r) override { *p = staged(c).payload; *r = staged(c).res; }
+	// the chunk's staging leaves right behind its k_back (certified frames complete, queued frames with their preliminary record
+	// and a zeroed payload); what the list decoder finishes later k_finish writes into the pinned host arrays itself, over PCIe -
+	// so the queue keeps working across chunks on this route too
+	void dst_later(size_t c, uint8_t **p, Result **r) override { *p = out_of(c).payload; *r = out_of(c).res; }
+	int before_flush(size_t c, hipStream_t s, hipEvent_t back_done) override
+	{
+		HIP_OK(hipStreamWaitEvent(s, back_done, 0));
+		HIP_OK(hipMemcpyAsync(out_of(c).payload, staged(c).payload, n_of(c) * PAYLOAD_BYTES, hipMemcpyDeviceToHost, s));
+		HIP_OK(hipMemcpyAsync(out_of(c).res, staged(c).res, n_of(c) * sizeof(Result), hipMemcpyDeviceToHost, s));
+		return 0;
+	}
+};
+
+// n_frames frames through one handle's pipeline, samples in HBM.  seed (nullable): the frames are records of a stream decode that
+// start from these SyncStates (run_front1_seeded)
+static int decode_device_lane(ofdmrx_handle *h, FrameBatch fb, size_t n_frames, const int32_t *d_skip, Outputs out, const SyncState *seed)
+{
 	int max_skip = 0;
 	if (d_skip) {
 		// the counts steer the host loop (rounds of sync + header): fetched on the handle's stream, so they are ordered
@@ -428,110 +474,49 @@ static int decode_device_lane(ofdmrx_handle *h, const void *d_samples, int fmt, 
 		if (max_skip < 0)
 			return max_skip;
 	}
-	if (fresh) {
-		h->ev_used = 0;
-		h->spans.clear();
-	}
-	const int out_kind = host_pinned(d_payload), res_kind = host_pinned(d_results);
+	const int out_kind = host_pinned(out.payload), res_kind = host_pinned(out.res);
 	if (out_kind < 0 || res_kind < 0 || out_kind != res_kind)
 		return OFDMRX_E_ARG;
 	// the optional outputs live in the memory space of the results: pinned host memory too, then
-	if (out_kind == 1 && ((h->esn0_user && host_pinned(h->esn0_user) != 1) ||
-			(h->att_user && (host_pinned(h->att_user) != 1 || host_pinned(h->att_counts_user) != 1))))
+	if (out_kind == 1 && ((out.esn0 && host_pinned(out.esn0) != 1) || (out.att && (host_pinned(out.att) != 1 || host_pinned(out.att_counts) != 1))))
 		return OFDMRX_E_ARG;
 	const ChunkPlan plan = plan_chunks(h, n_frames, out_kind == 1);
-	struct Dev : PipeHooks {
-		const ChunkPlan *plan; const char *samples; size_t stride; uint8_t *pay; Result *res;
-		int before_front1(size_t c, FrameBatch *fb, size_t *) override { fb->samples = samples + plan->first(c) * stride; return 0; }
-		ofdmrx_handle *h = nullptr;
-		bool host_out = false;                                    // pay / res are pinned host memory: per-chunk device buffers + copies
-		void dst(size_t c, uint8_t **p, Result **r) override
-		{
-			if (host_out) {
-				*p = ((c & 1) ? h->payload2 : h->payload).as<uint8_t>();
-				*r = ((c & 1) ? h->res2 : h->res).as<Result>();
-			} else {
-				*p = pay + plan->first(c) * PAYLOAD_BYTES;
-				*r = res + plan->first(c);
-			}
-		}
-		// host outputs: the chunk's staging leaves right behind its k_back (certified frames complete, queued frames with their
-		// preliminary record and a zeroed payload); what the list decoder finishes later k_finish writes into the pinned host arrays
-		// itself, over PCIe - so the queue keeps working across chunks on this route too
-		void dst_later(size_t c, uint8_t **p, Result **r) override
-		{
-			*p = host_out ? pay + plan->first(c) * PAYLOAD_BYTES : nullptr;
-			*r = host_out ? res + plan->first(c) : nullptr;
-		}
-		int before_flush(size_t c, hipStream_t s, hipEvent_t back_done) override
-		{
-			if (!host_out)
-				return 0;
-			uint8_t *p;
-			Result *rs;
-			dst(c, &p, &rs);
-			HIP_OK(hipStreamWaitEvent(s, back_done, 0));
-			HIP_OK(hipMemcpyAsync(pay + plan->first(c) * PAYLOAD_BYTES, p, plan->size(c) * PAYLOAD_BYTES, hipMemcpyDeviceToHost, s));
-			HIP_OK(hipMemcpyAsync(res + plan->first(c), rs, plan->size(c) * sizeof(Result), hipMemcpyDeviceToHost, s));
-			return 0;
-		}
-		float *rows = nullptr;
-		float *esn0(size_t c) override { return rows ? rows + plan->first(c) * ROWS_MAX : nullptr; }
-		Attempt *att = nullptr;
-		int32_t *attc = nullptr;
-		void attempts(size_t c, Attempt **l, int32_t **n) override
-		{
-			*l = att ? att + plan->first(c) * ATTEMPTS_MAX : nullptr;
-			*n = att ? attc + plan->first(c) : nullptr;
-		}
-	} hooks;
-	hooks.rows = h->esn0_user;
-	hooks.att = (Attempt *)h->att_user;
-	hooks.attc = h->att_counts_user;
-	hooks.plan = &plan;
-	hooks.samples = (const char *)d_samples;
-	hooks.stride = stride;
-	hooks.pay = d_payload;
-	hooks.res = (Result *)d_results;
-	// Outputs in pinned HOST memory (hipHostMalloc / a registered range): every chunk's payloads and records leave for them on the
-	// copy queue right behind the chunk's flush - beside the next chunk's kernels - instead of one copy of the whole batch that the
-	// caller hangs behind the call.  (Samples stay where they are: in HBM.)
-	hooks.host_out = out_kind == 1;
-	if (hooks.host_out) {
-		hooks.h = h;
-		const size_t nc = plan.largest();
-		r = h->payload.ensure(nc * PAYLOAD_BYTES);
-		r = r ? r : h->res.ensure(nc * sizeof(Result));
-		if (plan.count() > 1) {
-			r = r ? r : h->payload2.ensure(nc * PAYLOAD_BYTES);
-			r = r ? r : h->res2.ensure(nc * sizeof(Result));
-		}
-		if (r)
-			return r;
+	if (out_kind == 1) {
+		PinnedOutHooks hooks(h, plan, fb, out);
+		int r = hooks.prepare();
+		return r ? r : finish_call(h, run_pipeline(h, hooks, plan, fb, d_skip, max_skip, seed));
 	}
-	return finish_call(h, run_pipeline(h, hooks, plan, fmt, channels, spf, stride, d_skip, max_skip, seed));
+	DeviceHooks hooks(h, plan, fb, out);
+	return finish_call(h, run_pipeline(h, hooks, plan, fb, d_skip, max_skip, seed));
 }
 
-int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, uint8_t *d_payload, ofdmrx_frame_result *d_results)
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out)
 {
-	return decode_device_lane(h, fb.samples, fb.fmt, fb.channels, (size_t)fb.samples_per_frame, fb.frame_stride_bytes, n, nullptr,
-		d_payload, d_results, d_records, false);
+	return decode_device_lane(h, fb, n, nullptr, out, d_records);
+}
+
+// what the setters left in the handle, beside the call's own two arrays
+static Outputs outputs_of(const ofdmrx_handle *h, uint8_t *payload, ofdmrx_frame_result *results)
+{
+	return { payload, (Result *)results, h->esn0_user, (Attempt *)h->att_user, h->att_counts_user };
 }
 
 extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels,
 	size_t spf, size_t stride, size_t n_frames, const int32_t *d_skip, uint8_t *d_payload, ofdmrx_frame_result *d_results)
 {
-	int r = check_args(h, d_samples, fmt, channels, spf, stride, n_frames, d_payload, d_results);
+	const FrameBatch fb{ d_samples, stride, (long)spf, fmt, channels };
+	int r = check_args(h, fb, n_frames, d_payload, d_results);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
+	const Outputs out = outputs_of(h, d_payload, d_results);
 	// two lanes: whole chunks to each, the second half through lane2 (see ofdmrx_handle).  Not for calls with SKIP counts (their
 	// rounds are steered from the host), nor below four chunks of at least 1024 frames: a pipeline that short has nothing to share
 	const size_t chunk = (size_t)h->chunk;
 	const bool could_split = h->lanes == 2 && !d_skip && chunk >= 1024 && n_frames >= 4 * chunk;
-	h->split_at = 0;
+	begin_call(h);
 	if (!could_split)
-		return decode_device_lane(h, d_samples, fmt, channels, spf, stride, n_frames, d_skip, d_payload, d_results);
+		return decode_device_lane(h, fb, n_frames, d_skip, out, nullptr);
 	if (!h->lane2) {
 		ofdmrx_config c2 = h->cfg;
 		c2.stream = nullptr;                                      // a stream of its own
@@ -541,7 +526,7 @@ extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_sample
 		if (r) {                                                  // (no room for a second pipeline: one lane)
 			h->lane2 = nullptr;
 			h->lanes = 1;
-			return decode_device_lane(h, d_samples, fmt, channels, spf, stride, n_frames, d_skip, d_payload, d_results);
+			return decode_device_lane(h, fb, n_frames, d_skip, out, nullptr);
 		}
 		h->lane2->cert_mode = h->cert_mode;
 		h->lane2->sc_mode = h->sc_mode;
@@ -553,13 +538,13 @@ extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_sample
 	// whatever the caller's stream has enqueued so far (the samples' producer) comes first for the second lane too
 	HIP_OK(hipEventRecord(h->ev_lane_in, h->stream));
 	HIP_OK(hipStreamWaitEvent(g->stream, h->ev_lane_in, 0));
-	g->esn0_user = h->esn0_user ? h->esn0_user + n1 * ROWS_MAX : nullptr;
-	g->att_user = h->att_user ? h->att_user + n1 * ATTEMPTS_MAX : nullptr;
-	g->att_counts_user = h->att_counts_user ? h->att_counts_user + n1 : nullptr;
-	r = decode_device_lane(h, d_samples, fmt, channels, spf, stride, n1, nullptr, d_payload, d_results);
+	r = decode_device_lane(h, fb, n1, nullptr, out, nullptr);
 	if (r)
 		return r;
-	r = decode_device_lane(g, (const char *)d_samples + n1 * stride, fmt, channels, spf, stride, n2, nullptr, d_payload + n1 * PAYLOAD_BYTES, d_results + n1);
+	FrameBatch fb2 = fb;
+	fb2.samples = (const char *)d_samples + n1 * stride;
+	begin_call(g);
+	r = decode_device_lane(g, fb2, n2, nullptr, out.from(n1), nullptr);
 	h->split_at = n1;
 	// the caller's stream sees the finished batch
 	HIP_OK(hipEventRecord(h->ev_lane_done, g->stream));
@@ -567,15 +552,126 @@ extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_sample
 	return r;
 }
 
+// the arrays `from` has for n frames and their places in `to`, in the order in which the host entry copies
+// them: device staging -> pinned staging -> the caller's arrays
+struct Piece { void *to; const void *from; size_t bytes; };
+static std::array<Piece, 5> pieces(const Outputs &to, const Outputs &from, size_t n)
+{
+	return { { { to.payload, from.payload, n * PAYLOAD_BYTES }, { to.res, from.res, n * sizeof(Result) },
+		{ to.esn0, from.esn0, from.esn0 ? n * ROWS_MAX * sizeof(float) : 0 }, { to.att, from.att, from.att ? n * ATTEMPTS_MAX * sizeof(Attempt) : 0 },
+		{ to.att_counts, from.att_counts, from.att ? n * sizeof(int32_t) : 0 } } };
+}
+
 // Host-pointer entry: the same chunk pipeline with three copies hung on its events.  Chunk c+1 is copied in on a copy
 // stream while chunk c runs (from pageable memory that call blocks the host thread - which is exactly the time the GPU
 // needs for chunk c; from pinned memory it is asynchronous); the staging buffer of chunk c is free once front1(c) has
 // read it (Theil-Sen, LLRs, polar work on the carriers).  Payloads and results leave through pinned staging buffers
 // right behind the back half of their chunk.
+struct HostHooks : CallHooks {                                // (batch.samples and out: the caller's HOST arrays)
+	const size_t nc;                                          // frames the staging of one parity is laid out for: the largest chunk
+	const size_t esn0_bytes, att_bytes, attc_bytes;           // ... and what it takes for the optional outputs
+	std::vector<size_t> ev_in, ev_f1, ev_out;
+	size_t copied_out = 0;
+	HostHooks(ofdmrx_handle *h, const ChunkPlan &plan, FrameBatch batch, Outputs out) : CallHooks(h, plan, batch, out), nc(plan.largest()),
+		esn0_bytes(out.esn0 ? nc * ROWS_MAX * sizeof(float) : 0), att_bytes(out.att ? nc * ATTEMPTS_MAX * sizeof(Attempt) : 0),
+		attc_bytes(out.att ? nc * sizeof(int32_t) : 0), ev_in(plan.count(), (size_t)-1), ev_f1(ev_in), ev_out(ev_in) {}
+	int prepare()                                             // the staging of both parities: samples in, outputs in HBM, outputs in pinned memory
+	{
+		const size_t n_chunks = plan.count(), out_bytes = nc * (PAYLOAD_BYTES + sizeof(Result)) + esn0_bytes + att_bytes + attc_bytes;
+		int r = ensure_pair(h->in_stage, nc * batch.frame_stride_bytes, n_chunks);
+		r = r ? r : ensure_pair(h->payload, nc * PAYLOAD_BYTES, n_chunks);
+		r = r ? r : ensure_pair(h->res, nc * sizeof(Result), n_chunks);
+		if (esn0_bytes)
+			r = r ? r : ensure_pair(h->esn0_dev, esn0_bytes, n_chunks);
+		if (att_bytes) {
+			r = r ? r : ensure_pair(h->att_dev, att_bytes, n_chunks);
+			r = r ? r : ensure_pair(h->attc_dev, attc_bytes, n_chunks);
+		}
+		if (r)
+			return r;
+		for (size_t q = 0; q < std::min<size_t>(n_chunks, 2); ++q)
+			if (h->out_stage_cap[q] < out_bytes) {
+				if (h->out_stage[q])
+					(void)hipHostFree(h->out_stage[q]);
+				h->out_stage[q] = nullptr;
+				h->out_stage_cap[q] = 0;
+				HIP_OK(hipHostMalloc(&h->out_stage[q], out_bytes, hipHostMallocDefault));
+				h->out_stage_cap[q] = out_bytes;
+			}
+		return 0;
+	}
+	void *stage(size_t c) const { return h->in_stage[par(c)].p; }
+	Outputs dev_stage(size_t c) const                         // the chunk's outputs in HBM, those the call has
+	{
+		Outputs o = staged(c);
+		o.esn0 = out.esn0 ? h->esn0_dev[par(c)].as<float>() : nullptr;
+		o.att = out.att ? h->att_dev[par(c)].as<Attempt>() : nullptr;
+		o.att_counts = out.att ? h->attc_dev[par(c)].as<int32_t>() : nullptr;
+		return o;
+	}
+	Outputs pinned(size_t c) const                            // ... and in the pinned staging: array after array, nc frames each
+	{
+		char *d = (char *)h->out_stage[par(c)], *opt = d + nc * (PAYLOAD_BYTES + sizeof(Result));
+		return { (uint8_t *)d, (Result *)(d + nc * PAYLOAD_BYTES), out.esn0 ? (float *)opt : nullptr,
+			out.att ? (Attempt *)(opt + esn0_bytes) : nullptr, out.att ? (int32_t *)(opt + esn0_bytes + att_bytes) : nullptr };
+	}
+	int copy_in(size_t c)
+	{
+		if (c >= 2 && ev_f1[c - 2] != (size_t)-1)    // the staging buffer was last read by front1(c-2)
+			HIP_OK(hipStreamWaitEvent(h->stream_c, h->ev_pool[ev_f1[c - 2]], 0));
+		HIP_OK(hipMemcpyAsync(stage(c), samples_of(c), n_of(c) * batch.frame_stride_bytes, hipMemcpyHostToDevice, h->stream_c));
+		ev_in[c] = mark(h, h->stream_c);
+		return 0;
+	}
+	int copy_out(size_t c)                             // pinned staging -> the caller's arrays, once chunk c has left the device
+	{
+		HIP_OK(hipEventSynchronize(h->ev_pool[ev_out[c]]));
+		for (const Piece &p : pieces(out_of(c), pinned(c), n_of(c)))
+			if (p.bytes)
+				std::memcpy(p.to, p.from, p.bytes);
+		return 0;
+	}
+	int before_front1(size_t c, FrameBatch *fb, size_t *ready) override
+	{
+		if (c == 0) {
+			int r = copy_in(0);
+			if (r)
+				return r;
+		}
+		fb->samples = stage(c);
+		*ready = ev_in[c];
+		return 0;
+	}
+	int after_front1(size_t c, size_t ev) override
+	{
+		ev_f1[c] = ev;
+		return c + 1 < plan.count() ? copy_in(c + 1) : 0;    // chunk c+1 travels while chunk c is decoded
+	}
+	void dst(size_t c, uint8_t **p, Result **r) override { *p = staged(c).payload; *r = staged(c).res; }
+	float *esn0(size_t c) override { return dev_stage(c).esn0; }
+	void attempts(size_t c, Attempt **l, int32_t **n) override { *l = dev_stage(c).att; *n = dev_stage(c).att_counts; }
+	bool outputs_leave_by_chunk() override { return true; }
+	int after_flush(size_t c, hipStream_t s) override
+	{
+		// out_stage[par(c)] still holds chunk c-2 until the host has copied it out
+		while (copied_out + 2 <= c) {
+			int r = copy_out(copied_out++);
+			if (r)
+				return r;
+		}
+		for (const Piece &p : pieces(pinned(c), dev_stage(c), n_of(c)))
+			if (p.bytes)
+				HIP_OK(hipMemcpyAsync(p.to, p.from, p.bytes, hipMemcpyDeviceToHost, s));
+		ev_out[c] = mark(h, s);
+		return 0;
+	}
+};
+
 extern "C" int ofdmrx_decode_batch(ofdmrx_handle *h, const void *samples, int fmt, int channels,
 	size_t spf, size_t stride, size_t n_frames, const int32_t *skip, uint8_t *payload_out, ofdmrx_frame_result *results)
 {
-	int r = check_args(h, samples, fmt, channels, spf, stride, n_frames, payload_out, results);
+	const FrameBatch fb{ samples, stride, (long)spf, fmt, channels };
+	int r = check_args(h, fb, n_frames, payload_out, results);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -585,158 +681,24 @@ extern "C" int ofdmrx_decode_batch(ofdmrx_handle *h, const void *samples, int fm
 		if (max_skip < 0)
 			return max_skip;
 	}
-	h->ev_used = 0;
-	h->spans.clear();
-	h->split_at = 0;
+	begin_call(h);
 	if (!h->stream_c)
 		HIP_OK(hipStreamCreateWithFlags(&h->stream_c, hipStreamNonBlocking));
 	const ChunkPlan plan = plan_chunks(h, n_frames, true);
-	const size_t n_chunks = plan.count(), nc = plan.largest();
-	r = ensure_events(h, n_chunks * (events_per_chunk(max_skip) + 4) + 8);
-	r = r ? r : h->in_stage.ensure(nc * stride);
-	if (n_chunks > 1) {
-		r = r ? r : h->in_stage2.ensure(nc * stride);
-		r = r ? r : h->payload2.ensure(nc * PAYLOAD_BYTES);
-		r = r ? r : h->res2.ensure(nc * sizeof(Result));
-	}
-	r = r ? r : h->payload.ensure(nc * PAYLOAD_BYTES);
-	r = r ? r : h->res.ensure(nc * sizeof(Result));
-	if (skip)
-		r = r ? r : h->skip_stage.ensure(n_frames * sizeof(int32_t));
+	HostHooks hooks(h, plan, fb, outputs_of(h, payload_out, results));
+	r = ensure_events(h, plan.count() * (events_per_chunk(max_skip) + 4) + 8);
+	r = r ? r : hooks.prepare();
 	if (r)
 		return r;
-	const size_t esn0_bytes = h->esn0_user ? nc * ROWS_MAX * sizeof(float) : 0;
-	if (esn0_bytes) {
-		r = h->esn0_dev.ensure(esn0_bytes);
-		if (!r && n_chunks > 1)
-			r = h->esn0_dev2.ensure(esn0_bytes);
-		if (r)
-			return r;
-	}
-	const size_t att_bytes = h->att_user ? nc * ATTEMPTS_MAX * sizeof(Attempt) : 0, attc_bytes = h->att_user ? nc * sizeof(int32_t) : 0;
-	if (att_bytes) {
-		r = h->att_dev.ensure(att_bytes);
-		r = r ? r : h->attc_dev.ensure(attc_bytes);
-		if (!r && n_chunks > 1) {
-			r = h->att_dev2.ensure(att_bytes);
-			r = r ? r : h->attc_dev2.ensure(attc_bytes);
-		}
-		if (r)
-			return r;
-	}
-	const size_t out_bytes = nc * (PAYLOAD_BYTES + sizeof(Result)) + esn0_bytes + att_bytes + attc_bytes;
-	for (int q = 0; q < (n_chunks > 1 ? 2 : 1); ++q)
-		if (h->out_stage_cap[q] < out_bytes) {
-			if (h->out_stage[q])
-				(void)hipHostFree(h->out_stage[q]);
-			h->out_stage[q] = nullptr;
-			h->out_stage_cap[q] = 0;
-			HIP_OK(hipHostMalloc(&h->out_stage[q], out_bytes, hipHostMallocDefault));
-			h->out_stage_cap[q] = out_bytes;
-		}
 	if (skip) {
+		r = h->skip_stage.ensure(n_frames * sizeof(int32_t));
+		if (r)
+			return r;
 		HIP_OK(hipMemcpyAsync(h->skip_stage.p, skip, n_frames * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
 		HIP_OK(hipStreamSynchronize(h->stream));         // `skip` may be pageable and go out of scope
 	}
-	struct Host : PipeHooks {
-		ofdmrx_handle *h; const ChunkPlan *plan; const char *samples; size_t stride, n_chunks, nc;
-		uint8_t *payload_out; ofdmrx_frame_result *results;
-		std::vector<size_t> ev_in, ev_f1, ev_out;
-		size_t copied_out = 0;
-		size_t n_of(size_t c) const { return plan->size(c); }
-		void *stage(size_t c) const { return (c & 1) ? h->in_stage2.p : h->in_stage.p; }
-		int copy_in(size_t c)
-		{
-			if (c >= 2 && ev_f1[c - 2] != (size_t)-1)    // the staging buffer was last read by front1(c-2)
-				HIP_OK(hipStreamWaitEvent(h->stream_c, h->ev_pool[ev_f1[c - 2]], 0));
-			HIP_OK(hipMemcpyAsync(stage(c), samples + plan->first(c) * stride, n_of(c) * stride, hipMemcpyHostToDevice, h->stream_c));
-			ev_in[c] = mark(h, h->stream_c);
-			return 0;
-		}
-		int copy_out(size_t c)                             // pinned staging -> the caller's arrays, once chunk c has left the device
-		{
-			HIP_OK(hipEventSynchronize(h->ev_pool[ev_out[c]]));
-			const char *src = (const char *)h->out_stage[c & 1];
-			std::memcpy(payload_out + plan->first(c) * PAYLOAD_BYTES, src, n_of(c) * PAYLOAD_BYTES);
-			std::memcpy(results + plan->first(c), src + nc * PAYLOAD_BYTES, n_of(c) * sizeof(Result));
-			if (h->esn0_user)
-				std::memcpy(h->esn0_user + plan->first(c) * ROWS_MAX, src + nc * (PAYLOAD_BYTES + sizeof(Result)), n_of(c) * ROWS_MAX * sizeof(float));
-			if (h->att_user) {
-				std::memcpy(h->att_user + plan->first(c) * ATTEMPTS_MAX, src + att_off, n_of(c) * ATTEMPTS_MAX * sizeof(Attempt));
-				std::memcpy(h->att_counts_user + plan->first(c), src + att_off + nc * ATTEMPTS_MAX * sizeof(Attempt), n_of(c) * sizeof(int32_t));
-			}
-			return 0;
-		}
-		size_t att_off = 0;                                // where the attempt log starts in the pinned staging
-		void attempts(size_t c, Attempt **l, int32_t **n) override
-		{
-			*l = h->att_user ? ((c & 1) ? h->att_dev2 : h->att_dev).as<Attempt>() : nullptr;
-			*n = h->att_user ? ((c & 1) ? h->attc_dev2 : h->attc_dev).as<int32_t>() : nullptr;
-		}
-		int before_front1(size_t c, FrameBatch *fb, size_t *ready) override
-		{
-			if (c == 0) {
-				int r = copy_in(0);
-				if (r)
-					return r;
-			}
-			fb->samples = stage(c);
-			*ready = ev_in[c];
-			return 0;
-		}
-		int after_front1(size_t c, size_t ev) override
-		{
-			ev_f1[c] = ev;
-			return c + 1 < n_chunks ? copy_in(c + 1) : 0;    // chunk c+1 travels while chunk c is decoded
-		}
-		void dst(size_t c, uint8_t **p, Result **r) override
-		{
-			*p = ((c & 1) ? h->payload2 : h->payload).as<uint8_t>();
-			*r = ((c & 1) ? h->res2 : h->res).as<Result>();
-		}
-		float *esn0(size_t c) override { return h->esn0_user ? ((c & 1) ? h->esn0_dev2 : h->esn0_dev).as<float>() : nullptr; }
-		bool outputs_leave_by_chunk() override { return true; }
-		int after_flush(size_t c, hipStream_t s) override
-		{
-			// out_stage[c & 1] still holds chunk c-2 until the host has copied it out
-			while (copied_out + 2 <= c) {
-				int r = copy_out(copied_out++);
-				if (r)
-					return r;
-			}
-			uint8_t *p;
-			Result *rs;
-			dst(c, &p, &rs);
-			char *d = (char *)h->out_stage[c & 1];
-			HIP_OK(hipMemcpyAsync(d, p, n_of(c) * PAYLOAD_BYTES, hipMemcpyDeviceToHost, s));
-			HIP_OK(hipMemcpyAsync(d + nc * PAYLOAD_BYTES, rs, n_of(c) * sizeof(Result), hipMemcpyDeviceToHost, s));
-			if (h->esn0_user)
-				HIP_OK(hipMemcpyAsync(d + nc * (PAYLOAD_BYTES + sizeof(Result)), esn0(c), n_of(c) * ROWS_MAX * sizeof(float), hipMemcpyDeviceToHost, s));
-			if (h->att_user) {
-				Attempt *al;
-				int32_t *an;
-				attempts(c, &al, &an);
-				HIP_OK(hipMemcpyAsync(d + att_off, al, n_of(c) * ATTEMPTS_MAX * sizeof(Attempt), hipMemcpyDeviceToHost, s));
-				HIP_OK(hipMemcpyAsync(d + att_off + nc * ATTEMPTS_MAX * sizeof(Attempt), an, n_of(c) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-			}
-			ev_out[c] = mark(h, s);
-			return 0;
-		}
-	} hooks;
-	hooks.h = h;
-	hooks.samples = (const char *)samples;
-	hooks.stride = stride;
-	hooks.plan = &plan;
-	hooks.n_chunks = n_chunks;
-	hooks.nc = nc;
-	hooks.payload_out = payload_out;
-	hooks.results = results;
-	hooks.att_off = nc * (PAYLOAD_BYTES + sizeof(Result)) + esn0_bytes;
-	hooks.ev_in.assign(n_chunks, (size_t)-1);
-	hooks.ev_f1.assign(n_chunks, (size_t)-1);
-	hooks.ev_out.assign(n_chunks, (size_t)-1);
-	r = run_pipeline(h, hooks, plan, fmt, channels, spf, stride, skip ? h->skip_stage.as<int32_t>() : nullptr, max_skip);
-	while (!r && hooks.copied_out < n_chunks)
+	r = run_pipeline(h, hooks, plan, fb, skip ? h->skip_stage.as<int32_t>() : nullptr, max_skip, nullptr);
+	while (!r && hooks.copied_out < plan.count())
 		r = hooks.copy_out(hooks.copied_out++);
 	if (!r)
 		HIP_OK(hipStreamSynchronize(h->stream));

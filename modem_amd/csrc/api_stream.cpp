@@ -6,20 +6,14 @@
 //   the records through the chunk pipeline of the batch entries (api_pipeline.cpp: decode_records), every frame = the whole stream
 #include "api_internal.h"
 
-static size_t sample_bytes(int fmt) { return fmt == OFDMRX_FMT_S16 ? 2 : fmt == OFDMRX_FMT_U8 ? 1 : 4; }
-
-static int stream_args(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t n_samples, size_t max_frames,
-	const void *payload, const void *results, const size_t *n_preambles)
+// fb: the whole recording as one frame (stride 0)
+static int stream_args(ofdmrx_handle *h, FrameBatch fb, size_t max_frames, const void *payload, const void *results, const size_t *n_preambles)
 {
-	if (!h || !samples || !n_preambles || n_samples == 0 || n_samples > (size_t)0x7fffffff / 2)
+	if (!h || !n_preambles || fb.samples_per_frame <= 0 || fb.samples_per_frame > 0x7fffffffL / 2)
 		return OFDMRX_E_ARG;
 	if (max_frames && (!payload || !results))
 		return OFDMRX_E_ARG;
-	if (fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channels < 1 || channels > 2)   // decode.cc:578
-		return OFDMRX_E_ARG;
-	if ((size_t)samples % (sample_bytes(fmt) * (size_t)channels))                    // (like the batch entries: whole sample frames)
-		return OFDMRX_E_ARG;
-	return 0;
+	return check_samples(fb.samples, fb.fmt, fb.channels);        // (like the batch entries)
 }
 
 // the scan's launches for the 2-channel view fb2 of the stream: edges, accept, records (at most max_rec)
@@ -42,15 +36,13 @@ static int enqueue_scan(ofdmrx_handle *h, FrameBatch fb2, long n, long max_rec)
 	return 0;
 }
 
-// The stream scan of d_samples (device memory) and the records through the pipeline.  *n_pre: accepted preambles.
-static int decode_stream_dev(ofdmrx_handle *h, const void *d_samples, int fmt, int channels, size_t n_samples, size_t max_frames,
-	uint8_t *d_payload, ofdmrx_frame_result *d_results, size_t *n_pre)
+// The stream scan of fb (the recording, in device memory) and the records through the pipeline.  *n_pre: accepted preambles.
+// out has no attempt log: stream calls do not write it, every record is one preamble's outcome already
+static int decode_stream_dev(ofdmrx_handle *h, FrameBatch fb, size_t max_frames, Outputs out, size_t *n_pre)
 {
 	hipStream_t s = h->stream;
-	const long n = (long)n_samples;
-	h->ev_used = 0;
-	h->spans.clear();
-	h->split_at = 0;
+	const long n = fb.samples_per_frame;
+	begin_call(h);
 	int r = ensure_events(h, 16);
 	r = r ? r : h->sx_counts.ensure(2 * sizeof(long long));
 	if (r)
@@ -58,8 +50,8 @@ static int decode_stream_dev(ofdmrx_handle *h, const void *d_samples, int fmt, i
 	if (h->sx_edge_cap == 0)                                      // a preamble every frame and a few noise triggers fit (else: grown below)
 		h->sx_edge_cap = std::max(4096L, n / 2048);
 	const size_t e0 = mark(h, s);
-	FrameBatch fb2{ d_samples, 0, n, fmt, 2 };
-	if (channels == 1) {                                          // D1 over the whole stream, then its analytic signal read as I/Q pairs
+	FrameBatch fb2 = fb;                                          // what the scan and the pipeline read: I/Q pairs
+	if (fb.channels == 1) {                                       // D1 over the whole stream, then its analytic signal read as I/Q pairs
 		const long ntiles = (n + 4095) / 4096;
 		const int ck_n = mono_ck_per_frame(n);
 		r = h->sx_dc_end.ensure((size_t)ntiles * sizeof(double));
@@ -69,7 +61,6 @@ static int decode_stream_dev(ofdmrx_handle *h, const void *d_samples, int fmt, i
 		if (r)
 			return r;
 		Range rg("ofdmrx:stream_front");
-		const FrameBatch fb{ d_samples, 0, n, fmt, 1 };
 		launch_stream_dc(s, fb, h->host.front, h->sx_dc_end.as<double>(), h->sx_dc_in.as<double>(), h->sx_ck.as<double>());
 		launch_front_end(s, h->rate, 1, fb, mono_args(h->host.front, h->sx_ck.as<double>(), ck_n), h->sx_z.as<cf>());
 		fb2 = FrameBatch{ h->sx_z.p, 0, n, OFDMRX_FMT_F32, 2 };
@@ -101,38 +92,26 @@ static int decode_stream_dev(ofdmrx_handle *h, const void *d_samples, int fmt, i
 		h->last_n = 0;
 		h->last_first = 0;
 		HIP_OK(hipStreamSynchronize(s));
-		if (h->sticky != hipSuccess) {
-			g_last_error = std::string("hipEventRecord: ") + hipGetErrorString(h->sticky);
-			h->sticky = hipSuccess;
-			return OFDMRX_E_HIP;
-		}
-		return 0;
+		return finish_call(h, 0);
 	}
-	// the attempt log is not written by stream calls: every record is one preamble's outcome already
-	ofdmrx_attempt *att = h->att_user;
-	int32_t *attc = h->att_counts_user;
-	h->att_user = nullptr;
-	h->att_counts_user = nullptr;
-	r = decode_records(h, fb2, h->sx_rec.as<SyncState>(), n_rec, d_payload, d_results);
-	h->att_user = att;
-	h->att_counts_user = attc;
-	return r;
+	return decode_records(h, fb2, h->sx_rec.as<SyncState>(), n_rec, out);
 }
 
 extern "C" int ofdmrx_decode_stream_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels, size_t n_samples,
 	size_t max_frames, uint8_t *d_payload_out, ofdmrx_frame_result *d_results, size_t *n_preambles)
 {
-	int r = stream_args(h, d_samples, fmt, channels, n_samples, max_frames, d_payload_out, d_results, n_preambles);
+	const FrameBatch fb{ d_samples, 0, (long)n_samples, fmt, channels };
+	int r = stream_args(h, fb, max_frames, d_payload_out, d_results, n_preambles);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
-	return decode_stream_dev(h, d_samples, fmt, channels, n_samples, max_frames, d_payload_out, d_results, n_preambles);
+	return decode_stream_dev(h, fb, max_frames, Outputs{ d_payload_out, (Result *)d_results, h->esn0_user }, n_preambles);
 }
 
 extern "C" int ofdmrx_decode_stream(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t n_samples,
 	size_t max_frames, uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_preambles)
 {
-	int r = stream_args(h, samples, fmt, channels, n_samples, max_frames, payload_out, results, n_preambles);
+	int r = stream_args(h, FrameBatch{ samples, 0, (long)n_samples, fmt, channels }, max_frames, payload_out, results, n_preambles);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -141,43 +120,29 @@ extern "C" int ofdmrx_decode_stream(ofdmrx_handle *h, const void *samples, int f
 	if (r)
 		return r;
 	HIP_OK(hipMemcpyAsync(h->sx_in.p, samples, in_bytes, hipMemcpyHostToDevice, h->stream));
-	// outputs: device staging for as many records as the stream can hold (at most one per edge), copied out behind the call
-	const size_t room = std::min<size_t>(max_frames, (size_t)std::max(4096L, (long)(n_samples / 2048)));
-	r = h->sx_pay.ensure(std::max<size_t>(1, room) * PAYLOAD_BYTES);
-	r = r ? r : h->sx_res.ensure(std::max<size_t>(1, room) * sizeof(Result));
+	const FrameBatch fb{ h->sx_in.p, 0, (long)n_samples, fmt, channels };
+	// outputs: device staging for as many records as the stream can hold (at most one per edge), copied out behind the call;
+	// the Es/N0 rows likewise, in place of the caller's host array
+	float *const rows_user = h->esn0_user;
+	auto stage = [&](size_t frames) -> int {
+		int rr = h->sx_pay.ensure(std::max<size_t>(1, frames) * PAYLOAD_BYTES);
+		rr = rr ? rr : h->sx_res.ensure(std::max<size_t>(1, frames) * sizeof(Result));
+		const size_t cap = h->sx_pay.bytes / PAYLOAD_BYTES;
+		return (rr || !rows_user) ? rr : h->sx_esn0.ensure(std::max<size_t>(1, cap) * ROWS_MAX * sizeof(float));
+	};
+	auto staged = [&] { return Outputs{ h->sx_pay.as<uint8_t>(), h->sx_res.as<Result>(), rows_user ? h->sx_esn0.as<float>() : nullptr }; };
+	r = stage(std::min<size_t>(max_frames, (size_t)std::max(4096L, (long)(n_samples / 2048))));
 	if (r)
 		return r;
-	float *rows_user = h->esn0_user;
 	size_t n_pre = 0;
-	// a first pass finds how many records there are; the staging is sized for them before the pipeline runs
-	r = 0;
-	{
-		const size_t stage_cap = h->sx_pay.bytes / PAYLOAD_BYTES;
-		// esn0 rows: device staging in place of the caller's host array during the call
-		if (rows_user) {
-			r = h->sx_esn0.ensure(std::max<size_t>(1, stage_cap) * ROWS_MAX * sizeof(float));
-			if (r)
-				return r;
-			h->esn0_user = h->sx_esn0.as<float>();
-		}
-		r = decode_stream_dev(h, h->sx_in.p, fmt, channels, n_samples, std::min(max_frames, stage_cap), h->sx_pay.as<uint8_t>(),
-			(ofdmrx_frame_result *)h->sx_res.p, &n_pre);
-		h->esn0_user = rows_user;
-		if (r)
-			return r;
-	}
-	size_t n_rec = std::min(n_pre, max_frames);
+	// a first pass finds how many records there are
+	r = decode_stream_dev(h, fb, std::min(max_frames, h->sx_pay.bytes / PAYLOAD_BYTES), staged(), &n_pre);
+	if (r)
+		return r;
+	const size_t n_rec = std::min(n_pre, max_frames);
 	if (n_rec > h->sx_pay.bytes / PAYLOAD_BYTES) {                // more records than the staging held (a stream of many short frames): again, with room
-		r = h->sx_pay.ensure(n_rec * PAYLOAD_BYTES);
-		r = r ? r : h->sx_res.ensure(n_rec * sizeof(Result));
-		if (!r && rows_user)
-			r = h->sx_esn0.ensure(n_rec * ROWS_MAX * sizeof(float));
-		if (r)
-			return r;
-		if (rows_user)
-			h->esn0_user = h->sx_esn0.as<float>();
-		r = decode_stream_dev(h, h->sx_in.p, fmt, channels, n_samples, n_rec, h->sx_pay.as<uint8_t>(), (ofdmrx_frame_result *)h->sx_res.p, &n_pre);
-		h->esn0_user = rows_user;
+		r = stage(n_rec);
+		r = r ? r : decode_stream_dev(h, fb, n_rec, staged(), &n_pre);
 		if (r)
 			return r;
 	}

@@ -136,7 +136,5 @@ extern "C" int ofdmrx_tx_encode_stream(ofdmrx_handle *h, const uint8_t *payload,
 		e = e == hipSuccess ? hipMemcpy(pcm, dx.p, out_bytes, hipMemcpyDeviceToHost) : e;
 		if (e != hipSuccess) { g_last_error = hipGetErrorString(e); r = OFDMRX_E_HIP; }
 	}
-	dp.release();
-	dx.release();
 	return r;
 }
