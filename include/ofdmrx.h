@@ -48,7 +48,9 @@ extern "C" {
  *   6: ofdmrx_config.flags bit 3 (OFDMRX_FLAG_TWO_LANES): a device-entry call of four chunks or more runs its second half through a
  *      second pipeline beside the first (same outputs; the handle then holds the state of two pipelines); the list-1 pass takes whole
  *      residencies of its decoders and leaves the rest to the next chunk's run (same outputs)
- *   7: ofdmrx_decode_stream, ofdmrx_decode_stream_device (every preamble of one recording in one call), ofdmrx_debug_stream_edges */
+ *   7: ofdmrx_decode_stream, ofdmrx_decode_stream_device (every preamble of one recording in one call), ofdmrx_debug_stream_edges;
+ *      added within 1.7 (the minor number stays: a caller detects them by symbol): the live feed - ofdmrx_feed_begin, ofdmrx_feed_push,
+ *      ofdmrx_feed_end, ofdmrx_feed_lag, ofdmrx_feed_resident_samples */
 #define OFDMRX_ABI_MINOR 7
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -230,6 +232,53 @@ int ofdmrx_decode_stream_device(ofdmrx_handle *h, const void *d_samples, int sam
  * maximum of each run (t_max) and index_max; at most max_edges of them are written, *n_edges counts all.  HOST pointers. */
 int ofdmrx_debug_stream_edges(ofdmrx_handle *h, const float *timing, size_t n, size_t max_edges,
 	int64_t *t_edge, int64_t *t_max, int32_t *index_max, size_t *n_edges);
+
+/*
+ * Live feed (added within revision 1.7): the same recording pushed block by block as it arrives, each record returned once its last
+ * sample is in.  One feed per handle; HOST pointers; the calls block.
+ *   begin   opens a feed of `channels` interleaved values of sample_format: position 0, record 0.
+ *   push    n_samples more sample frames (0 is allowed); returns the records that have become due, in preamble order.
+ *   end     the stream is over: the last partial tile is scanned with n = the samples fed and every pending preamble decoded with
+ *           the samples past the end read as zero - what ofdmrx_decode_stream does for a frame the recording cuts off.
+ * The records of every push and of end, concatenated, are the records ofdmrx_decode_stream returns for the concatenation of the
+ * pushed samples, however the stream is cut into pushes: sc_start is the absolute stream index (64-bit: the length of a feed is not
+ * limited, only what is resident), n_sync_rejects counts from the start of the feed, record k is the (k+1)-th accepted preamble.
+ * 2-channel input: payloads and every byte of every ofdmrx_frame_result equal the one-call result (the scan's tiles stay on
+ * absolute multiples of 4096 samples and form their sums themselves; the trigger is carried from push to push as the small discrete
+ * state the one-call scan carries from tile to tile).  Mono input: the DC blocker's double-precision states are composed in another
+ * order, so cfo_rad, cfo_fine, sfo_slope and esn0_db_last may differ within the 1e-5 of the intermediates and bit_flips as described
+ * at ofdmrx_frame_result; everything decided is equal.
+ * Due: records leave in preamble order.  A preamble whose header fails is due once the scan has passed its edge (the scan works on
+ * complete tiles of 4096 samples) and its header symbol has arrived; one with a valid header once the last sample of the frame of
+ * that header's mode has arrived - the end of its last symbol, sc_start + ofdmrx_frame_samples(rate, mode) - 2 rate -
+ * (2 x 1440 + 160) rate / 8000 samples - plus ofdmrx_feed_lag(), which is 0: no kernel reads past the frame.
+ * max_frames: at most that many records are written (payload_out: 5380 bytes each; NULL outputs only with max_frames 0) and
+ * *n_records counts them; the rest stay staged in the handle, in order, *n_left counts those, and later push (n_samples may be 0) or
+ * end calls return them.  The feed closes when an end call leaves *n_left == 0; begin then starts a new stream.  After the first
+ * end call push accepts n_samples == 0 only.  Es/N0 rows (ofdmrx_set_esn0_rows, a host pointer): row block i belongs to the i-th
+ * record the call writes.  The attempt log is not written and OFDMRX_FLAG_TWO_LANES is ignored, as for stream calls;
+ * ofdmrx_get_timing and the stage taps describe the last decode a feed call ran.
+ * OFDMRX_E_ARG: push / end without begin, begin while a feed is open, any ofdmrx_decode_batch* / ofdmrx_decode_stream* while a feed
+ * is open, a NULL handle, NULL samples with n_samples > 0, NULL n_records / n_left, NULL outputs with max_frames > 0, a bad format
+ * or channel count, samples not on a sample-frame boundary - all before any device call.  ofdmrx_destroy frees an open feed.
+ * ofdmrx_feed_resident_samples: sample frames of the stream held on the device now: fed - base, where base is the largest multiple
+ * of 4096 not above the smallest of
+ *   scanned - BUFFER_LEN                      (scanned: the scan's frontier, the largest multiple of 4096 <= fed; BUFFER_LEN = 6 x 1440 rate / 8000)
+ *   sc_start of the oldest preamble not yet decoded
+ *   i_max - (MATCH_DEL + 4 x 1440 rate / 8000) while the trigger is on (i_max: the maximum of the timing metric in the running run)
+ *   mono input: the start of the front-end stretch (7936 samples) that holds the last sample, minus 320
+ * taken before a push appends its samples.  With at most one frame pending and the trigger's runs shorter than a frame it never
+ * exceeds ofdmrx_frame_samples(rate, 13) + BUFFER_LEN + 3 x 4096 + the largest push so far; each further pending frame may add its
+ * span.  (Device memory: two buffers of up to 1.5 x the largest window, the window moves from one to the other.)
+ * -1 (OFDMRX_E_ARG) from either query without an open feed.
+ */
+int ofdmrx_feed_begin(ofdmrx_handle *h, int sample_format, int channels);
+int ofdmrx_feed_push(ofdmrx_handle *h, const void *samples, size_t n_samples, size_t max_frames,
+	uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_records, size_t *n_left);
+int ofdmrx_feed_end(ofdmrx_handle *h, size_t max_frames, uint8_t *payload_out, ofdmrx_frame_result *results,
+	size_t *n_records, size_t *n_left);
+long long ofdmrx_feed_lag(ofdmrx_handle *h);
+long long ofdmrx_feed_resident_samples(ofdmrx_handle *h);
 
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);

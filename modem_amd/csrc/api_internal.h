@@ -1,4 +1,4 @@
-// api_internal.h -- what the four files of the C ABI share: the handle, its buffers, the helpers that cross files.
+// api_internal.h -- what the files of the C ABI share: the handle, its buffers, the helpers that cross files.
 // (round 6: ofdmrx_api.cpp was one file of 1700 lines - api_create.cpp / api_pipeline.cpp / api_debug.cpp / api_tx.cpp now)
 #pragma once
 #include "../../include/ofdmrx.h"
@@ -220,6 +220,7 @@ struct ofdmrx_handle {
 	// stream decode (api_stream.cpp): scratch kept between calls, grown on demand
 	DevBuf sx_in, sx_z, sx_ck, sx_dc_end, sx_dc_in, sx_fn, sx_carry, sx_edges, sx_counts, sx_rec, sx_pay, sx_res, sx_esn0, sx_timing;
 	long sx_edge_cap = 0;     // edges the edge buffer holds
+	struct ofdmrx_feed *feed = nullptr;   // the open live feed (api_feed.cpp), one per handle
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -253,3 +254,4 @@ int finish_call(ofdmrx_handle *h, int r);                                       
 // the chunk pipeline for n records of a stream decode: every frame is the whole stream fb (stride 0), record k starts from
 // d_records[k] (header, demod, ...); device or pinned host outputs like ofdmrx_decode_batch_device; keeps the call's events so far
 int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out);
+void feed_free(ofdmrx_handle *h);                                                           // api_feed.cpp: the open feed and its window go

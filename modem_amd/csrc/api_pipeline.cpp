@@ -506,8 +506,8 @@ extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_sample
 {
 	const FrameBatch fb{ d_samples, stride, (long)spf, fmt, channels };
 	int r = check_args(h, fb, n_frames, d_payload, d_results);
-	if (r)
-		return r;
+	if (r || h->feed)                                             // (a handle with an open feed decodes nothing else)
+		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	const Outputs out = outputs_of(h, d_payload, d_results);
 	// two lanes: whole chunks to each, the second half through lane2 (see ofdmrx_handle).  Not for calls with SKIP counts (their
@@ -672,8 +672,8 @@ extern "C" int ofdmrx_decode_batch(ofdmrx_handle *h, const void *samples, int fm
 {
 	const FrameBatch fb{ samples, stride, (long)spf, fmt, channels };
 	int r = check_args(h, fb, n_frames, payload_out, results);
-	if (r)
-		return r;
+	if (r || h->feed)
+		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	int max_skip = 0;
 	if (skip) {

@@ -1,58 +1,156 @@
-// decode_stream_main.cpp -- `decode_stream OUTDIR INPUT`: every frame of a recording in one call (ofdmrx_decode_stream).
+// decode_stream_main.cpp -- `decode_stream [--live] OUTDIR INPUT`: every frame of a recording.
 // OUTDIR/<k>.dat holds the 5380 bytes `decode OUT INPUT k` writes (descrambled; zeros for a failed frame), for every preamble k
 // the SKIP loop of decode.cc:390-448 would count; one summary line per record on stderr.  Exit status 0 like `decode`
 // (decode.cc:619), 1 on argument, WAV or library errors.
+// Without --live the whole recording is read and decoded in one call (ofdmrx_decode_stream).  With --live the WAV header is read,
+// then the body in blocks of one second as it arrives (INPUT `-`: standard input, e.g. a recorder's pipe), every block is pushed into
+// a feed (ofdmrx_feed_*) and every record is written as soon as it is returned: the same files and lines, each when its frame is in.
 #include "wav_read.h"
 #include <cstdlib>
 #include <string>
 
-int main(int argc, char **argv)
+// one record: its line on stderr, its file
+static bool emit_record(const std::string &outdir, size_t k, const ofdmrx_frame_result &q, const uint8_t *payload)
 {
-	if (argc != 3) {
-		std::fprintf(stderr, "usage: %s OUTDIR INPUT\n", argv[0]);
-		return 1;
+	static const char *names[] = { "ok", "no sync", "OSD error", "header CRC error", "mode unsupported", "call sign unsupported",
+		"payload decoding error" };
+	char cs[10];
+	unsigned long long v = q.call_sign;
+	for (int i = 8; i >= 0; --i, v /= 37)                         // base37_decoder, decode.cc:155-159
+		cs[i] = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"[v % 37];
+	cs[9] = 0;
+	std::fprintf(stderr, "%zu: sample %lld mode %d call sign %s %s bit flips %d\n", k, (long long)q.sc_start, q.oper_mode, cs,
+		q.status >= 0 && q.status <= 6 ? names[q.status] : "?", q.bit_flips);
+	const std::string name = outdir + "/" + std::to_string(k) + ".dat";
+	FILE *f = std::fopen(name.c_str(), "wb");
+	if (!f) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for writing.\n", name.c_str());
+		return false;
 	}
-	const std::string outdir = argv[1];
-	const char *input_name = argv[2];
-	if (!std::strcmp(input_name, "-"))
-		input_name = "/dev/stdin";
-	Wav w;
-	if (!read_wav(input_name, w) || w.frames == 0) {
-		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
-		return 1;
-	}
-	if (w.channels < 1 || w.channels > 2) {
+	std::fwrite(payload, 1, OFDMRX_PAYLOAD_BYTES, f);
+	std::fclose(f);
+	return true;
+}
+
+static bool supported(int channels, int rate)
+{
+	if (channels < 1 || channels > 2) {
 		std::fprintf(stderr, "Only real or analytic signal (one or two channels) supported.\n");
-		return 1;
+		return false;
 	}
-	if (w.rate != 8000 && w.rate != 16000 && w.rate != 44100 && w.rate != 48000) {   // decode.cc:590-605
+	if (rate != 8000 && rate != 16000 && rate != 44100 && rate != 48000) {   // decode.cc:590-605
 		std::fprintf(stderr, "Unsupported sample rate.\n");
-		return 1;
+		return false;
 	}
 	if (ofdmrx_abi_version() != OFDMRX_ABI_VERSION || ofdmrx_abi_minor() < 7) {
 		std::fprintf(stderr, "libofdmrx: ABI %d.%d, this program needs %d.7\n", ofdmrx_abi_version(), ofdmrx_abi_minor(), OFDMRX_ABI_VERSION);
-		return 1;
+		return false;
 	}
+	return true;
+}
+
+static ofdmrx_handle *create(int rate)
+{
 	ofdmrx_config cfg{};
 	cfg.abi_version = OFDMRX_ABI_VERSION;
-	cfg.sample_rate = w.rate;
+	cfg.sample_rate = rate;
 	cfg.list_size = 8;
 	cfg.device = 0;
 	cfg.chunk_frames = 64;
 	cfg.descramble = 1;
 	ofdmrx_handle *h = nullptr;
-	int r = ofdmrx_create(&cfg, &h);
+	const int r = ofdmrx_create(&cfg, &h);
 	if (r) {
 		std::fprintf(stderr, "ofdmrx_create: %s\n", ofdmrx_strerror(r));
+		return nullptr;
+	}
+	return h;
+}
+
+// the body block by block through a feed
+static int run_live(const std::string &outdir, const char *input_name)
+{
+	WavStream w;
+	if (!wav_open(input_name, w)) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
 		return 1;
 	}
+	if (!supported(w.channels, w.rate))
+		return 1;
+	ofdmrx_handle *h = create(w.rate);
+	if (!h)
+		return 1;
+	int r = ofdmrx_feed_begin(h, w.fmt, w.channels);
+	const size_t cap = 64;
+	std::vector<uint8_t> out(cap * OFDMRX_PAYLOAD_BYTES), pcm;
+	std::vector<ofdmrx_frame_result> res(cap);
+	size_t k = 0, total = 0;
+	bool written = true;
+	// one push (or the end of the feed) and every record it makes ready: when more are ready than the arrays hold, further calls
+	// without samples take the rest
+	auto step = [&](bool end, const void *samples, size_t n) -> int {
+		size_t n_rec = 0, n_left = 0;
+		do {
+			const int rr = end ? ofdmrx_feed_end(h, cap, out.data(), res.data(), &n_rec, &n_left)
+				: ofdmrx_feed_push(h, samples, n, cap, out.data(), res.data(), &n_rec, &n_left);
+			if (rr)
+				return rr;
+			samples = nullptr;
+			n = 0;
+			for (size_t i = 0; i < n_rec && written; ++i, ++k)
+				written = emit_record(outdir, k, res[i], out.data() + i * OFDMRX_PAYLOAD_BYTES);
+		} while (n_left && written);
+		return 0;
+	};
+	for (bool last = false; !r && written && !last;) {
+		const size_t n = wav_read_block(w, (size_t)w.rate, pcm);  // one second; fewer at the end of the body
+		total += n;
+		last = n < (size_t)w.rate;
+		if (n)
+			r = step(false, pcm.data(), n);
+	}
+	if (!r && written && total == 0) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
+		written = false;
+	}
+	if (!r && written)
+		r = step(true, nullptr, 0);
+	if (r)
+		std::fprintf(stderr, "ofdmrx_feed: %s\n", ofdmrx_strerror(r));
+	ofdmrx_destroy(h);
+	return (r || !written) ? 1 : 0;
+}
+
+int main(int argc, char **argv)
+{
+	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
+	if (argc != 3 && !live) {
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n", argv[0]);
+		return 1;
+	}
+	const std::string outdir = argv[live ? 2 : 1];
+	const char *input_name = argv[live ? 3 : 2];
+	if (!std::strcmp(input_name, "-"))
+		input_name = "/dev/stdin";
+	if (live)
+		return run_live(outdir, input_name);
+	Wav w;
+	if (!read_wav(input_name, w) || w.frames == 0) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
+		return 1;
+	}
+	if (!supported(w.channels, w.rate))
+		return 1;
+	ofdmrx_handle *h = create(w.rate);
+	if (!h)
+		return 1;
 	size_t cap = 64, n_pre = 0;
 	std::vector<uint8_t> out;
 	std::vector<ofdmrx_frame_result> res;
 	for (;;) {                                                    // a second call only when the recording holds more than the first guess
 		out.assign(cap * OFDMRX_PAYLOAD_BYTES, 0);
 		res.assign(cap, ofdmrx_frame_result{});
-		r = ofdmrx_decode_stream(h, w.pcm.data(), w.fmt, w.channels, w.frames, cap, out.data(), res.data(), &n_pre);
+		const int r = ofdmrx_decode_stream(h, w.pcm.data(), w.fmt, w.channels, w.frames, cap, out.data(), res.data(), &n_pre);
 		if (r) {
 			std::fprintf(stderr, "ofdmrx_decode_stream: %s\n", ofdmrx_strerror(r));
 			ofdmrx_destroy(h);
@@ -63,25 +161,8 @@ int main(int argc, char **argv)
 		cap = n_pre;
 	}
 	ofdmrx_destroy(h);
-	static const char *names[] = { "ok", "no sync", "OSD error", "header CRC error", "mode unsupported", "call sign unsupported",
-		"payload decoding error" };
-	for (size_t k = 0; k < n_pre; ++k) {
-		const ofdmrx_frame_result &q = res[k];
-		char cs[10];
-		unsigned long long v = q.call_sign;
-		for (int i = 8; i >= 0; --i, v /= 37)                     // base37_decoder, decode.cc:155-159
-			cs[i] = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"[v % 37];
-		cs[9] = 0;
-		std::fprintf(stderr, "%zu: sample %lld mode %d call sign %s %s bit flips %d\n", k, (long long)q.sc_start, q.oper_mode, cs,
-			q.status >= 0 && q.status <= 6 ? names[q.status] : "?", q.bit_flips);
-		const std::string name = outdir + "/" + std::to_string(k) + ".dat";
-		FILE *f = std::fopen(name.c_str(), "wb");
-		if (!f) {
-			std::fprintf(stderr, "Couldn't open file \"%s\" for writing.\n", name.c_str());
+	for (size_t k = 0; k < n_pre; ++k)
+		if (!emit_record(outdir, k, res[k], out.data() + k * OFDMRX_PAYLOAD_BYTES))
 			return 1;
-		}
-		std::fwrite(out.data() + k * OFDMRX_PAYLOAD_BYTES, 1, OFDMRX_PAYLOAD_BYTES, f);
-		std::fclose(f);
-	}
 	return 0;
 }

@@ -8,6 +8,9 @@
 //   k_stream_tile<.., true>   the tiles again, now with their incoming state: falling edges, t_max, index_max, in stream order
 //   k_stream_accept           decode.cc:110-151 for every edge (sc_accept_wg, shared with k_sync_accept)
 //   k_stream_records          a scan over accept / reject: record indices, cumulative rejects, the SyncState of every record
+// The live feed (api_feed.cpp) runs the same kernels push by push over a window of the stream: the WIN forms take
+// where the push's first tile / block lies in the stream and the state the last push left, and compute from the same absolute
+// positions as the one-call forms (whose instantiations are unchanged).
 #include "dev_common.h"
 #include "kernels.h"
 #include "mono_front.h"
@@ -39,16 +42,19 @@ struct Affine { double v, w; };                               // x -> w x + v
 __device__ __forceinline__ Affine aff_then(Affine l, Affine r) { return Affine{ r.v + r.w * l.v, l.w * r.w }; }
 
 // PASS 0: the state each tile ends on from a zero state; PASS 1: the kept states from the tile's true entry state tile_in[t]
-template <int PASS>
+// WIN (the live feed): tile 0 starts at the absolute position `origin` (a multiple of MONO_CK), fb.samples and ck are
+// the addresses position 0 / state 0 would have, fb.samples_per_frame the samples fed so far; only the states of complete blocks
+// of MONO_CK samples are kept (ck_n is unused)
+template <int PASS, bool WIN = false>
 __global__ __launch_bounds__(256) void k_sdc_tile(FrameBatch fb, FrontCoef co, double *__restrict__ tile_end, const double *__restrict__ tile_in,
-	double *__restrict__ ck, int ck_n)
+	double *__restrict__ ck, int ck_n, long origin = 0)
 {
 	const int tid = threadIdx.x;
 	const long t = blockIdx.x;
 	MonoFrame fr{ (const char *)fb.samples, fb.fmt, fb.samples_per_frame, nullptr };
 	__shared__ Affine sh[256];
 	const double a = (double)co.dc_a, g = (double)co.dc_b * (1.0 - a) * (double)fr.scale();
-	const long s0 = t * 4096 + (long)tid * 16;
+	const long s0 = (WIN ? origin : 0) + t * 4096 + (long)tid * 16;
 	double sl = 0.0;
 	float x8[8];
 	fr.load8(s0, x8);
@@ -63,15 +69,18 @@ __global__ __launch_bounds__(256) void k_sdc_tile(FrameBatch fb, FrontCoef co, d
 			tile_end[t] = me.v;
 	} else {
 		const double s_true = me.v + mono_pow(a, 16 * (tid + 1)) * tile_in[t];
-		const long m = t * (4096 / MONO_CK) + (tid >> 2);    // this thread ends sample 16 tid + 15 of its tile
-		if ((tid & 3) == 3 && m < ck_n)
+		const long m = (WIN ? origin / MONO_CK : 0) + t * (4096 / MONO_CK) + (tid >> 2);    // this thread ends sample 16 tid + 15 of its tile
+		if ((tid & 3) == 3 && (WIN ? (m + 1) * MONO_CK <= fr.n : m < ck_n))
 			ck[m] = s_true;
 	}
 }
 
 // the tiles' entry states C_0 = 0, C_{t+1} = tile_end[t] + a^4096 C_t: one workgroup, a range of tiles per thread composed as an
 // affine map, an exclusive scan of the maps, then each range in turn
-__global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *__restrict__ tile_end, double *__restrict__ tile_in, long ntiles)
+// entry (WIN; nullable): the state before the first tile, left by an earlier push
+template <bool WIN = false>
+__global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *__restrict__ tile_end, double *__restrict__ tile_in, long ntiles,
+	const double *__restrict__ entry = nullptr)
 {
 	const int tid = threadIdx.x;
 	__shared__ Affine sh[1024];
@@ -82,6 +91,10 @@ __global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *_
 		f = aff_then(f, Affine{ tile_end[k], A });
 	block_scan_incl<1024>(f, sh, tid, aff_then);
 	double c = tid ? sh[tid - 1].v : 0.0;                     // the maps applied to C_0 = 0
+	if constexpr (WIN) {
+		const double c0 = entry ? *entry : 0.0;                   // ... to C_0 = the entry state
+		c = tid ? sh[tid - 1].v + sh[tid - 1].w * c0 : c0;
+	}
 	for (long k = k0; k < k1; ++k) {
 		tile_in[k] = c;
 		c = tile_end[k] + A * c;
@@ -92,9 +105,17 @@ void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_e
 {
 	const long ntiles = (fb.samples_per_frame + 4095) / 4096;
 	const int ck_n = mono_ck_per_frame(fb.samples_per_frame);
-	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
-	hipLaunchKernelGGL(k_sdc_scan, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles);
-	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
+	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n, 0L);
+	hipLaunchKernelGGL(k_sdc_scan<false>, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles, nullptr);
+	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n, 0L);
+}
+void launch_stream_dc_window(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, long origin)
+{
+	const long ntiles = (fb.samples_per_frame - origin + 4095) / 4096;
+	const double *entry = origin > 0 ? ck + origin / MONO_CK - 1 : nullptr;
+	hipLaunchKernelGGL((k_sdc_tile<0, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, origin);
+	hipLaunchKernelGGL(k_sdc_scan<true>, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles, entry);
+	hipLaunchKernelGGL((k_sdc_tile<1, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, origin);
 }
 
 // ---------------------------------------------------------------- the trigger as a scan
@@ -168,16 +189,19 @@ __device__ __forceinline__ void tile_trigger(TrigShared &sh, const int (&cls)[SP
 
 // EMIT = false: the timing metric of the tile and its function (StreamFn) for both incoming states; EMIT = true: the same metric and
 // the tile's falling edges from its incoming StreamCarry.  GIVEN: the metric is a caller's sequence (ofdmrx_debug_stream_edges).
-template <int RATE, bool GIVEN, bool EMIT>
+// WIN (the live feed): block b is tile tile0 + b of the stream - the same absolute sample positions as in a one-call scan, so the same
+// metric values - fb.samples is the address position 0 would have, n the samples fed so far; fn / carry are indexed by b, and the
+// edge positions count from the push's first edge (the carry that enters a push has count 0)
+template <int RATE, bool GIVEN, bool EMIT, bool WIN = false>
 __global__ __launch_bounds__(256) void k_stream_tile(FrameBatch fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
-	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap)
+	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap, long long tile0 = 0)
 {
 	typedef RateCfg<RATE> RC;
 	constexpr int HS = RC::HS, GL = RC::GL, ML = RC::MATCH_LEN, MD = RC::MATCH_DEL;
 	constexpr int D = RC::BUFFER_LEN - 1 - (RC::SEARCH_POS + HS);   // P at time t: its newest pair is (t - D, t - D + HS)
 	constexpr int L = STREAM_TILE + ML - 1, PM = (L + 255) / 256;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const long long T0 = (long long)blockIdx.x * STREAM_TILE;
+	const long long T0 = ((long long)blockIdx.x + (WIN ? tile0 : 0)) * STREAM_TILE;
 	const float lo = (float)(0.17 * ML), hi = (float)(0.19 * ML);   // decode.cc:76
 	__shared__ TrigShared tsh;
 	float v[SPT];
@@ -356,7 +380,10 @@ __device__ __forceinline__ StreamCarry fn_apply(const StreamFn &f, StreamCarry c
 	return o;
 }
 
-__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts)
+// WIN: the scan starts from the carry the previous push left (*c_in, its edge count taken as 0) and leaves *c_out for the next
+template <bool WIN = false>
+__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts,
+	const StreamCarry *__restrict__ c_in = nullptr, StreamCarry *__restrict__ c_out = nullptr)
 {
 	const int tid = threadIdx.x;
 	__shared__ StreamFn sh[1024];
@@ -373,14 +400,21 @@ __global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restr
 		f = fn_then(f, fn[k]);
 	block_scan_incl<1024>(f, sh, tid, fn_then);
 	StreamCarry c{ 0, -INFINITY, -1, 0 };                     // the stream starts with the trigger off (decode.cc:68-74)
+	if constexpr (WIN) {
+		c = *c_in;
+		c.count = 0;
+	}
 	if (tid)
 		c = fn_apply(sh[tid - 1], c);
 	for (long k = k0; k < k1; ++k) {
 		carry[k] = c;
 		c = fn_apply(fn[k], c);
 	}
-	if (k0 < ntiles && k1 == ntiles)
+	if (k0 < ntiles && k1 == ntiles) {
 		counts[0] = c.count;
+		if constexpr (WIN)
+			*c_out = c;
+	}
 }
 
 void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
@@ -388,23 +422,33 @@ void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *giv
 {
 	const long ntiles = (n + STREAM_TILE - 1) / STREAM_TILE;
 	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
 	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
 	}
-	hipLaunchKernelGGL(k_stream_fn_scan, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts);
+	hipLaunchKernelGGL(k_stream_fn_scan<false>, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts, nullptr, nullptr);
 	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
 	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
 	}
+}
+
+void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, long long tile0, long ntiles, StreamFn *fn, StreamCarry *carry,
+	const StreamCarry *c_in, StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, nullptr, n, fn, carry, edges, cap, tile0));
+	hipLaunchKernelGGL(k_stream_fn_scan<true>, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts, c_in, c_out);
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, nullptr, n, fn, carry, edges, cap, tile0));
 }
 
 // ---------------------------------------------------------------- accept, records
 constexpr int ACCEPT_GRID = 2048;
-template <int RATE>
+// WIN (the live feed): fb.samples is the address position 0 would have and only the positions from win_lo on are in memory.  The host
+// has checked that no edge of this push reads below it (api_feed.cpp); an edge that would is left rejected and reported in counts[2]
+template <int RATE, bool WIN = false>
 __global__ __launch_bounds__(256) void k_stream_accept(FrameBatch fb, const cf *__restrict__ tw, const cf *__restrict__ kern,
-	StreamEdge *__restrict__ edges, long cap, const long long *__restrict__ counts)
+	StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts, long long win_lo = 0)
 {
 	typedef RateCfg<RATE> RC;
 	constexpr int BUFFER_LEN = RC::BUFFER_LEN, SEARCH_POS = RC::SEARCH_POS, HALF_LEN = RC::HS, MATCH_DEL = RC::MATCH_DEL, NT = 256;
@@ -419,6 +463,16 @@ __global__ __launch_bounds__(256) void k_stream_accept(FrameBatch fb, const cf *
 	for (long long e = blockIdx.x; e < ne; e += gridDim.x) {
 		__syncthreads();
 		StreamEdge ed = edges[e];
+		if constexpr (WIN) {
+			// the lowest positions direct_P and sc_accept_wg read for this edge
+			const long long lo_p = ed.t_max - MATCH_DEL - (BUFFER_LEN - 1 - (SEARCH_POS + HALF_LEN)) - (HALF_LEN - 1);
+			const long long lo_w = ed.g - (BUFFER_LEN - 1) + (SEARCH_POS - ed.index_max) + HALF_LEN;
+			if (win_lo > 0 && (lo_p < win_lo || lo_w < win_lo)) {     // (uniform)
+				if (tid == 0)
+					counts[2] = 1;
+				continue;
+			}
+		}
 		if (wave == 0) {                                          // decode.cc:91: arg(P) delayed by match_del (k_sync: direct_P)
 			float phase = 0.f;
 			const long long tp = ed.t_max - MATCH_DEL;
@@ -452,14 +506,19 @@ __global__ __launch_bounds__(256) void k_stream_accept(FrameBatch fb, const cf *
 	}
 }
 
-void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, const long long *counts)
+void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
 {
 	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL(k_stream_accept<RATE>, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, false>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, 0LL));
+}
+void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts, long long win_lo)
+{
+	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, true>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, win_lo));
 }
 
 __global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
-	SyncState *__restrict__ rec, long max_rec)
+	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base)
 {
 	const int tid = threadIdx.x;
 	__shared__ long long sh[1024];
@@ -481,12 +540,12 @@ __global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const S
 			st.found = 1;
 			st.symbol_pos = ed.symbol_pos;
 			st.cfo_rad = ed.cfo_rad;
-			st.rejects = (int)(e - k);                            // the edges before it that decode.cc:140-145 rejected
+			st.rejects = (int)(rej_base + (e - k));               // the edges before it that decode.cc:140-145 rejected (rej_base: in earlier pushes of a feed)
 			st.skip_left = 0;
 			st.status = 1;
 			st.oper_mode = 0;
 			st.call_sign = 0;
-			st.hdr_rounds = (int)k;
+			st.hdr_rounds = (int)(rec_base + k);
 			st.okay = 0;
 			st.pend_g = 0;
 			st.pend_index_max = 0;
@@ -500,11 +559,12 @@ __global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const S
 		counts[1] = base;
 }
 
-void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec)
+void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec,
+	long long rec_base, long long rej_base)
 {
 	int buffer_len = 0;
 	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
-	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec);
+	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec, rec_base, rej_base);
 }
 
 }  // namespace rx

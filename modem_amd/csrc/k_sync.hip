@@ -111,12 +111,13 @@ __global__ __launch_bounds__(256) void k_mono_carries(FrameBatch fb, FrontCoef c
 // starts on the kept state before it - four spans of 2048 samples cover a stretch and the filter's reach + the 63 samples back to
 // that state
 constexpr int FE_STRETCH = 4 * 2048 - 256;
-template <int RATE>
-__global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FrameBatch fb, MonoArgs ma, cf *__restrict__ z_all)
+// WIN (the live feed, one frame): block b is stretch stretch0 + b; fb.samples, ma.ck and z_all are the addresses position 0 would have
+template <int RATE, bool WIN = false>
+__global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FrameBatch fb, MonoArgs ma, cf *__restrict__ z_all, long stretch0 = 0)
 {
 	static_assert(MonoCfg<RATE>::REACH + MONO_CK <= 256, "a stretch and its lead-in fit four spans");
 	const int f = blockIdx.y, tid = threadIdx.x;
-	const long lo = (long)blockIdx.x * FE_STRETCH;
+	const long lo = ((long)blockIdx.x + (WIN ? stretch0 : 0)) * FE_STRETCH;
 	__shared__ typename MonoCover<RATE, 256>::Shared msh;
 	MonoCover<RATE, 256> mc;
 	mc.init(mono_frame(fb, ma.ck, ma.ck_per_frame, f), ma, &msh, z_all + (size_t)f * fb.samples_per_frame, tid);
@@ -581,8 +582,13 @@ void launch_front_end(hipStream_t s, int rate, int n, FrameBatch fb, MonoArgs ma
 		fbq.samples = (const char *)fb.samples + (size_t)f0 * fb.frame_stride_bytes;
 		MonoArgs maq = ma;
 		maq.ck = ma.ck + (size_t)f0 * ma.ck_per_frame;
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL(k_front_end<RATE>, dim3(stretches, nf), dim3(256), 0, s, fbq, maq, z + (size_t)f0 * fb.samples_per_frame));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, false>), dim3(stretches, nf), dim3(256), 0, s, fbq, maq, z + (size_t)f0 * fb.samples_per_frame, 0L));
 	}
+}
+long front_end_stretch() { return FE_STRETCH; }
+void launch_front_end_window(hipStream_t s, int rate, FrameBatch fb, MonoArgs ma, cf *z, long stretch0, long n_stretch)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, true>), dim3((unsigned)n_stretch, 1), dim3(256), 0, s, fb, ma, z, stretch0));
 }
 #define SYNC_SPLIT_ROUNDS 2   // rates above 8 kHz: scan + accept pairs before the one-wave catch-all (a frame needs the catch-all only
                               // after that many rejected triggers; finished frames leave every later launch at once)

@@ -248,7 +248,22 @@ void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *giv
 	StreamEdge *edges, long cap, long long *counts);
 // decode.cc:110-151 for every edge (of the min(counts[0], cap) written), then the records: counts[1] = accepted edges, rec[k] = the
 // SyncState that k_header finds for the (k+1)-th accepted edge after a round with skip_left = 0 (k < max_rec)
-void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, const long long *counts);
-void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec);
+// rec_base / rej_base: records / rejected edges before the first edge (a feed's earlier pushes)
+void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
+void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec,
+	long long rec_base = 0, long long rej_base = 0);
+// ---- the live feed (api_feed.cpp): the same kernels over a WINDOW of the stream.  fb.samples (and ck, z) are the
+// addresses position 0 would have - the window's buffer minus its base - and fb.samples_per_frame the samples fed so far; the host
+// checks before every launch that the window holds every position the launch reads below that.
+// the DC blocker's states of the complete blocks of [origin, fb.samples_per_frame), origin a multiple of 64, from the state kept before origin
+void launch_stream_dc_window(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, long origin);
+// the analytic signal of the stretches stretch0 .. stretch0 + n_stretch - 1 (k_sync.hip: FE_STRETCH samples each, from position 0)
+long front_end_stretch();
+void launch_front_end_window(hipStream_t s, int rate, FrameBatch fb, MonoArgs ma, cf *z, long stretch0, long n_stretch);
+// tiles tile0 .. tile0 + ntiles - 1 from the carry *c_in (count taken as 0); *c_out: the carry behind them; counts[0]: their edges
+void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, long long tile0, long ntiles, StreamFn *fn, StreamCarry *carry,
+	const StreamCarry *c_in, StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts);
+// counts[2] is set when an edge would read below win_lo (it is then left rejected: an internal error)
+void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts, long long win_lo);
 
 }  // namespace rx

@@ -25,6 +25,7 @@ EXPORTS = [
     "ofdmrx_util_awgn_tile", "ofdmrx_util_channel", "ofdmrx_frame_samples", "ofdmrx_tx_frame_samples",
     "ofdmrx_tx_encode_device", "ofdmrx_stream_samples", "ofdmrx_tx_encode_stream_device", "ofdmrx_tx_encode_stream",
     "ofdmrx_callsign_value", "ofdmrx_decode_stream", "ofdmrx_decode_stream_device", "ofdmrx_debug_stream_edges",
+    "ofdmrx_feed_begin", "ofdmrx_feed_push", "ofdmrx_feed_end", "ofdmrx_feed_lag", "ofdmrx_feed_resident_samples",
 ]
 
 
@@ -113,6 +114,14 @@ def load_library():
     L.ofdmrx_decode_stream_device.argtypes = stream
     L.ofdmrx_debug_stream_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_size_t)]
+    L.ofdmrx_feed_begin.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.ofdmrx_feed_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
+                                   C.POINTER(C.c_size_t)]
+    L.ofdmrx_feed_end.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ofdmrx_feed_lag.argtypes = [C.c_void_p]
+    L.ofdmrx_feed_lag.restype = C.c_longlong
+    L.ofdmrx_feed_resident_samples.argtypes = [C.c_void_p]
+    L.ofdmrx_feed_resident_samples.restype = C.c_longlong
     L.ofdmrx_synchronize.argtypes = [C.c_void_p]
     L.ofdmrx_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.ofdmrx_chunk_frames.argtypes = [C.c_void_p]
@@ -263,6 +272,10 @@ class Receiver:
         k = min(npre.value, cap)
         return (out[:k], res[:k], npre.value) + ((rows[:k],) if esn0_rows else ())
 
+    def feed(self, channels, dtype=np.int16, esn0_rows=False):
+        """open a live feed of `channels` interleaved values of dtype: push blocks as they arrive, take each record when it is due"""
+        return Feed(self, channels, dtype, esn0_rows)
+
     def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
         """device pointers (ints), or pinned host outputs; -> n_preambles (the call synchronises once, after the scan)"""
         npre = C.c_size_t(0)
@@ -409,3 +422,75 @@ class Receiver:
     def tx_encode(self, d_payload, n, d_pcm, mode=6, freq_off=2000, call_sign="ANONYMOUS", channels=2):
         """device transmitter: n x 5380 payload bytes -> n x tx_frame_samples(mode) x channels int16 (device pointers)"""
         self._check(self._lib.ofdmrx_tx_encode_device(self._h, d_payload, n, mode, freq_off, call_sign.encode(), channels, d_pcm))
+
+
+class Feed:
+    """A recording decoded block by block (ofdmrx_feed_*): push(pcm) returns the records that have become due, end() the rest.
+    The records of all calls, concatenated, are what Receiver.decode_stream returns for the concatenated samples.  One feed per
+    Receiver at a time; a context manager ends (and discards what is left of) a feed that was not ended."""
+
+    def __init__(self, rx, channels, dtype=np.int16, esn0_rows=False):
+        self._rx, self._lib, self._h = rx, rx._lib, rx._h
+        self.channels, self.dtype, self._rows = int(channels), np.dtype(dtype), bool(esn0_rows)
+        rx._check(self._lib.ofdmrx_feed_begin(self._h, rx._fmt(self.dtype), self.channels))
+        self.open = True
+        self.n_left = 0
+
+    @property
+    def lag(self):
+        return int(self._lib.ofdmrx_feed_lag(self._h))
+
+    @property
+    def resident_samples(self):
+        return int(self._lib.ofdmrx_feed_resident_samples(self._h))
+
+    def _call(self, f, max_frames, ending=False):
+        """f(cap, payload, results, n_records, n_left) until nothing is left (max_frames None) or once"""
+        pays, ress, rows = [], [], []
+        cap = 16 if max_frames is None else int(max_frames)
+        first = True
+        while first or (max_frames is None and self.n_left > 0 and self.open):
+            out = np.zeros((max(cap, 1), PAYLOAD_BYTES), np.uint8)
+            res = np.zeros(max(cap, 1), RESULT_DTYPE)
+            rw = np.zeros((max(cap, 1), 126), np.float32) if self._rows else None
+            nrec, nleft = C.c_size_t(0), C.c_size_t(0)
+            if self._rows:
+                self._rx._check(self._lib.ofdmrx_set_esn0_rows(self._h, _ptr(rw)))
+            try:
+                self._rx._check(f(first, cap, _ptr(out) if cap else None, _ptr(res) if cap else None, C.byref(nrec), C.byref(nleft)))
+            finally:
+                if self._rows:
+                    self._lib.ofdmrx_set_esn0_rows(self._h, None)
+            first = False
+            self.n_left = nleft.value
+            pays.append(out[:nrec.value])
+            ress.append(res[:nrec.value])
+            if self._rows:
+                rows.append(rw[:nrec.value])
+            if ending and nleft.value == 0:
+                self.open = False
+        ret = (np.concatenate(pays), np.concatenate(ress))
+        return ret + ((np.concatenate(rows),) if self._rows else ())
+
+    def push(self, pcm, max_frames=None):
+        """more samples [k, channels] (or [k] mono; k may be 0) -> (payloads, results[, esn0 rows]) of the records now due;
+        max_frames None: everything that is ready (else the rest stays staged: n_left)"""
+        pcm = np.ascontiguousarray(pcm, dtype=self.dtype).reshape(-1, self.channels)
+        n = pcm.shape[0]
+        return self._call(lambda first, cap, o, r, a, b: self._lib.ofdmrx_feed_push(self._h, _ptr(pcm) if n and first else None,
+                                                                                   n if first else 0, cap, o, r, a, b), max_frames)
+
+    def _end(self, first, cap, o, r, a, b):
+        return self._lib.ofdmrx_feed_end(self._h, cap, o, r, a, b)
+
+    def end(self, max_frames=None):
+        """the stream is over -> the remaining records; the feed is closed once nothing is left"""
+        return self._call(self._end, max_frames, ending=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        while self.open:
+            self.end()
+        return False

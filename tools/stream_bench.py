@@ -6,6 +6,10 @@ Input (made on the device): --streams streams of --count mode-6 payloads each, 8
 (host clock around a synchronise), warm-up first.  Compared in the same process: the batch entry on the same payloads as single-payload
 frames (ofdmrx_tx_encode_device, what bench.py runs), and today's route to the payloads of one --skip-count-payload stream (that many
 copies of it with skip counts 0 .. n-1).  Every payload is checked.  Prints one JSON line (and writes it to --out).
+
+--feed BLOCK: instead, ONE such recording from host memory through the live feed (ofdmrx_feed_*) in pushes of BLOCK samples, beside the
+host-pointer one-call entry (ofdmrx_decode_stream) on the same samples: samples/s and records/s of both and their ratio.  Every push
+synchronises with the host, so the feed is the slower per sample; records and payloads are checked to be the same.
 """
 import argparse
 import ctypes as C
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--noise-db", type=float, default=-30.0)
     ap.add_argument("--skip-count", type=int, default=64)
     ap.add_argument("--out", default="")
+    ap.add_argument("--feed", type=int, default=0, metavar="BLOCK", help="the same recording through the live feed in pushes of BLOCK samples")
     a = ap.parse_args()
     import torch
     import modem_amd
@@ -51,6 +56,8 @@ def main():
         rx.awgn_tile(clean.data_ptr(), 1, pcm[s].data_ptr(), 1, n, a.noise_db, 11 + s, 0)
     rx.synchronize()
     del clean
+    if a.feed:
+        return feed_bench(a, rx, pcm[0].cpu().numpy(), pay[0].cpu().numpy())
     out = torch.zeros((S, K, 5380), dtype=torch.uint8, device=dev)
     res = torch.zeros((S, K, M.RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
 
@@ -123,6 +130,47 @@ def main():
         "skip_route_payloads": J, "skip_route_ms": sdt * 1e3, "skip_route_frames_per_s": J / sdt, "skip_route_payloads_ok": sok, "skip_route_status_counts": sstat,
         "stream_route_same_payloads_ms": s1dt * 1e3, "stream_route_preambles": npre, "stream_route_payloads_ok": s1ok,
         "input_bytes_per_step": S * n * 4,
+    }
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    rx.close()
+
+
+def feed_bench(a, rx, pcm, pay):
+    """one recording (host memory): the one-call host entry against the feed in pushes of a.feed samples"""
+    n, K, B = len(pcm), len(pay), a.feed
+
+    def one_call():
+        return rx.decode_stream(pcm, max_frames=K)[:2]
+
+    def fed():
+        got = []
+        with rx.feed(2) as f:
+            for p in range(0, n, B):
+                got.append(f.push(pcm[p:p + B]))
+            got.append(f.end())
+        return np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got])
+
+    times = {}
+    outs = {}
+    for name, fn in (("one_call", one_call), ("feed", fed)):
+        for _ in range(a.warmup):
+            fn()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            outs[name] = fn()
+        times[name] = (time.perf_counter() - t0) / a.steps
+    same = outs["feed"][0].tobytes() == outs["one_call"][0].tobytes() and outs["feed"][1].tobytes() == outs["one_call"][1].tobytes()
+    rec = {
+        "metric": "live feed against the one-call host entry, mode-6 8 kHz 2-channel int16, AWGN %g dB" % a.noise_db,
+        "payloads": K, "samples": n, "block": B, "pushes": (n + B - 1) // B, "steps": a.steps,
+        "one_call_ms": times["one_call"] * 1e3, "one_call_samples_per_s": n / times["one_call"], "one_call_records_per_s": K / times["one_call"],
+        "feed_ms": times["feed"] * 1e3, "feed_samples_per_s": n / times["feed"], "feed_records_per_s": len(outs["feed"][1]) / times["feed"],
+        "feed_vs_one_call": times["one_call"] / times["feed"], "feed_ms_per_push": times["feed"] * 1e3 / ((n + B - 1) // B),
+        "records": len(outs["feed"][1]), "payloads_ok": int((outs["feed"][0] == pay).all(axis=1).sum()), "same_bytes_as_one_call": bool(same),
     }
     line = json.dumps(rec)
     print(line)
