@@ -50,7 +50,8 @@ extern "C" {
  *      residencies of its decoders and leaves the rest to the next chunk's run (same outputs)
  *   7: ofdmrx_decode_stream, ofdmrx_decode_stream_device (every preamble of one recording in one call), ofdmrx_debug_stream_edges;
  *      added within 1.7 (the minor number stays: a caller detects them by symbol): the live feed - ofdmrx_feed_begin, ofdmrx_feed_push,
- *      ofdmrx_feed_end, ofdmrx_feed_lag, ofdmrx_feed_resident_samples */
+ *      ofdmrx_feed_end, ofdmrx_feed_lag, ofdmrx_feed_resident_samples; many recordings in one call - ofdmrx_decode_streams,
+ *      ofdmrx_decode_streams_device, ofdmrx_debug_streams_edges */
 #define OFDMRX_ABI_MINOR 7
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -231,6 +232,45 @@ int ofdmrx_decode_stream_device(ofdmrx_handle *h, const void *d_samples, int sam
  * sequence of n values, with the thresholds and match_len of the handle's rate: the falling edges (t_edge), the first index of the
  * maximum of each run (t_max) and index_max; at most max_edges of them are written, *n_edges counts all.  HOST pointers. */
 int ofdmrx_debug_stream_edges(ofdmrx_handle *h, const float *timing, size_t n, size_t max_edges,
+	int64_t *t_edge, int64_t *t_max, int32_t *index_max, size_t *n_edges);
+
+/*
+ * Many recordings in one call (added within revision 1.7): n_streams recordings - a directory of WAV files, a bank of receiver
+ * channels, a sweep over multi-frame streams; what ofdmrx_tx_encode_stream_device writes - scanned together and their records
+ * decoded in shared chunks.  Recording s is n_samples[s] sample frames at samples + s * stream_stride_bytes; the lengths may
+ * differ, a length of 0 is allowed (no records), and the bytes between the end of a recording and the next stride are never read.
+ * The records of recording s are, byte for byte - payload and every byte of every ofdmrx_frame_result - what ofdmrx_decode_stream
+ * returns for that recording alone, for 2-channel and for mono input, every format and rate, however the recordings are batched:
+ * sc_start is an index into recording s, n_sync_rejects counts from its start, n_preambles[s] is its own count.  Mono input keeps
+ * that because every recording runs the arithmetic of the one-call entry with its own tile count: the DC blocker's scan over tiles
+ * of 4096 samples composes per recording, in the order a call with that recording alone composes it, and the analytic signal is
+ * formed in stretches on multiples of 7936 samples from that recording's position 0.
+ * Packing: records in recording order, then preamble order; recording s contributes min(n_preambles[s], max_frames_per_stream)
+ * records, first_record[s] (n_streams + 1 entries) is its first index in that order and first_record[n_streams] the total.  Only
+ * the first max_records of the packed order are written and nothing past them is touched; first_record describes the uncapped
+ * packing, so a caller sees what was cut.  payload_out / results may be NULL only when max_records is 0 (a count-only call).
+ * Es/N0 rows (ofdmrx_set_esn0_rows): row block i belongs to packed record i.  The attempt log is not written, OFDMRX_FLAG_TWO_LANES
+ * is ignored, the other flags hold; ofdmrx_get_timing, the stage taps, ofdmrx_list_decoded_frames and ofdmrx_sc_decided_frames
+ * describe the call as for a stream call.
+ * OFDMRX_E_ARG, before any device call: a NULL handle, samples, n_samples, n_preambles or first_record; n_streams outside 1 .. 65535;
+ * a length above 0x7fffffff / 2; a stride that is not a multiple of the sample-frame size or is smaller than the longest recording;
+ * a bad format or channel count; NULL outputs with max_records > 0; an open feed.
+ * HOST pointers; blocks until done.
+ */
+int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int sample_format, int channels,
+	size_t n_streams, size_t stream_stride_bytes, const size_t *n_samples, size_t max_frames_per_stream, size_t max_records,
+	uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_preambles, size_t *first_record);
+/* the same with samples, payload_out and results in DEVICE memory (both outputs may instead be pinned host memory, as for
+ * ofdmrx_decode_batch_device); n_samples, n_preambles and first_record are HOST arrays.  One host synchronisation: the read-back of
+ * all recordings' edge and preamble counts after the scan (not one per recording).  If a recording has more falling edges than its
+ * share of the edge buffer, the buffer grows and the scan runs once more, as in ofdmrx_decode_stream_device. */
+int ofdmrx_decode_streams_device(ofdmrx_handle *h, const void *d_samples, int sample_format, int channels,
+	size_t n_streams, size_t stream_stride_bytes, const size_t *n_samples, size_t max_frames_per_stream, size_t max_records,
+	uint8_t *d_payload_out, ofdmrx_frame_result *d_results, size_t *n_preambles, size_t *first_record);
+/* test entry: ofdmrx_debug_stream_edges for n_streams timing sequences at once (sequence s: n[s] values, packed back to back in
+ * `timing`) through the segmented trigger scan: nothing of a sequence's trigger state enters the next.  t_edge, t_max, index_max:
+ * [n_streams][max_edges_per_stream], the first max_edges_per_stream edges of every sequence; n_edges[s] counts all.  HOST pointers. */
+int ofdmrx_debug_streams_edges(ofdmrx_handle *h, const float *timing, size_t n_streams, const size_t *n, size_t max_edges_per_stream,
 	int64_t *t_edge, int64_t *t_max, int32_t *index_max, size_t *n_edges);
 
 /*

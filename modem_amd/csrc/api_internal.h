@@ -220,6 +220,11 @@ struct ofdmrx_handle {
 	// stream decode (api_stream.cpp): scratch kept between calls, grown on demand
 	DevBuf sx_in, sx_z, sx_ck, sx_dc_end, sx_dc_in, sx_fn, sx_carry, sx_edges, sx_counts, sx_rec, sx_pay, sx_res, sx_esn0, sx_timing;
 	long sx_edge_cap = 0;     // edges the edge buffer holds
+	// many recordings in one call (api_streams.cpp): the per-recording lengths and tile places, the packed order, the record -> recording map
+	DevBuf sxs_len, sxs_tile0, sxs_given0, sxs_first, sxs_rec_src;
+	std::vector<int> sxs_len_h;           // (host copies the uploads read: they live as long as the handle)
+	std::vector<long long> sxs_tile0_h, sxs_given0_h, sxs_counts_h;
+	long sxs_edge_cap = 0;    // every recording's share of the edge buffer
 	struct ofdmrx_feed *feed = nullptr;   // the open live feed (api_feed.cpp), one per handle
 };
 
@@ -253,5 +258,8 @@ inline void begin_call(ofdmrx_handle *h)
 int finish_call(ofdmrx_handle *h, int r);                                                   // api_pipeline.cpp: a call ends: r, or the sticky event error
 // the chunk pipeline for n records of a stream decode: every frame is the whole stream fb (stride 0), record k starts from
 // d_records[k] (header, demod, ...); device or pinned host outputs like ofdmrx_decode_batch_device; keeps the call's events so far
-int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out);
+// srcs (nullable): the records of several recordings in one chunk plan - record k reads recording src_of[k], src_len[..] sample
+// frames at fb.samples + src_of[k] * stride_bytes (device arrays; fb has stride 0, fb.samples_per_frame the longest recording)
+struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; };
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources *srcs = nullptr);
 void feed_free(ofdmrx_handle *h);                                                           // api_feed.cpp: the open feed and its window go

@@ -5,12 +5,17 @@
 // Without --live the whole recording is read and decoded in one call (ofdmrx_decode_stream).  With --live the WAV header is read,
 // then the body in blocks of one second as it arrives (INPUT `-`: standard input, e.g. a recorder's pipe), every block is pushed into
 // a feed (ofdmrx_feed_*) and every record is written as soon as it is returned: the same files and lines, each when its frame is in.
+// `decode_stream --batch OUTROOT A.wav B.wav ...`: many recordings in one call (ofdmrx_decode_streams).  Recording i goes to
+// OUTROOT/<i>/<k>.dat (the directories are made) and its summary lines are the one-call lines prefixed with `<i>:`.  The inputs must
+// share sample rate, channel count and sample format.
 #include "wav_read.h"
+#include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <sys/stat.h>
 
 // one record: its line on stderr, its file
-static bool emit_record(const std::string &outdir, size_t k, const ofdmrx_frame_result &q, const uint8_t *payload)
+static bool emit_record(const std::string &outdir, size_t k, const ofdmrx_frame_result &q, const uint8_t *payload, const char *prefix = "")
 {
 	static const char *names[] = { "ok", "no sync", "OSD error", "header CRC error", "mode unsupported", "call sign unsupported",
 		"payload decoding error" };
@@ -19,7 +24,7 @@ static bool emit_record(const std::string &outdir, size_t k, const ofdmrx_frame_
 	for (int i = 8; i >= 0; --i, v /= 37)                         // base37_decoder, decode.cc:155-159
 		cs[i] = " 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"[v % 37];
 	cs[9] = 0;
-	std::fprintf(stderr, "%zu: sample %lld mode %d call sign %s %s bit flips %d\n", k, (long long)q.sc_start, q.oper_mode, cs,
+	std::fprintf(stderr, "%s%zu: sample %lld mode %d call sign %s %s bit flips %d\n", prefix, k, (long long)q.sc_start, q.oper_mode, cs,
 		q.status >= 0 && q.status <= 6 ? names[q.status] : "?", q.bit_flips);
 	const std::string name = outdir + "/" + std::to_string(k) + ".dat";
 	FILE *f = std::fopen(name.c_str(), "wb");
@@ -121,11 +126,74 @@ static int run_live(const std::string &outdir, const char *input_name)
 	return (r || !written) ? 1 : 0;
 }
 
+// every recording of a list in one call
+static int run_batch(const std::string &outroot, int n_inputs, char **inputs)
+{
+	std::vector<Wav> wavs((size_t)n_inputs);
+	size_t longest = 0;
+	for (int i = 0; i < n_inputs; ++i) {
+		if (!read_wav(inputs[i], wavs[i])) {                      // (a WAV without sample frames is a recording of length 0: no records)
+			std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", inputs[i]);
+			return 1;
+		}
+		if (wavs[i].rate != wavs[0].rate || wavs[i].channels != wavs[0].channels || wavs[i].fmt != wavs[0].fmt) {
+			std::fprintf(stderr, "\"%s\" and \"%s\" do not share sample rate, channels and sample format: a batch takes recordings of one kind.\n",
+				inputs[0], inputs[i]);
+			return 1;
+		}
+		longest = std::max(longest, wavs[i].frames);
+	}
+	const Wav &w0 = wavs[0];
+	if (!supported(w0.channels, w0.rate))
+		return 1;
+	const size_t S = (size_t)n_inputs, frame_bytes = (w0.fmt == OFDMRX_FMT_S16 ? 2 : w0.fmt == OFDMRX_FMT_U8 ? 1 : 4) * (size_t)w0.channels;
+	const size_t stride = std::max<size_t>(longest, 1) * frame_bytes;
+	std::vector<uint8_t> all(S * stride);
+	std::vector<size_t> lens(S), n_pre(S), first(S + 1);
+	for (size_t i = 0; i < S; ++i) {
+		lens[i] = wavs[i].frames;
+		std::memcpy(all.data() + i * stride, wavs[i].pcm.data(), lens[i] * frame_bytes);
+		wavs[i].pcm = std::vector<uint8_t>();
+	}
+	ofdmrx_handle *h = create(w0.rate);
+	if (!h)
+		return 1;
+	size_t cap = 64 * S;
+	std::vector<uint8_t> out;
+	std::vector<ofdmrx_frame_result> res;
+	for (;;) {                                                    // a second call only when the recordings hold more than the first guess
+		out.assign(cap * OFDMRX_PAYLOAD_BYTES, 0);
+		res.assign(cap, ofdmrx_frame_result{});
+		const int r = ofdmrx_decode_streams(h, all.data(), w0.fmt, w0.channels, S, stride, lens.data(), (size_t)-1, cap, out.data(), res.data(),
+			n_pre.data(), first.data());
+		if (r) {
+			std::fprintf(stderr, "ofdmrx_decode_streams: %s\n", ofdmrx_strerror(r));
+			ofdmrx_destroy(h);
+			return 1;
+		}
+		if (first[S] <= cap)
+			break;
+		cap = first[S];
+	}
+	ofdmrx_destroy(h);
+	(void)mkdir(outroot.c_str(), 0777);
+	for (size_t i = 0; i < S; ++i) {
+		const std::string dir = outroot + "/" + std::to_string(i), prefix = std::to_string(i) + ":";
+		(void)mkdir(dir.c_str(), 0777);
+		for (size_t k = first[i]; k < first[i + 1]; ++k)
+			if (!emit_record(dir, k - first[i], res[k], out.data() + k * OFDMRX_PAYLOAD_BYTES, prefix.c_str()))
+				return 1;
+	}
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc >= 4 && !std::strcmp(argv[1], "--batch"))
+		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s --batch OUTROOT INPUT...\n", argv[0], argv[0]);
 		return 1;
 	}
 	const std::string outdir = argv[live ? 2 : 1];

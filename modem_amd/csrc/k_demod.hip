@@ -59,8 +59,9 @@ template <int RATE> struct DifCfg {
                               // Measured per 8192 frames: 7 (72 VGPRs, five workgroups, spills) 2.46 - 2.67 ms, 6 (80) 2.04 - 2.10, 5 (96) 2.02, 4 (128, three
                               // workgroups) 3.05
 #endif
-template <int RATE, int MONO>
-__global__ __launch_bounds__(DifCfg<RATE>::NT, MONO == 2 ? DEMOD_MONO_WAVES : DifCfg<RATE>::WAVES) void k_demod(FrameBatch fb, cf *__restrict__ z_all, MonoArgs ma, Tables tb,
+// FB = SourceBatch: frame f is a record of source batch_source(fb, f) (many recordings in one call, kernels.h)
+template <int RATE, int MONO, class FB = FrameBatch>
+__global__ __launch_bounds__(DifCfg<RATE>::NT, MONO == 2 ? DEMOD_MONO_WAVES : DifCfg<RATE>::WAVES) void k_demod(FB fb, cf *__restrict__ z_all, MonoArgs ma, Tables tb,
 	const SyncState *__restrict__ st_all, cf *__restrict__ cons_all, cf *__restrict__ carr_all)
 {
 	constexpr int SYMBOL_LEN = RateCfg<RATE>::SL, SYM_STRIDE = RateCfg<RATE>::STRIDE, GUARD_LEN = RateCfg<RATE>::GL;
@@ -68,7 +69,8 @@ __global__ __launch_bounds__(DifCfg<RATE>::NT, MONO == 2 ? DEMOD_MONO_WAVES : Di
 	const SyncState st = st_all[f];
 	if (!st.okay)
 		return;
-	SampleSrc src{ (const char *)fb.samples + (size_t)f * fb.frame_stride_bytes, fb.fmt, fb.channels, fb.samples_per_frame,
+	const int fs = batch_source(fb, f);
+	SampleSrc src{ (const char *)fb.samples + (size_t)fs * fb.frame_stride_bytes, fb.fmt, fb.channels, batch_len(fb, fs),
 		fb.channels == 1 ? z_all + (size_t)f * fb.samples_per_frame : nullptr };
 	const ModeDesc md = mode_desc(st.oper_mode);
 	cf *cons = cons_all + (size_t)f * CONS_MAX;
@@ -436,6 +438,10 @@ __global__ __launch_bounds__(256) void k_fft_debug(int len, int sign, const cf *
 }
 
 bool demod_forms_cons(int rate) { return DEMOD_CONS_OUT(rate); }
+void launch_demod_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, const SyncState *st, cf *cons, cf *carr)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_demod<RATE, 0, SourceBatch>), dim3(n), dim3(DifCfg<RATE>::NT), 0, s, fb, nullptr, MonoArgs{}, tb, st, cons, carr));
+}
 void launch_demod(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const MonoArgs &ma, Tables tb, const SyncState *st, cf *cons, cf *carr)
 {
 	if (fb.channels == 1 && mono_fused(rate)) {

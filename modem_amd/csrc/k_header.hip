@@ -442,8 +442,9 @@ __device__ __forceinline__ unsigned crc16_u64(unsigned long long data)
                            // barrier-separated steps, latency-bound: 1.48 ms per 8192 frames at 2, 0.88 at 4, 0.79 at 5; the uncertified order-3
                            // search (OSD_NO_CERTIFICATE: 30 ms) does not care
 #endif
-template <int RATE, bool MONO>
-__global__ __launch_bounds__(256, HDR_WAVES) void k_header(FrameBatch fb, cf *__restrict__ z_all, MonoArgs ma, Tables tb,
+// FB = SourceBatch: frame f is a record of source batch_source(fb, f) (many recordings in one call, kernels.h)
+template <int RATE, bool MONO, class FB = FrameBatch>
+__global__ __launch_bounds__(256, HDR_WAVES) void k_header(FB fb, cf *__restrict__ z_all, MonoArgs ma, Tables tb,
 	SyncState *__restrict__ st_all, int8_t *__restrict__ hdr_soft, Attempt *__restrict__ attempts, int32_t *__restrict__ attempt_counts)
 {
 	constexpr int SYMBOL_LEN = RateCfg<RATE>::SL, SYM_STRIDE = RateCfg<RATE>::STRIDE;
@@ -463,7 +464,8 @@ __global__ __launch_bounds__(256, HDR_WAVES) void k_header(FrameBatch fb, cf *__
 		}
 		return;
 	}
-	SampleSrc src{ (const char *)fb.samples + (size_t)f * fb.frame_stride_bytes, fb.fmt, fb.channels, fb.samples_per_frame,
+	const int fs = batch_source(fb, f);
+	SampleSrc src{ (const char *)fb.samples + (size_t)fs * fb.frame_stride_bytes, fb.fmt, fb.channels, batch_len(fb, fs),
 		fb.channels == 1 ? z_all + (size_t)f * fb.samples_per_frame : nullptr };
 	const long body = st.sc_start + SYM_STRIDE;               // decode.cc:405
 	if constexpr (MONO) {                                     // the symbol's analytic signal first (mono_front.h; its LDS is buf's)
@@ -560,6 +562,10 @@ void launch_header(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const M
 	} else {
 		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_header<RATE, false>), dim3(n), dim3(256), 0, s, fb, z, ma, tb, st, hdr_soft, att, attempt_counts));
 	}
+}
+void launch_header_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, SyncState *st, int8_t *hdr_soft)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_header<RATE, false, SourceBatch>), dim3(n), dim3(256), 0, s, fb, nullptr, MonoArgs{}, tb, st, hdr_soft, nullptr, nullptr));
 }
 void launch_osd_only(hipStream_t s, int n, Tables tb, const int8_t *soft, uint8_t *hard, int32_t *unique)
 {

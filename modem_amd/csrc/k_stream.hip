@@ -11,12 +11,18 @@
 // The live feed (api_feed.cpp) runs the same kernels push by push over a window of the stream: the WIN forms take
 // where the push's first tile / block lies in the stream and the state the last push left, and compute from the same absolute
 // positions as the one-call forms (whose instantiations are unchanged).
+// Many recordings in one call (api_streams.cpp): the FB = SourceBatch forms take the recording from blockIdx.y - its
+// own base, length and places in the per-tile and edge arrays - and run what the one-call forms run on it; the scans over tiles
+// are one workgroup per recording, so nothing is carried from one recording into the next.
+#include <type_traits>
 #include "dev_common.h"
 #include "kernels.h"
 #include "mono_front.h"
 #include "sync_accept.h"
 
 namespace rx {
+
+template <class FB> constexpr bool many_v = std::is_same<FB, SourceBatch>::value;
 
 // inclusive Hillis-Steele scan over NT threads in LDS (sh: NT entries); returns this thread's inclusive value, sh holds them all
 // afterwards (the caller synchronises before reusing sh)
@@ -45,13 +51,25 @@ __device__ __forceinline__ Affine aff_then(Affine l, Affine r) { return Affine{ 
 // WIN (the live feed): tile 0 starts at the absolute position `origin` (a multiple of MONO_CK), fb.samples and ck are
 // the addresses position 0 / state 0 would have, fb.samples_per_frame the samples fed so far; only the states of complete blocks
 // of MONO_CK samples are kept (ck_n is unused)
-template <int PASS, bool WIN = false>
-__global__ __launch_bounds__(256) void k_sdc_tile(FrameBatch fb, FrontCoef co, double *__restrict__ tile_end, const double *__restrict__ tile_in,
+// FB = SourceBatch: tile blockIdx.x of recording blockIdx.y; ck_n is then the states kept per recording (the row length of ck)
+template <int PASS, bool WIN = false, class FB = FrameBatch>
+__global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *__restrict__ tile_end, const double *__restrict__ tile_in,
 	double *__restrict__ ck, int ck_n, long origin = 0)
 {
 	const int tid = threadIdx.x;
 	const long t = blockIdx.x;
 	MonoFrame fr{ (const char *)fb.samples, fb.fmt, fb.samples_per_frame, nullptr };
+	if constexpr (many_v<FB>) {
+		const int q = blockIdx.y;
+		fr.base += (size_t)q * fb.frame_stride_bytes;
+		fr.n = fb.src_len[q];
+		if (t * 4096 >= fr.n)                                     // (uniform: a tile past this recording's end)
+			return;
+		tile_end += fb.tile0[q];
+		tile_in += fb.tile0[q];
+		ck += (size_t)q * ck_n;
+		ck_n = (int)((fr.n + MONO_CK - 1) / MONO_CK);               // (mono_ck_per_frame)
+	}
 	__shared__ Affine sh[256];
 	const double a = (double)co.dc_a, g = (double)co.dc_b * (1.0 - a) * (double)fr.scale();
 	const long s0 = (WIN ? origin : 0) + t * 4096 + (long)tid * 16;
@@ -100,6 +118,29 @@ __global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *_
 		c = tile_end[k] + A * c;
 	}
 }
+// Many recordings: one workgroup per recording runs k_sdc_scan<false> on that recording's tiles - the same ranges per thread, the
+// same order of composition as a call with that recording alone, so the same doubles.  (A kernel of its own rather than a shared
+// body: k_sdc_scan's code stays what it was.)
+__global__ __launch_bounds__(1024) void k_sdcs_scan(FrontCoef co, const double *__restrict__ tile_end_all, double *__restrict__ tile_in_all,
+	const long long *__restrict__ tile0)
+{
+	const int tid = threadIdx.x;
+	__shared__ Affine sh[1024];
+	const double *__restrict__ tile_end = tile_end_all + tile0[blockIdx.x];
+	double *__restrict__ tile_in = tile_in_all + tile0[blockIdx.x];
+	const long ntiles = (long)(tile0[blockIdx.x + 1] - tile0[blockIdx.x]);
+	const double A = mono_pow((double)co.dc_a, 4096);
+	const long per = (ntiles + 1023) / 1024, k0 = (long)tid * per, k1 = k0 + per < ntiles ? k0 + per : ntiles;
+	Affine f{ 0.0, 1.0 };
+	for (long k = k0; k < k1; ++k)
+		f = aff_then(f, Affine{ tile_end[k], A });
+	block_scan_incl<1024>(f, sh, tid, aff_then);
+	double c = tid ? sh[tid - 1].v : 0.0;
+	for (long k = k0; k < k1; ++k) {
+		tile_in[k] = c;
+		c = tile_end[k] + A * c;
+	}
+}
 
 void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck)
 {
@@ -108,6 +149,13 @@ void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_e
 	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n, 0L);
 	hipLaunchKernelGGL(k_sdc_scan<false>, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles, nullptr);
 	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n, 0L);
+}
+void launch_streams_dc(hipStream_t s, int n_src, long max_len, SourceBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, int ck_per_src)
+{
+	const dim3 grid((unsigned)((max_len + 4095) / 4096), (unsigned)n_src);
+	hipLaunchKernelGGL((k_sdc_tile<0, false, SourceBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_per_src, 0L);
+	hipLaunchKernelGGL(k_sdcs_scan, dim3((unsigned)n_src), dim3(1024), 0, s, co, tile_end, tile_in, fb.tile0);
+	hipLaunchKernelGGL((k_sdc_tile<1, false, SourceBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_per_src, 0L);
 }
 void launch_stream_dc_window(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, long origin)
 {
@@ -192,10 +240,25 @@ __device__ __forceinline__ void tile_trigger(TrigShared &sh, const int (&cls)[SP
 // WIN (the live feed): block b is tile tile0 + b of the stream - the same absolute sample positions as in a one-call scan, so the same
 // metric values - fb.samples is the address position 0 would have, n the samples fed so far; fn / carry are indexed by b, and the
 // edge positions count from the push's first edge (the carry that enters a push has count 0)
-template <int RATE, bool GIVEN, bool EMIT, bool WIN = false>
-__global__ __launch_bounds__(256) void k_stream_tile(FrameBatch fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
+// FB = SourceBatch: tile blockIdx.x of recording blockIdx.y, read from that recording's base with its length (n is unused): a position
+// below 0 or at or past the length reads as zero, exactly as in a call with that recording alone; edges is [recordings][cap]
+template <int RATE, bool GIVEN, bool EMIT, bool WIN = false, class FB = FrameBatch>
+__global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
 	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap, long long tile0 = 0)
 {
+	const void *samples = fb.samples;
+	if constexpr (many_v<FB>) {
+		const int q = blockIdx.y;
+		n = fb.src_len[q];
+		if ((long)blockIdx.x * STREAM_TILE >= n)                  // (uniform: a tile past this recording's end)
+			return;
+		samples = (const char *)fb.samples + (size_t)q * fb.frame_stride_bytes;
+		fn += fb.tile0[q];
+		carry += fb.tile0[q];
+		edges += (size_t)q * cap;
+		if constexpr (GIVEN)
+			given += fb.given0[q];
+	}
 	typedef RateCfg<RATE> RC;
 	constexpr int HS = RC::HS, GL = RC::GL, ML = RC::MATCH_LEN, MD = RC::MATCH_DEL;
 	constexpr int D = RC::BUFFER_LEN - 1 - (RC::SEARCH_POS + HS);   // P at time t: its newest pair is (t - D, t - D + HS)
@@ -217,7 +280,7 @@ __global__ __launch_bounds__(256) void k_stream_tile(FrameBatch fb, const float 
 		__shared__ double Sd[L];
 		__shared__ double red[3][4];
 		__shared__ double3 sc3[256];
-		const SampleSrc src{ fb.samples, fb.fmt, fb.channels, n, nullptr };
+		const SampleSrc src{ samples, fb.fmt, fb.channels, n, nullptr };
 		const long long tm0 = T0 - (ML - 1);
 		double p0r = 0.0, p0i = 0.0, r0 = 0.0;
 		{
@@ -381,9 +444,9 @@ __device__ __forceinline__ StreamCarry fn_apply(const StreamFn &f, StreamCarry c
 }
 
 // WIN: the scan starts from the carry the previous push left (*c_in, its edge count taken as 0) and leaves *c_out for the next
-template <bool WIN = false>
-__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts,
-	const StreamCarry *__restrict__ c_in = nullptr, StreamCarry *__restrict__ c_out = nullptr)
+template <bool WIN>
+__device__ __forceinline__ void fn_scan_wg(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts,
+	const StreamCarry *__restrict__ c_in, StreamCarry *__restrict__ c_out)
 {
 	const int tid = threadIdx.x;
 	__shared__ StreamFn sh[1024];
@@ -416,6 +479,21 @@ __global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restr
 			*c_out = c;
 	}
 }
+template <bool WIN = false>
+__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts,
+	const StreamCarry *__restrict__ c_in = nullptr, StreamCarry *__restrict__ c_out = nullptr)
+{
+	fn_scan_wg<WIN>(fn, ntiles, carry, counts, c_in, c_out);
+}
+// The segmented scan: one workgroup per recording composes that recording's tiles alone, from the initial carry (trigger off, no
+// maximum, no edges) - the reset at a recording's start is that nothing of its neighbour is ever composed with it.
+// counts: [recordings][2], cleared by the caller before the scan (a recording without tiles writes nothing)
+__global__ __launch_bounds__(1024) void k_streams_fn_scan(const StreamFn *__restrict__ fn, const long long *__restrict__ tile0, StreamCarry *__restrict__ carry,
+	long long *__restrict__ counts)
+{
+	const long long t0 = tile0[blockIdx.x];
+	fn_scan_wg<false>(fn + t0, (long)(tile0[blockIdx.x + 1] - t0), carry + t0, counts + 2 * (size_t)blockIdx.x, nullptr, nullptr);
+}
 
 void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
 	StreamEdge *edges, long cap, long long *counts)
@@ -434,6 +512,23 @@ void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *giv
 	}
 }
 
+void launch_streams_scan(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, const float *given, StreamFn *fn, StreamCarry *carry,
+	StreamEdge *edges, long cap, long long *counts)
+{
+	const dim3 grid((unsigned)((max_len + STREAM_TILE - 1) / STREAM_TILE), (unsigned)n_src);
+	if (given) {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+	} else {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+	}
+	hipLaunchKernelGGL(k_streams_fn_scan, dim3((unsigned)n_src), dim3(1024), 0, s, fn, fb.tile0, carry, counts);
+	if (given) {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+	} else {
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+	}
+}
+
 void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, long long tile0, long ntiles, StreamFn *fn, StreamCarry *carry,
 	const StreamCarry *c_in, StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts)
 {
@@ -446,15 +541,25 @@ void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, l
 constexpr int ACCEPT_GRID = 2048;
 // WIN (the live feed): fb.samples is the address position 0 would have and only the positions from win_lo on are in memory.  The host
 // has checked that no edge of this push reads below it (api_feed.cpp); an edge that would is left rejected and reported in counts[2]
-template <int RATE, bool WIN = false>
-__global__ __launch_bounds__(256) void k_stream_accept(FrameBatch fb, const cf *__restrict__ tw, const cf *__restrict__ kern,
+// FB = SourceBatch: the edges of recording blockIdx.y (edges: [recordings][cap], counts: [recordings][2]), read from its base with its length
+template <int RATE, bool WIN = false, class FB = FrameBatch>
+__global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restrict__ tw, const cf *__restrict__ kern,
 	StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts, long long win_lo = 0)
 {
+	const void *samples = fb.samples;
+	long n_src = fb.samples_per_frame;
+	if constexpr (many_v<FB>) {
+		const int q = blockIdx.y;
+		samples = (const char *)fb.samples + (size_t)q * fb.frame_stride_bytes;
+		n_src = fb.src_len[q];
+		edges += (size_t)q * cap;
+		counts += 2 * (size_t)q;
+	}
 	typedef RateCfg<RATE> RC;
 	constexpr int BUFFER_LEN = RC::BUFFER_LEN, SEARCH_POS = RC::SEARCH_POS, HALF_LEN = RC::HS, MATCH_DEL = RC::MATCH_DEL, NT = 256;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const long long ne = counts[0] < cap ? counts[0] : cap;
-	const SampleSrc src{ fb.samples, fb.fmt, fb.channels, fb.samples_per_frame, nullptr };
+	const SampleSrc src{ samples, fb.fmt, fb.channels, n_src, nullptr };
 	__shared__ cf buf[HALF_LEN], xr[HALF_LEN];
 	__shared__ cf rot[(HALF_LEN + NT - 1) / NT];
 	__shared__ float red_p[4];
@@ -511,14 +616,23 @@ void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, Str
 	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, false>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, 0LL));
 }
+void launch_streams_accept(hipStream_t s, int rate, int n_src, SourceBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
+{
+	// (workgroups per recording: the one-call grid shared out, every recording's edges strided over its own)
+	long per = ACCEPT_GRID / n_src < cap ? ACCEPT_GRID / n_src : cap;
+	per = per > 0 ? per : 1;
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, false, SourceBatch>), dim3((unsigned)per, (unsigned)n_src), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
+		edges, cap, counts, 0LL));
+}
 void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts, long long win_lo)
 {
 	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, true>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, win_lo));
 }
 
-__global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
-	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base)
+// rec_src (nullable) / src: the recording every record written reads (many recordings in one call)
+__device__ __forceinline__ void stream_records_wg(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
+	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base, int *__restrict__ rec_src = nullptr, int src = 0)
 {
 	const int tid = threadIdx.x;
 	__shared__ long long sh[1024];
@@ -552,11 +666,62 @@ __global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const S
 			st.pend_phase = 0.f;
 			st.pending = 0;
 			rec[k] = st;
+			if (rec_src)
+				rec_src[k] = src;
 		}
 		base += total;
 	}
 	if (tid == 0)
 		counts[1] = base;
+}
+__global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
+	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base)
+{
+	stream_records_wg(buffer_len, edges, cap, counts, rec, max_rec, rec_base, rej_base);
+}
+
+// Many recordings: their accepted preambles counted (counts[q][1]), ...
+__global__ __launch_bounds__(1024) void k_streams_count(const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts)
+{
+	const int tid = threadIdx.x, q = blockIdx.x;
+	__shared__ long long sh[1024];
+	const long long ne = counts[2 * (size_t)q] < cap ? counts[2 * (size_t)q] : cap;
+	long long acc = 0;
+	for (long long e = tid; e < ne; e += 1024)
+		acc += edges[(size_t)q * cap + e].accept;
+	block_scan_incl<1024>(acc, sh, tid, add_ll);
+	if (tid == 0)
+		counts[2 * (size_t)q + 1] = sh[1023];
+}
+// ... the packed order: first[q] = the records of the recordings before q, each min(accepted, max_per_src) (one workgroup,
+// a stretch of recordings per thread), first[n_src] = all of them ...
+__global__ __launch_bounds__(1024) void k_streams_first(int n_src, const long long *__restrict__ counts, long long max_per_src, long long *__restrict__ first)
+{
+	const int tid = threadIdx.x;
+	__shared__ long long sh[1024];
+	const int per = (n_src + 1023) / 1024, q0 = tid * per, q1 = q0 + per < n_src ? q0 + per : n_src;
+	long long mine = 0;
+	for (int q = q0; q < q1; ++q)
+		mine += counts[2 * (size_t)q + 1] < max_per_src ? counts[2 * (size_t)q + 1] : max_per_src;
+	block_scan_incl<1024>(mine, sh, tid, add_ll);
+	long long at = tid ? sh[tid - 1] : 0;
+	for (int q = q0; q < q1; ++q) {
+		first[q] = at;
+		at += counts[2 * (size_t)q + 1] < max_per_src ? counts[2 * (size_t)q + 1] : max_per_src;
+	}
+	if (tid == 1023)
+		first[n_src] = sh[1023];
+}
+// ... and every recording's records at its place in it, as k_stream_records writes them for that recording alone (record indices
+// and cumulative rejects count from the recording's own start), with the recording each one reads
+__global__ __launch_bounds__(1024) void k_streams_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
+	const long long *__restrict__ first, SyncState *__restrict__ rec, int *__restrict__ rec_src, long long max_per_src, long long max_rec)
+{
+	const int q = blockIdx.x;
+	const long long at = first[q];
+	long long room = max_rec > at ? max_rec - at : 0;             // only the first max_rec of the packed order are written
+	room = room < max_per_src ? room : max_per_src;
+	stream_records_wg(buffer_len, edges + (size_t)q * cap, cap, counts + 2 * (size_t)q, rec + at, (long)room, 0, 0, rec_src + at, q);
 }
 
 void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec,
@@ -565,6 +730,15 @@ void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, lon
 	int buffer_len = 0;
 	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
 	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec, rec_base, rej_base);
+}
+void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge *edges, long cap, long long *counts, long long *first,
+	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec)
+{
+	int buffer_len = 0;
+	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
+	hipLaunchKernelGGL(k_streams_count, dim3((unsigned)n_src), dim3(1024), 0, s, edges, cap, counts);
+	hipLaunchKernelGGL(k_streams_first, dim3(1), dim3(1024), 0, s, n_src, counts, max_per_src, first);
+	hipLaunchKernelGGL(k_streams_records, dim3((unsigned)n_src), dim3(1024), 0, s, buffer_len, edges, cap, counts, first, rec, rec_src, max_per_src, max_rec);
 }
 
 }  // namespace rx

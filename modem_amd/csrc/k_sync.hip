@@ -112,14 +112,19 @@ __global__ __launch_bounds__(256) void k_mono_carries(FrameBatch fb, FrontCoef c
 // that state
 constexpr int FE_STRETCH = 4 * 2048 - 256;
 // WIN (the live feed, one frame): block b is stretch stretch0 + b; fb.samples, ma.ck and z_all are the addresses position 0 would have
-template <int RATE, bool WIN = false>
-__global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FrameBatch fb, MonoArgs ma, cf *__restrict__ z_all, long stretch0 = 0)
+// FB = SourceBatch (many recordings in one call): frame f is source f with its own length; the grid covers the longest one
+template <int RATE, bool WIN = false, class FB = FrameBatch>
+__global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FB fb, MonoArgs ma, cf *__restrict__ z_all, long stretch0 = 0)
 {
 	static_assert(MonoCfg<RATE>::REACH + MONO_CK <= 256, "a stretch and its lead-in fit four spans");
 	const int f = blockIdx.y, tid = threadIdx.x;
 	const long lo = ((long)blockIdx.x + (WIN ? stretch0 : 0)) * FE_STRETCH;
 	__shared__ typename MonoCover<RATE, 256>::Shared msh;
 	MonoCover<RATE, 256> mc;
+	if constexpr (!std::is_same<FB, FrameBatch>::value) {
+		if (lo >= fb.src_len[f])
+			return;
+	}
 	mc.init(mono_frame(fb, ma.ck, ma.ck_per_frame, f), ma, &msh, z_all + (size_t)f * fb.samples_per_frame, tid);
 	mc.hi = lo + FE_STRETCH < mc.fr.n ? lo + FE_STRETCH : mc.fr.n;   // (cover() runs whole spans: they reach into the next workgroup's stretch)
 	mc.cover(ma, lo, lo + FE_STRETCH, tid);
@@ -584,6 +589,11 @@ void launch_front_end(hipStream_t s, int rate, int n, FrameBatch fb, MonoArgs ma
 		maq.ck = ma.ck + (size_t)f0 * ma.ck_per_frame;
 		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, false>), dim3(stretches, nf), dim3(256), 0, s, fbq, maq, z + (size_t)f0 * fb.samples_per_frame, 0L));
 	}
+}
+void launch_streams_front(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, MonoArgs ma, cf *z)
+{
+	const unsigned stretches = (unsigned)((max_len + FE_STRETCH - 1) / FE_STRETCH);
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, false, SourceBatch>), dim3(stretches, (unsigned)n_src), dim3(256), 0, s, fb, ma, z, 0L));
 }
 long front_end_stretch() { return FE_STRETCH; }
 void launch_front_end_window(hipStream_t s, int rate, FrameBatch fb, MonoArgs ma, cf *z, long stretch0, long n_stretch)

@@ -15,6 +15,20 @@ struct FrameBatch {
 	int channels;                  // 1 or 2
 };
 
+// Many recordings in one call (ofdmrx_decode_streams): source q is src_len[q] sample frames at samples +
+// q * frame_stride_bytes, and frame f of a launch reads source src_of[f] (src_of = nullptr: source f).  A kernel template takes
+// either kind of batch: with a FrameBatch the two helpers below are what the kernels have always computed.
+struct SourceBatch : FrameBatch {
+	const int *src_of;             // [frames of the launch], nullable
+	const int *src_len;            // [sources]
+	const long long *tile0;        // the stream scan: [sources + 1] first tile of every source in the per-tile arrays (a running sum)
+	const long long *given0;       // ofdmrx_debug_streams_edges: [sources] where its sequence starts in the packed timing values
+};
+__host__ __device__ inline int batch_source(const FrameBatch &, int f) { return f; }
+__host__ __device__ inline long batch_len(const FrameBatch &fb, int) { return fb.samples_per_frame; }
+__host__ __device__ inline int batch_source(const SourceBatch &fb, int f) { return fb.src_of ? fb.src_of[f] : f; }
+__host__ __device__ inline long batch_len(const SourceBatch &fb, int q) { return fb.src_len[q]; }
+
 struct FrontCoef {                 // BlockDC::samples(2*(symbol_len+guard_len)) + Hilbert<cmplx,filter_len> (decode.cc:386,193)
 	float dc_a, dc_b;
 	float reco, imco[32];          // (filter_len-1)/4 odd-tap pairs: 5 / 10 / 28 / 31 at 8 / 16 / 44.1 / 48 kHz
@@ -178,6 +192,9 @@ void launch_header(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const M
 void launch_osd_only(hipStream_t s, int n, Tables tb, const int8_t *soft, uint8_t *hard, int32_t *unique);
 bool demod_forms_cons(int rate);   // cons is complete after k_demod (else k_theil_sen forms the rows from the carriers)
 void launch_demod(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const MonoArgs &ma, Tables tb, const SyncState *st, cf *cons, cf *carr);
+// the same two for records of many recordings (2-channel sources: mono input has been through launch_streams_front)
+void launch_header_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, SyncState *st, int8_t *hdr_soft);
+void launch_demod_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, const SyncState *st, cf *cons, cf *carr);
 void launch_theil_sen(hipStream_t s, int n, const SyncState *st, cf *cons, const cf *carr, float *slope, float *yint, int *chunk_flags);
 void launch_theil_sen_raw(hipStream_t s, int rows, int cols, const float *y, float *slope, float *yint);
 // D5's rotation + D6-D8 + the syndrome certificate (k_finish.hip: k_back).  cert_mode 0: every frame with a header goes to the list
@@ -265,5 +282,21 @@ void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, l
 	const StreamCarry *c_in, StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts);
 // counts[2] is set when an edge would read below win_lo (it is then left rejected: an internal error)
 void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts, long long win_lo);
+
+// ---- many recordings in one call (api_streams.cpp): the same scan with the recording as a second grid dimension.
+// Every recording is scanned from its own position 0 with its own tile count, and nothing crosses from one to the next: what
+// enters tile 0 of each is the initial state.  fb.tile0 places a recording's tiles in tile_end / tile_in / fn / carry; ck is
+// [n_src][ck_per_src], z [n_src][fb.samples_per_frame], edges [n_src][cap], counts [n_src][2] (falling edges, accepted preambles).
+// max_len: the longest recording (the grids' first dimension).  The caller clears counts before launch_streams_scan: a recording
+// without tiles writes none
+void launch_streams_dc(hipStream_t s, int n_src, long max_len, SourceBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, int ck_per_src);
+void launch_streams_front(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, MonoArgs ma, cf *z);
+void launch_streams_scan(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, const float *given, StreamFn *fn, StreamCarry *carry,
+	StreamEdge *edges, long cap, long long *counts);
+void launch_streams_accept(hipStream_t s, int rate, int n_src, SourceBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
+// first[q] (n_src + 1): where recording q's records begin in the packed order, a running sum of min(accepted, max_per_src);
+// rec / rec_src: the SyncState of every packed record below max_rec and the recording it reads
+void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge *edges, long cap, long long *counts, long long *first,
+	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec);
 
 }  // namespace rx

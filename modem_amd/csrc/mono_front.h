@@ -91,6 +91,10 @@ __device__ __forceinline__ MonoFrame mono_frame(const FrameBatch &fb, const doub
 {
 	return MonoFrame{ (const char *)fb.samples + (size_t)f * fb.frame_stride_bytes, fb.fmt, fb.samples_per_frame, ck_all + (size_t)f * ck_per_frame };
 }
+__device__ __forceinline__ MonoFrame mono_frame(const SourceBatch &fb, const double *ck_all, int ck_per_frame, int f)   // (source f, its own length)
+{
+	return MonoFrame{ (const char *)fb.samples + (size_t)f * fb.frame_stride_bytes, fb.fmt, fb.src_len[f], ck_all + (size_t)f * ck_per_frame };
+}
 __device__ __forceinline__ double mono_pow(double a, int e)   // a^e, e >= 0
 {
 	double pw = 1.0, bs = a;

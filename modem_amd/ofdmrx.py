@@ -26,6 +26,7 @@ EXPORTS = [
     "ofdmrx_tx_encode_device", "ofdmrx_stream_samples", "ofdmrx_tx_encode_stream_device", "ofdmrx_tx_encode_stream",
     "ofdmrx_callsign_value", "ofdmrx_decode_stream", "ofdmrx_decode_stream_device", "ofdmrx_debug_stream_edges",
     "ofdmrx_feed_begin", "ofdmrx_feed_push", "ofdmrx_feed_end", "ofdmrx_feed_lag", "ofdmrx_feed_resident_samples",
+    "ofdmrx_decode_streams", "ofdmrx_decode_streams_device", "ofdmrx_debug_streams_edges",
 ]
 
 
@@ -114,6 +115,12 @@ def load_library():
     L.ofdmrx_decode_stream_device.argtypes = stream
     L.ofdmrx_debug_stream_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_size_t)]
+    streams = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+               C.c_void_p, C.c_void_p]
+    L.ofdmrx_decode_streams.argtypes = streams
+    L.ofdmrx_decode_streams_device.argtypes = streams
+    L.ofdmrx_debug_streams_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
     L.ofdmrx_feed_begin.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.ofdmrx_feed_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
                                    C.POINTER(C.c_size_t)]
@@ -292,6 +299,67 @@ class Receiver:
         self._check(self._lib.ofdmrx_debug_stream_edges(self._h, _ptr(timing), len(timing), cap, _ptr(te), _ptr(tm), _ptr(im), C.byref(ne)))
         k = min(ne.value, cap)
         return te[:k], tm[:k], im[:k], ne.value
+
+    def decode_streams(self, pcms, max_frames_per_stream=None, esn0_rows=False, max_records=None, stride_samples=None):
+        """many recordings in one call: pcms is a list of arrays [samples, channels] (or [samples] mono) of one dtype and channel
+        count, lengths may differ -> a list of (payloads [k, 5380], results [k], n_preambles) per recording, k =
+        min(n_preambles, max_frames_per_stream) (less for the recordings max_records cuts); with esn0_rows each tuple ends with its
+        rows.  max_records None: every record (the call is made twice when the first guess is short)"""
+        pcms = [np.ascontiguousarray(p) for p in pcms]
+        pcms = [p[:, None] if p.ndim == 1 else p for p in pcms]
+        if not pcms or any(p.dtype != pcms[0].dtype or p.shape[1] != pcms[0].shape[1] for p in pcms):
+            raise OfdmRxError("decode_streams: the recordings must share dtype and channel count")
+        dt, ch, S = pcms[0].dtype, pcms[0].shape[1], len(pcms)
+        lens = np.array([p.shape[0] for p in pcms], np.uintp)
+        stride = max(int(lens.max()), 1) if stride_samples is None else int(stride_samples)
+        buf = np.zeros((S, stride, ch), dt)
+        for q, p in enumerate(pcms):
+            buf[q, :p.shape[0]] = p
+        per = np.iinfo(np.uintp).max if max_frames_per_stream is None else int(max_frames_per_stream)
+        cap = int(max_records) if max_records is not None else int(sum(min(per, max(16, int(n) // 20000)) for n in lens))
+        npre, first = np.zeros(S, np.uintp), np.zeros(S + 1, np.uintp)
+        while True:
+            out = np.zeros((max(cap, 1), PAYLOAD_BYTES), np.uint8)
+            res = np.zeros(max(cap, 1), RESULT_DTYPE)
+            rows = np.zeros((max(cap, 1), 126), np.float32) if esn0_rows else None
+            if esn0_rows:
+                self._check(self._lib.ofdmrx_set_esn0_rows(self._h, _ptr(rows)))
+            try:
+                self._check(self._lib.ofdmrx_decode_streams(self._h, _ptr(buf), self._fmt(dt), ch, S, stride * ch * dt.itemsize, _ptr(lens), per, cap,
+                                                            _ptr(out) if cap else None, _ptr(res) if cap else None, _ptr(npre), _ptr(first)))
+            finally:
+                if esn0_rows:
+                    self._lib.ofdmrx_set_esn0_rows(self._h, None)
+            if max_records is not None or int(first[S]) <= cap:
+                break
+            cap = int(first[S])
+        ret = []
+        for q in range(S):
+            a, b = min(int(first[q]), cap), min(int(first[q + 1]), cap)
+            ret.append((out[a:b], res[a:b], int(npre[q])) + ((rows[a:b],) if esn0_rows else ()))
+        return ret
+
+    def decode_streams_device(self, d_samples, fmt, channels, n_samples, stride_bytes, max_frames_per_stream, max_records, d_payload, d_results):
+        """device pointers (ints), or pinned host outputs; n_samples: the recordings' lengths (host) -> (n_preambles [S], first_record
+        [S + 1]); the call synchronises once, after the scan of all recordings"""
+        lens = np.ascontiguousarray(n_samples, dtype=np.uintp)
+        S = len(lens)
+        npre, first = np.zeros(S, np.uintp), np.zeros(S + 1, np.uintp)
+        self._check(self._lib.ofdmrx_decode_streams_device(self._h, d_samples, fmt, channels, S, stride_bytes, _ptr(lens), max_frames_per_stream,
+                                                           max_records, d_payload, d_results, _ptr(npre), _ptr(first)))
+        return npre.astype(np.int64), first.astype(np.int64)
+
+    def debug_streams_edges(self, timings, max_edges_per_stream=None):
+        """the segmented trigger scan on several timing sequences -> per sequence (t_edge, t_max, index_max, n_edges)"""
+        timings = [np.ascontiguousarray(t, dtype=np.float32) for t in timings]
+        lens = np.array([len(t) for t in timings], np.uintp)
+        S = len(timings)
+        cap = max_edges_per_stream if max_edges_per_stream is not None else max(1, int(lens.max()) // 2 + 1)
+        packed = np.concatenate(timings) if S else np.zeros(0, np.float32)
+        te, tm, im = np.zeros((S, cap), np.int64), np.zeros((S, cap), np.int64), np.zeros((S, cap), np.int32)
+        ne = np.zeros(S, np.uintp)
+        self._check(self._lib.ofdmrx_debug_streams_edges(self._h, _ptr(packed), S, _ptr(lens), cap, _ptr(te), _ptr(tm), _ptr(im), _ptr(ne)))
+        return [(te[q, :min(int(ne[q]), cap)], tm[q, :min(int(ne[q]), cap)], im[q, :min(int(ne[q]), cap)], int(ne[q])) for q in range(S)]
 
     def set_esn0_rows(self, d_rows):
         """device pointer (int) to n x 126 floats for the decode_device calls that follow, or None"""

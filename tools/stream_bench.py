@@ -10,6 +10,10 @@ copies of it with skip counts 0 .. n-1).  Every payload is checked.  Prints one 
 --feed BLOCK: instead, ONE such recording from host memory through the live feed (ofdmrx_feed_*) in pushes of BLOCK samples, beside the
 host-pointer one-call entry (ofdmrx_decode_stream) on the same samples: samples/s and records/s of both and their ratio.  Every push
 synchronises with the host, so the feed is the slower per sample; records and payloads are checked to be the same.
+
+--batched: instead, the --streams recordings (a) through a loop of ofdmrx_decode_stream_device, one call per recording, and (b) through
+ONE ofdmrx_decode_streams_device call, alternating step by step: records/s and samples/s of both with the median and the range over the
+steps, and their ratio.  The records of (a) and (b) are checked to be the same bytes.
 """
 import argparse
 import ctypes as C
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--skip-count", type=int, default=64)
     ap.add_argument("--out", default="")
     ap.add_argument("--feed", type=int, default=0, metavar="BLOCK", help="the same recording through the live feed in pushes of BLOCK samples")
+    ap.add_argument("--batched", action="store_true", help="a loop of one-call decodes over the recordings against one ofdmrx_decode_streams_device call")
     a = ap.parse_args()
     import torch
     import modem_amd
@@ -45,6 +50,8 @@ def main():
     L.ofdmrx_stream_samples.restype = C.c_long
     S, K = a.streams, a.count
     n = int(L.ofdmrx_stream_samples(8000, 6, K))
+    if a.batched:
+        return batched_bench(a, rx, torch, dev, S, K, n)
     g = torch.Generator(device=dev)
     g.manual_seed(7)
     pay = torch.randint(0, 256, (S, K, 5380), dtype=torch.uint8, device=dev, generator=g)
@@ -135,6 +142,67 @@ def main():
     print(line)
     if a.out:
         with open(a.out, "w") as f:
+            f.write(line + "\n")
+    rx.close()
+
+
+def batched_bench(a, rx, torch, dev, S, K, n):
+    """S recordings of K payloads: a loop of one-call decodes against one call for all of them"""
+    import modem_amd.ofdmrx as M
+    L = rx._lib
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    pay = torch.randint(0, 256, (S, K, 5380), dtype=torch.uint8, device=dev, generator=g)
+    clean = torch.empty((S, n, 2), dtype=torch.int16, device=dev)
+    pcm = torch.empty((S, n, 2), dtype=torch.int16, device=dev)
+    rc = L.ofdmrx_tx_encode_stream_device(rx._h, pay.data_ptr(), S, K, 6, 2000, b"ANONYMOUS", 2, 16, clean.data_ptr())
+    assert rc == 0, rc
+    rx.awgn_tile(clean.data_ptr(), S, pcm.data_ptr(), S, n, a.noise_db, 11, 0)
+    rx.synchronize()
+    del clean
+    rsz = M.RESULT_DTYPE.itemsize
+    outs = {k: (torch.zeros((S * K, 5380), dtype=torch.uint8, device=dev), torch.zeros((S * K, rsz), dtype=torch.uint8, device=dev)) for k in ("loop", "batched")}
+    lens = np.full(S, n, np.uintp)
+
+    def loop():
+        out, res = outs["loop"]
+        for s in range(S):
+            npre = rx.decode_stream_device(pcm[s].data_ptr(), 0, 2, n, K, out[s * K].data_ptr(), res[s * K].data_ptr())
+            assert npre == K, npre
+        rx.synchronize()
+
+    def batched():
+        out, res = outs["batched"]
+        npre, first = rx.decode_streams_device(pcm.data_ptr(), 0, 2, lens, n * 4, K, S * K, out.data_ptr(), res.data_ptr())
+        rx.synchronize()
+        assert (npre == K).all() and first[S] == S * K, (npre, first)
+
+    for _ in range(a.warmup):
+        loop()
+        batched()
+    times = {"loop": [], "batched": []}
+    for _ in range(a.steps):                                     # alternating: both see the same drift of the clocks
+        for name, fn in (("loop", loop), ("batched", batched)):
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    same = all(bool((outs["loop"][i] == outs["batched"][i]).all().item()) for i in (0, 1))
+    ok = int((outs["batched"][0] == pay.reshape(S * K, 5380)).all(dim=1).sum().item())
+    rec = {"metric": "many recordings: a loop of ofdmrx_decode_stream_device against one ofdmrx_decode_streams_device, mode-6 8 kHz 2-channel int16, "
+                     "AWGN %g dB" % a.noise_db,
+           "streams": S, "payloads_per_stream": K, "samples_per_stream": n, "steps": a.steps, "warmup": a.warmup}
+    for name in ("loop", "batched"):
+        t = np.array(times[name])
+        med = float(np.median(t))
+        rec.update({name + "_ms_median": med * 1e3, name + "_ms_min": float(t.min()) * 1e3, name + "_ms_max": float(t.max()) * 1e3,
+                    name + "_records_per_s": S * K / med, name + "_samples_per_s": S * n / med})
+    rec.update({"batched_vs_loop": rec["loop_ms_median"] / rec["batched_ms_median"],
+                "batched_vs_loop_worst_case": rec["loop_ms_min"] / rec["batched_ms_max"],
+                "same_bytes_as_loop": same, "payloads_ok": ok})
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "a") as f:
             f.write(line + "\n")
     rx.close()
 
