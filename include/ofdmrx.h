@@ -51,7 +51,8 @@ extern "C" {
  *   7: ofdmrx_decode_stream, ofdmrx_decode_stream_device (every preamble of one recording in one call), ofdmrx_debug_stream_edges;
  *      added within 1.7 (the minor number stays: a caller detects them by symbol): the live feed - ofdmrx_feed_begin, ofdmrx_feed_push,
  *      ofdmrx_feed_end, ofdmrx_feed_lag, ofdmrx_feed_resident_samples; many recordings in one call - ofdmrx_decode_streams,
- *      ofdmrx_decode_streams_device, ofdmrx_debug_streams_edges */
+ *      ofdmrx_decode_streams_device, ofdmrx_debug_streams_edges; a bank of live channels - ofdmrx_bank_begin, ofdmrx_bank_push,
+ *      ofdmrx_bank_end, ofdmrx_bank_resident_samples, ofdmrx_bank_preambles, ofdmrx_bank_last_stage_ops */
 #define OFDMRX_ABI_MINOR 7
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -319,6 +320,65 @@ int ofdmrx_feed_end(ofdmrx_handle *h, size_t max_frames, uint8_t *payload_out, o
 	size_t *n_records, size_t *n_left);
 long long ofdmrx_feed_lag(ofdmrx_handle *h);
 long long ofdmrx_feed_resident_samples(ofdmrx_handle *h);
+
+/*
+ * Live feed bank (added within revision 1.7): many recordings that are all still arriving - a bank of receiver channels - pushed and
+ * decoded in one call.  One bank per handle, never beside a feed; HOST pointers; the calls block.  A push costs the same number of
+ * kernel launches, copies and host synchronisations whatever the number of channels, and the records that are due on all channels
+ * go through the record pipeline together, in shared chunks.
+ *   begin   n_channels (1 .. 65535) receiver channels, all of `channels` interleaved values of sample_format at the handle's rate;
+ *           every channel starts at position 0, record 0.
+ *   push    channel c brings n_samples[c] more sample frames (0 allowed; each <= 1 << 26), found at samples + c * stride_bytes.
+ *           ends (nullable, [n_channels]): non-zero = channel c's stream is over after these samples.  Returns the records that
+ *           have become due.
+ *   end     every channel still open ends; the bank closes when an end call leaves *n_left == 0.
+ * Per channel: the records of channel c are the records returned for c (record_channel[i] == c) over all push and end calls,
+ * concatenated in the order returned.  They equal what a single ofdmrx_feed_* returns when fed channel c's samples in the same
+ * sequence of push lengths - every payload byte and every byte of every ofdmrx_frame_result, every format and every rate.  A
+ * zero-length share counts as a zero-length push: the channel behaves as a single feed does with that push left out.  For 2-channel
+ * input this is therefore also ofdmrx_decode_stream of the concatenation of channel c's samples, byte for byte.
+ * Mono input inherits the feed's documented relation to the one-call decode and no more: every channel's DC-blocker states are
+ * composed in exactly the order a single feed with that channel's push lengths composes them.
+ * Positions and counters: sc_start is the absolute position in channel c (64-bit), n_sync_rejects counts from channel c's start,
+ * record_index[i] is k, the preamble index ofdmrx_decode_stream would give the record, record_channel[i] is c.
+ * Nothing crosses channels: how many other channels there are, what they hold, when they push and whether they have ended has no
+ * effect on a channel's records.
+ * Due: a channel's record is due by the single feed's rule applied to that channel's own samples fed and scan frontier - one with a
+ * valid header once its frame's last sample has arrived, one with a failed header once the scan has passed its edge and its header
+ * symbol has arrived.  A channel that ends has its last partial tile scanned with n = its samples fed and every pending preamble
+ * decoded with the samples past the end read as zero, in the call that ends it.
+ * Order: within one call the records are ordered by channel index, then by preamble order; across calls delivery is first in, first
+ * out.  max_records caps what a call writes (payload_out: 5380 bytes each); the rest stay staged, *n_left counts them, and a later
+ * call (all lengths 0) drains them.  Nothing past the first *n_records entries of any output array is touched.
+ * Es/N0 rows (ofdmrx_set_esn0_rows, a host pointer): row block i belongs to the i-th record the call writes.  The attempt log is not
+ * written and OFDMRX_FLAG_TWO_LANES is ignored; the other flags hold, as for the feed.
+ * An ended channel accepts only n_samples[c] == 0 and stays closed until the bank closes.
+ * OFDMRX_E_ARG, before any device call: push or end without begin; begin while a bank or a feed is open; ofdmrx_feed_begin, any
+ * ofdmrx_decode_batch* or ofdmrx_decode_stream* while a bank is open; a NULL handle, n_samples, n_records or n_left; NULL samples
+ * while any length is non-zero; NULL outputs (any of the four arrays) with max_records > 0; n_channels outside 1 .. 65535; a bad
+ * format or channel count; a length above 1 << 26; samples for an ended channel; a stride that is not a multiple of the
+ * sample-frame size or is smaller than the longest share of this push; samples off the sample-frame boundary; a channel index out
+ * of range in the two queries (they return -1).  ofdmrx_destroy frees an open bank.
+ * ofdmrx_bank_resident_samples: as ofdmrx_feed_resident_samples, for one channel: fed[c] - base[c].  Device memory: the windows of
+ * all channels share one capacity - two slabs of n_channels x cap sample frames, cap up to 1.5 x the largest window any channel has
+ * needed, so 2 x cap x (bytes per sample frame) per channel (mono input: 2 x cap x (bytes per sample + 8 + 1 / 8) for the samples,
+ * the analytic signal and the DC blocker's kept states) - plus 200 bytes of per-channel parameters and carries, every channel's
+ * share of the edge buffer (at most 4096 edges of 40 bytes), and the packed new samples of one push.
+ * ofdmrx_bank_preambles: preambles accepted on that channel so far.
+ * ofdmrx_bank_last_stage_ops: kernel launches + memcpys + host synchronisations the bank's own stages (window move, new samples,
+ * scan, accept, records, header) enqueued in the last bank call - NOT the record pipeline's (decode_records), whose count follows
+ * the number of records.  It does not depend on n_channels; it grows only with an edge-buffer regrow pass and with the header
+ * stage's loop over chunks when more preambles are pending than a chunk holds.
+ */
+int ofdmrx_bank_begin(ofdmrx_handle *h, size_t n_channels, int sample_format, int channels);
+int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t stride_bytes, const size_t *n_samples, const uint8_t *ends,
+	size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results, int32_t *record_channel, int64_t *record_index,
+	size_t *n_records, size_t *n_left);
+int ofdmrx_bank_end(ofdmrx_handle *h, size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results,
+	int32_t *record_channel, int64_t *record_index, size_t *n_records, size_t *n_left);
+long long ofdmrx_bank_resident_samples(ofdmrx_handle *h, size_t channel);
+long long ofdmrx_bank_preambles(ofdmrx_handle *h, size_t channel);
+long long ofdmrx_bank_last_stage_ops(ofdmrx_handle *h);
 
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);

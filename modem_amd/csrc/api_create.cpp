@@ -153,6 +153,8 @@ extern "C" void ofdmrx_destroy(ofdmrx_handle *h)
 		(void)hipStreamSynchronize(h->stream);
 	if (h->feed)
 		feed_free(h);
+	if (h->bank)
+		bank_free(h);
 	for (hipStream_t sx : { h->stream_b, h->stream_fin, h->stream_c })
 		if (sx) {
 			(void)hipStreamSynchronize(sx);

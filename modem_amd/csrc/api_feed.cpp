@@ -370,7 +370,7 @@ extern "C" int ofdmrx_feed_begin(ofdmrx_handle *h, int fmt, int channels)
 {
 	if (!h || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channels < 1 || channels > 2)
 		return OFDMRX_E_ARG;
-	if (h->feed)
+	if (h->feed || h->bank)
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	ofdmrx_feed *f = new (std::nothrow) ofdmrx_feed;

@@ -226,6 +226,8 @@ struct ofdmrx_handle {
 	std::vector<long long> sxs_tile0_h, sxs_given0_h, sxs_counts_h;
 	long sxs_edge_cap = 0;    // every recording's share of the edge buffer
 	struct ofdmrx_feed *feed = nullptr;   // the open live feed (api_feed.cpp), one per handle
+	struct ofdmrx_bank *bank = nullptr;   // the open bank of live channels (api_bank.cpp), one per handle, never beside a feed
+	bool busy_live() const { return feed || bank; }   // a handle with an open feed or bank decodes nothing else
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -260,6 +262,9 @@ int finish_call(ofdmrx_handle *h, int r);                                       
 // d_records[k] (header, demod, ...); device or pinned host outputs like ofdmrx_decode_batch_device; keeps the call's events so far
 // srcs (nullable): the records of several recordings in one chunk plan - record k reads recording src_of[k], src_len[..] sample
 // frames at fb.samples + src_of[k] * stride_bytes (device arrays; fb has stride 0, fb.samples_per_frame the longest recording)
-struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; };
+// org (nullable; then src_len and stride_bytes are unused): the sources are live channels read through their windows - position 0 of
+// channel q would lie at fb.samples + org[q] bytes and the channel has len[q] sample frames so far (kernels.h: WindowBatch)
+struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; const long long *org = nullptr; const long long *len = nullptr; };
 int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources *srcs = nullptr);
+void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank and its windows go
 void feed_free(ofdmrx_handle *h);                                                           // api_feed.cpp: the open feed and its window go

@@ -108,6 +108,14 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 		sb.src_of = srcs->src_of;
 		sb.src_len = srcs->src_len;
 	}
+	WindowBatch wb{};
+	const bool windows = srcs && srcs->org;
+	if (windows) {
+		static_cast<FrameBatch &>(wb) = fb;
+		wb.src_of = srcs->src_of;
+		wb.org = srcs->org;
+		wb.len = srcs->len;
+	}
 	SyncState *st = h->st.as<SyncState>();
 	const MonoArgs ma = mono_args(h->host.front, nullptr, 0);
 	size_t e0 = mark(h, s);
@@ -119,7 +127,9 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 	*ev_after_sync = b;
 	{
 		Range r("ofdmrx:header_osd");
-		if (srcs)
+		if (windows)
+			launch_header_bank(s, h->rate, n, wb, h->dev, st, h->hdr_soft.as<int8_t>());
+		else if (srcs)
 			launch_header_sources(s, h->rate, n, sb, h->dev, st, h->hdr_soft.as<int8_t>());
 		else
 			launch_header(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->hdr_soft.as<int8_t>(), nullptr, nullptr);
@@ -128,7 +138,9 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 	h->spans.push_back({ OFDMRX_T_HEADER, b, c });
 	{
 		Range r("ofdmrx:demod");
-		if (srcs)
+		if (windows)
+			launch_demod_bank(s, h->rate, n, wb, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
+		else if (srcs)
 			launch_demod_sources(s, h->rate, n, sb, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
 		else
 			launch_demod(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
@@ -526,7 +538,7 @@ extern "C" int ofdmrx_decode_batch_device(ofdmrx_handle *h, const void *d_sample
 {
 	const FrameBatch fb{ d_samples, stride, (long)spf, fmt, channels };
 	int r = check_args(h, fb, n_frames, d_payload, d_results);
-	if (r || h->feed)                                             // (a handle with an open feed decodes nothing else)
+	if (r || h->busy_live())                                      // (a handle with an open feed or bank decodes nothing else)
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	const Outputs out = outputs_of(h, d_payload, d_results);
@@ -692,7 +704,7 @@ extern "C" int ofdmrx_decode_batch(ofdmrx_handle *h, const void *samples, int fm
 {
 	const FrameBatch fb{ samples, stride, (long)spf, fmt, channels };
 	int r = check_args(h, fb, n_frames, payload_out, results);
-	if (r || h->feed)
+	if (r || h->busy_live())
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	int max_skip = 0;

@@ -102,7 +102,7 @@ extern "C" int ofdmrx_decode_stream_device(ofdmrx_handle *h, const void *d_sampl
 {
 	const FrameBatch fb{ d_samples, 0, (long)n_samples, fmt, channels };
 	int r = stream_args(h, fb, max_frames, d_payload_out, d_results, n_preambles);
-	if (r || h->feed)                                             // (a handle with an open feed decodes nothing else)
+	if (r || h->busy_live())                                      // (a handle with an open feed or bank decodes nothing else)
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	return decode_stream_dev(h, fb, max_frames, Outputs{ d_payload_out, (Result *)d_results, h->esn0_user }, n_preambles);
@@ -112,7 +112,7 @@ extern "C" int ofdmrx_decode_stream(ofdmrx_handle *h, const void *samples, int f
 	size_t max_frames, uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_preambles)
 {
 	int r = stream_args(h, FrameBatch{ samples, 0, (long)n_samples, fmt, channels }, max_frames, payload_out, results, n_preambles);
-	if (r || h->feed)
+	if (r || h->busy_live())
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	const size_t in_bytes = n_samples * sample_bytes(fmt) * (size_t)channels;

@@ -183,7 +183,7 @@ extern "C" int ofdmrx_decode_streams_device(ofdmrx_handle *h, const void *d_samp
 {
 	StreamsCall call;
 	int r = streams_args(h, d_samples, fmt, channels, n_streams, stride, n_samples, max_records, d_payload_out, d_results, n_preambles, first_record, &call);
-	if (r || h->feed)                                             // (a handle with an open feed decodes nothing else)
+	if (r || h->busy_live())                                      // (a handle with an open feed or bank decodes nothing else)
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	begin_call(h);
@@ -201,7 +201,7 @@ extern "C" int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int 
 {
 	StreamsCall call;
 	int r = streams_args(h, samples, fmt, channels, n_streams, stride, n_samples, max_records, payload_out, results, n_preambles, first_record, &call);
-	if (r || h->feed)
+	if (r || h->busy_live())
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	begin_call(h);

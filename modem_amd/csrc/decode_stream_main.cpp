@@ -8,6 +8,9 @@
 // `decode_stream --batch OUTROOT A.wav B.wav ...`: many recordings in one call (ofdmrx_decode_streams).  Recording i goes to
 // OUTROOT/<i>/<k>.dat (the directories are made) and its summary lines are the one-call lines prefixed with `<i>:`.  The inputs must
 // share sample rate, channel count and sample format.
+// `decode_stream --live --batch OUTROOT A.wav B.wav ...`: the same recordings read in blocks of one second, in lock step, and pushed
+// through one bank of live channels (ofdmrx_bank_*); a file that runs out ends its channel.  Every record is written as soon as it
+// is returned: the files and lines of --batch, up to the order of the lines.
 #include "wav_read.h"
 #include <algorithm>
 #include <cstdlib>
@@ -187,13 +190,98 @@ static int run_batch(const std::string &outroot, int n_inputs, char **inputs)
 	return 0;
 }
 
+// every recording of a list block by block, in lock step, through one bank
+static int run_live_batch(const std::string &outroot, int n_inputs, char **inputs)
+{
+	const size_t S = (size_t)n_inputs;
+	std::vector<WavStream> ws(S);
+	for (size_t i = 0; i < S; ++i) {
+		if (!wav_open(inputs[i], ws[i])) {
+			std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", inputs[i]);
+			return 1;
+		}
+		if (ws[i].rate != ws[0].rate || ws[i].channels != ws[0].channels || ws[i].fmt != ws[0].fmt) {
+			std::fprintf(stderr, "\"%s\" and \"%s\" do not share sample rate, channels and sample format: a batch takes recordings of one kind.\n",
+				inputs[0], inputs[i]);
+			return 1;
+		}
+	}
+	const WavStream &w0 = ws[0];
+	if (!supported(w0.channels, w0.rate))
+		return 1;
+	if (S > 65535) {
+		std::fprintf(stderr, "A bank takes at most 65535 recordings.\n");
+		return 1;
+	}
+	ofdmrx_handle *h = create(w0.rate);
+	if (!h)
+		return 1;
+	(void)mkdir(outroot.c_str(), 0777);
+	std::vector<std::string> dirs(S), prefixes(S);
+	for (size_t i = 0; i < S; ++i) {
+		dirs[i] = outroot + "/" + std::to_string(i);
+		prefixes[i] = std::to_string(i) + ":";
+		(void)mkdir(dirs[i].c_str(), 0777);
+	}
+	int r = ofdmrx_bank_begin(h, S, w0.fmt, w0.channels);
+	const size_t block = (size_t)w0.rate, frame_bytes = (w0.fmt == OFDMRX_FMT_S16 ? 2 : w0.fmt == OFDMRX_FMT_U8 ? 1 : 4) * (size_t)w0.channels;
+	const size_t stride = block * frame_bytes, cap = 64;
+	std::vector<uint8_t> all(S * stride), out(cap * OFDMRX_PAYLOAD_BYTES), pcm, ends(S), over(S, 0);
+	std::vector<ofdmrx_frame_result> res(cap);
+	std::vector<int32_t> chan(cap);
+	std::vector<int64_t> index(cap);
+	std::vector<size_t> lens(S), none(S, 0);
+	bool written = true;
+	auto step = [&](bool end) -> int {
+		size_t n_rec = 0, n_left = 0;
+		bool first = true;
+		do {
+			const int rr = end ? ofdmrx_bank_end(h, cap, out.data(), res.data(), chan.data(), index.data(), &n_rec, &n_left)
+				: ofdmrx_bank_push(h, first ? all.data() : nullptr, stride, first ? lens.data() : none.data(), first ? ends.data() : nullptr, cap,
+					out.data(), res.data(), chan.data(), index.data(), &n_rec, &n_left);
+			if (rr)
+				return rr;
+			first = false;
+			for (size_t i = 0; i < n_rec && written; ++i)
+				written = emit_record(dirs[(size_t)chan[i]], (size_t)index[i], res[i], out.data() + i * OFDMRX_PAYLOAD_BYTES, prefixes[(size_t)chan[i]].c_str());
+		} while (n_left && written);
+		return 0;
+	};
+	for (size_t open = S; !r && written && open;) {
+		for (size_t i = 0; i < S; ++i) {
+			lens[i] = 0;
+			ends[i] = 0;
+			if (over[i])
+				continue;
+			lens[i] = wav_read_block(ws[i], block, pcm);
+			std::memcpy(all.data() + i * stride, pcm.data(), lens[i] * frame_bytes);
+			if (lens[i] < block) {                                    // the file has run out: its channel ends behind these samples
+				ends[i] = over[i] = 1;
+				--open;
+			}
+		}
+		r = step(false);
+	}
+	if (!r && written)
+		r = step(true);
+	if (r)
+		std::fprintf(stderr, "ofdmrx_bank: %s\n", ofdmrx_strerror(r));
+	ofdmrx_destroy(h);
+	for (WavStream &w : ws)
+		if (w.f)
+			std::fclose(w.f);
+	return (r || !written) ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
+		return run_live_batch(argv[3], argc - 4, argv + 4);
 	if (argc >= 4 && !std::strcmp(argv[1], "--batch"))
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s --batch OUTROOT INPUT...\n", argv[0], argv[0]);
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n", argv[0], argv[0]);
 		return 1;
 	}
 	const std::string outdir = argv[live ? 2 : 1];

@@ -60,6 +60,7 @@ template <int RATE> struct DifCfg {
                               // workgroups) 3.05
 #endif
 // FB = SourceBatch: frame f is a record of source batch_source(fb, f) (many recordings in one call, kernels.h)
+// FB = WindowBatch: ... of the live channel batch_source(fb, f), read through its window at absolute positions
 template <int RATE, int MONO, class FB = FrameBatch>
 __global__ __launch_bounds__(DifCfg<RATE>::NT, MONO == 2 ? DEMOD_MONO_WAVES : DifCfg<RATE>::WAVES) void k_demod(FB fb, cf *__restrict__ z_all, MonoArgs ma, Tables tb,
 	const SyncState *__restrict__ st_all, cf *__restrict__ cons_all, cf *__restrict__ carr_all)
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(DifCfg<RATE>::NT, MONO == 2 ? DEMOD_MONO_WAVES : Di
 	if (!st.okay)
 		return;
 	const int fs = batch_source(fb, f);
-	SampleSrc src{ (const char *)fb.samples + (size_t)fs * fb.frame_stride_bytes, fb.fmt, fb.channels, batch_len(fb, fs),
+	SampleSrc src{ batch_base(fb, fs), fb.fmt, fb.channels, batch_len(fb, fs),
 		fb.channels == 1 ? z_all + (size_t)f * fb.samples_per_frame : nullptr };
 	const ModeDesc md = mode_desc(st.oper_mode);
 	cf *cons = cons_all + (size_t)f * CONS_MAX;
@@ -441,6 +442,10 @@ bool demod_forms_cons(int rate) { return DEMOD_CONS_OUT(rate); }
 void launch_demod_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, const SyncState *st, cf *cons, cf *carr)
 {
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_demod<RATE, 0, SourceBatch>), dim3(n), dim3(DifCfg<RATE>::NT), 0, s, fb, nullptr, MonoArgs{}, tb, st, cons, carr));
+}
+void launch_demod_bank(hipStream_t s, int rate, int n, WindowBatch fb, Tables tb, const SyncState *st, cf *cons, cf *carr)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_demod<RATE, 0, WindowBatch>), dim3(n), dim3(DifCfg<RATE>::NT), 0, s, fb, nullptr, MonoArgs{}, tb, st, cons, carr));
 }
 void launch_demod(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const MonoArgs &ma, Tables tb, const SyncState *st, cf *cons, cf *carr)
 {

@@ -443,6 +443,7 @@ __device__ __forceinline__ unsigned crc16_u64(unsigned long long data)
                            // search (OSD_NO_CERTIFICATE: 30 ms) does not care
 #endif
 // FB = SourceBatch: frame f is a record of source batch_source(fb, f) (many recordings in one call, kernels.h)
+// FB = WindowBatch: ... of the live channel batch_source(fb, f), read through its window at absolute positions
 template <int RATE, bool MONO, class FB = FrameBatch>
 __global__ __launch_bounds__(256, HDR_WAVES) void k_header(FB fb, cf *__restrict__ z_all, MonoArgs ma, Tables tb,
 	SyncState *__restrict__ st_all, int8_t *__restrict__ hdr_soft, Attempt *__restrict__ attempts, int32_t *__restrict__ attempt_counts)
@@ -465,7 +466,7 @@ __global__ __launch_bounds__(256, HDR_WAVES) void k_header(FB fb, cf *__restrict
 		return;
 	}
 	const int fs = batch_source(fb, f);
-	SampleSrc src{ (const char *)fb.samples + (size_t)fs * fb.frame_stride_bytes, fb.fmt, fb.channels, batch_len(fb, fs),
+	SampleSrc src{ batch_base(fb, fs), fb.fmt, fb.channels, batch_len(fb, fs),
 		fb.channels == 1 ? z_all + (size_t)f * fb.samples_per_frame : nullptr };
 	const long body = st.sc_start + SYM_STRIDE;               // decode.cc:405
 	if constexpr (MONO) {                                     // the symbol's analytic signal first (mono_front.h; its LDS is buf's)
@@ -566,6 +567,10 @@ void launch_header(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const M
 void launch_header_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, SyncState *st, int8_t *hdr_soft)
 {
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_header<RATE, false, SourceBatch>), dim3(n), dim3(256), 0, s, fb, nullptr, MonoArgs{}, tb, st, hdr_soft, nullptr, nullptr));
+}
+void launch_header_bank(hipStream_t s, int rate, int n, WindowBatch fb, Tables tb, SyncState *st, int8_t *hdr_soft)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_header<RATE, false, WindowBatch>), dim3(n), dim3(256), 0, s, fb, nullptr, MonoArgs{}, tb, st, hdr_soft, nullptr, nullptr));
 }
 void launch_osd_only(hipStream_t s, int n, Tables tb, const int8_t *soft, uint8_t *hard, int32_t *unique)
 {

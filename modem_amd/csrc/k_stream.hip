@@ -23,6 +23,7 @@
 namespace rx {
 
 template <class FB> constexpr bool many_v = std::is_same<FB, SourceBatch>::value;
+template <class FB> constexpr bool bank_v = std::is_same<FB, WindowBatch>::value;   // many live channels
 
 // inclusive Hillis-Steele scan over NT threads in LDS (sh: NT entries); returns this thread's inclusive value, sh holds them all
 // afterwards (the caller synchronises before reusing sh)
@@ -69,6 +70,18 @@ __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *_
 		tile_in += fb.tile0[q];
 		ck += (size_t)q * ck_n;
 		ck_n = (int)((fr.n + MONO_CK - 1) / MONO_CK);               // (mono_ck_per_frame)
+	}
+	if constexpr (bank_v<FB>) {                                   // WIN, channel blockIdx.y: its window, its tiles from where its DC blocker stands
+		static_assert(WIN, "a bank reads windows");
+		const int q = blockIdx.y;
+		if ((long long)t >= fb.dc_at[q + 1] - fb.dc_at[q])          // (uniform)
+			return;
+		fr.base = batch_base(fb, q);
+		fr.n = (long)fb.len[q];
+		tile_end += fb.dc_at[q];
+		tile_in += fb.dc_at[q];
+		ck = (double *)((char *)ck + fb.ck_org[q]);
+		origin = (long)fb.dc_from[q];
 	}
 	__shared__ Affine sh[256];
 	const double a = (double)co.dc_a, g = (double)co.dc_b * (1.0 - a) * (double)fr.scale();
@@ -142,6 +155,35 @@ __global__ __launch_bounds__(1024) void k_sdcs_scan(FrontCoef co, const double *
 	}
 }
 
+// Many live channels: one workgroup per channel runs k_sdc_scan<true> on the tiles that channel brings in this push - the same
+// ranges per thread, the same order of composition as a single feed with that channel's push lengths, so the same doubles - from
+// the state kept before the channel's first tile.  (A kernel of its own, as k_sdcs_scan is.)
+__global__ __launch_bounds__(1024) void k_bank_sdc_scan(WindowBatch fb, FrontCoef co, const double *__restrict__ tile_end_all, double *__restrict__ tile_in_all,
+	const double *__restrict__ ck_all)
+{
+	const int tid = threadIdx.x, q = blockIdx.x;
+	__shared__ Affine sh[1024];
+	const long ntiles = (long)(fb.dc_at[q + 1] - fb.dc_at[q]);
+	if (ntiles == 0)                                              // (uniform)
+		return;
+	const double *__restrict__ tile_end = tile_end_all + fb.dc_at[q];
+	double *__restrict__ tile_in = tile_in_all + fb.dc_at[q];
+	const double *ck = (const double *)((const char *)ck_all + fb.ck_org[q]);
+	const double *entry = fb.dc_from[q] > 0 ? ck + fb.dc_from[q] / MONO_CK - 1 : nullptr;
+	const double A = mono_pow((double)co.dc_a, 4096);
+	const long per = (ntiles + 1023) / 1024, k0 = (long)tid * per, k1 = k0 + per < ntiles ? k0 + per : ntiles;
+	Affine f{ 0.0, 1.0 };
+	for (long k = k0; k < k1; ++k)
+		f = aff_then(f, Affine{ tile_end[k], A });
+	block_scan_incl<1024>(f, sh, tid, aff_then);
+	const double c0 = entry ? *entry : 0.0;
+	double c = tid ? sh[tid - 1].v + sh[tid - 1].w * c0 : c0;
+	for (long k = k0; k < k1; ++k) {
+		tile_in[k] = c;
+		c = tile_end[k] + A * c;
+	}
+}
+
 void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck)
 {
 	const long ntiles = (fb.samples_per_frame + 4095) / 4096;
@@ -164,6 +206,14 @@ void launch_stream_dc_window(hipStream_t s, FrameBatch fb, FrontCoef co, double 
 	hipLaunchKernelGGL((k_sdc_tile<0, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, origin);
 	hipLaunchKernelGGL(k_sdc_scan<true>, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles, entry);
 	hipLaunchKernelGGL((k_sdc_tile<1, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, origin);
+}
+
+void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck)
+{
+	const dim3 grid((unsigned)max_tiles, (unsigned)n_ch);
+	hipLaunchKernelGGL((k_sdc_tile<0, true, WindowBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, 0L);
+	hipLaunchKernelGGL(k_bank_sdc_scan, dim3((unsigned)n_ch), dim3(1024), 0, s, fb, co, tile_end, tile_in, ck);
+	hipLaunchKernelGGL((k_sdc_tile<1, true, WindowBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, 0L);
 }
 
 // ---------------------------------------------------------------- the trigger as a scan
@@ -242,6 +292,7 @@ __device__ __forceinline__ void tile_trigger(TrigShared &sh, const int (&cls)[SP
 // edge positions count from the push's first edge (the carry that enters a push has count 0)
 // FB = SourceBatch: tile blockIdx.x of recording blockIdx.y, read from that recording's base with its length (n is unused): a position
 // below 0 or at or past the length reads as zero, exactly as in a call with that recording alone; edges is [recordings][cap]
+// FB = WindowBatch (with WIN): tile fb.tile0[q] + blockIdx.x of the live channel q = blockIdx.y (n and tile0 are unused); edges is [channels][cap]
 template <int RATE, bool GIVEN, bool EMIT, bool WIN = false, class FB = FrameBatch>
 __global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
 	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap, long long tile0 = 0)
@@ -258,6 +309,18 @@ __global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restr
 		edges += (size_t)q * cap;
 		if constexpr (GIVEN)
 			given += fb.given0[q];
+	}
+	if constexpr (bank_v<FB>) {                                   // WIN, channel blockIdx.y: its window, its tiles of this push, its places
+		static_assert(WIN && !GIVEN, "a bank scans windows of sample streams");
+		const int q = blockIdx.y;
+		if ((long long)blockIdx.x >= fb.tile_at[q + 1] - fb.tile_at[q])   // (uniform: this channel brings fewer tiles)
+			return;
+		n = (long)fb.len[q];
+		samples = batch_base(fb, q);
+		tile0 = fb.tile0[q];
+		fn += fb.tile_at[q];
+		carry += fb.tile_at[q];
+		edges += (size_t)q * cap;
 	}
 	typedef RateCfg<RATE> RC;
 	constexpr int HS = RC::HS, GL = RC::GL, ML = RC::MATCH_LEN, MD = RC::MATCH_DEL;
@@ -495,6 +558,22 @@ __global__ __launch_bounds__(1024) void k_streams_fn_scan(const StreamFn *__rest
 	fn_scan_wg<false>(fn + t0, (long)(tile0[blockIdx.x + 1] - t0), carry + t0, counts + 2 * (size_t)blockIdx.x, nullptr, nullptr);
 }
 
+// The segmented windowed scan: one workgroup per live channel composes the tiles that channel brings in this push, from the carry
+// that channel's last push left, and leaves the carry for its next one.  A channel without tiles keeps its carry.
+// counts: [channels][2], cleared by the caller
+__global__ __launch_bounds__(1024) void k_bank_fn_scan(const StreamFn *__restrict__ fn, const long long *__restrict__ tile_at, StreamCarry *__restrict__ carry,
+	long long *__restrict__ counts, const StreamCarry *__restrict__ c_in, StreamCarry *__restrict__ c_out)
+{
+	const long long t0 = tile_at[blockIdx.x];
+	const long nt = (long)(tile_at[blockIdx.x + 1] - t0);
+	if (nt == 0) {                                                // (uniform)
+		if (threadIdx.x == 0)
+			c_out[blockIdx.x] = c_in[blockIdx.x];
+		return;
+	}
+	fn_scan_wg<true>(fn + t0, nt, carry + t0, counts + 2 * (size_t)blockIdx.x, c_in + blockIdx.x, c_out + blockIdx.x);
+}
+
 void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
 	StreamEdge *edges, long cap, long long *counts)
 {
@@ -537,6 +616,15 @@ void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, l
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, nullptr, n, fn, carry, edges, cap, tile0));
 }
 
+void launch_bank_scan(hipStream_t s, int rate, int n_ch, long max_tiles, WindowBatch fb, StreamFn *fn, StreamCarry *carry, const StreamCarry *c_in,
+	StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts)
+{
+	const dim3 grid((unsigned)max_tiles, (unsigned)n_ch);
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, true, WindowBatch>), grid, dim3(256), 0, s, fb, nullptr, 0L, fn, carry, edges, cap, 0LL));
+	hipLaunchKernelGGL(k_bank_fn_scan, dim3((unsigned)n_ch), dim3(1024), 0, s, fn, fb.tile_at, carry, counts, c_in, c_out);
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, true, WindowBatch>), grid, dim3(256), 0, s, fb, nullptr, 0L, fn, carry, edges, cap, 0LL));
+}
+
 // ---------------------------------------------------------------- accept, records
 constexpr int ACCEPT_GRID = 2048;
 // WIN (the live feed): fb.samples is the address position 0 would have and only the positions from win_lo on are in memory.  The host
@@ -554,6 +642,15 @@ __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restri
 		n_src = fb.src_len[q];
 		edges += (size_t)q * cap;
 		counts += 2 * (size_t)q;
+	}
+	if constexpr (bank_v<FB>) {                                   // the edges of the live channel blockIdx.y, read through its window
+		static_assert(WIN, "a bank reads windows");
+		const int q = blockIdx.y;
+		samples = batch_base(fb, q);
+		n_src = (long)fb.len[q];
+		edges += (size_t)q * cap;
+		counts += 2 * (size_t)q;
+		win_lo = fb.lo[q];
 	}
 	typedef RateCfg<RATE> RC;
 	constexpr int BUFFER_LEN = RC::BUFFER_LEN, SEARCH_POS = RC::SEARCH_POS, HALF_LEN = RC::HS, MATCH_DEL = RC::MATCH_DEL, NT = 256;
@@ -573,8 +670,12 @@ __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restri
 			const long long lo_p = ed.t_max - MATCH_DEL - (BUFFER_LEN - 1 - (SEARCH_POS + HALF_LEN)) - (HALF_LEN - 1);
 			const long long lo_w = ed.g - (BUFFER_LEN - 1) + (SEARCH_POS - ed.index_max) + HALF_LEN;
 			if (win_lo > 0 && (lo_p < win_lo || lo_w < win_lo)) {     // (uniform)
-				if (tid == 0)
-					counts[2] = 1;
+				if (tid == 0) {
+					if constexpr (bank_v<FB>)
+						fb.below[blockIdx.y] = 1;
+					else
+						counts[2] = 1;
+				}
 				continue;
 			}
 		}
@@ -628,6 +729,14 @@ void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables 
 {
 	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, true>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, win_lo));
+}
+
+void launch_bank_accept(hipStream_t s, int rate, int n_ch, WindowBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
+{
+	long per = ACCEPT_GRID / n_ch < cap ? ACCEPT_GRID / n_ch : cap;
+	per = per > 0 ? per : 1;
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, true, WindowBatch>), dim3((unsigned)per, (unsigned)n_ch), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
+		edges, cap, counts, 0LL));
 }
 
 // rec_src (nullable) / src: the recording every record written reads (many recordings in one call)
@@ -724,6 +833,17 @@ __global__ __launch_bounds__(1024) void k_streams_records(int buffer_len, const 
 	stream_records_wg(buffer_len, edges + (size_t)q * cap, cap, counts + 2 * (size_t)q, rec + at, (long)room, 0, 0, rec_src + at, q);
 }
 
+// Many live channels: as k_streams_records, but record indices and rejects go on from what the channel's earlier pushes counted
+__global__ __launch_bounds__(1024) void k_bank_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
+	const long long *__restrict__ first, SyncState *__restrict__ rec, int *__restrict__ rec_src, const long long *__restrict__ rec_base,
+	const long long *__restrict__ rej_base, long long max_rec)
+{
+	const int q = blockIdx.x;
+	const long long at = first[q];
+	const long long room = max_rec > at ? max_rec - at : 0;       // only the first max_rec of the packed order are written
+	stream_records_wg(buffer_len, edges + (size_t)q * cap, cap, counts + 2 * (size_t)q, rec + at, (long)room, rec_base[q], rej_base[q], rec_src + at, q);
+}
+
 void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec,
 	long long rec_base, long long rej_base)
 {
@@ -739,6 +859,51 @@ void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge
 	hipLaunchKernelGGL(k_streams_count, dim3((unsigned)n_src), dim3(1024), 0, s, edges, cap, counts);
 	hipLaunchKernelGGL(k_streams_first, dim3(1), dim3(1024), 0, s, n_src, counts, max_per_src, first);
 	hipLaunchKernelGGL(k_streams_records, dim3((unsigned)n_src), dim3(1024), 0, s, buffer_len, edges, cap, counts, first, rec, rec_src, max_per_src, max_rec);
+}
+
+void launch_bank_records(hipStream_t s, int rate, int n_ch, const StreamEdge *edges, long cap, long long *counts, long long *first, SyncState *rec,
+	int *rec_src, const long long *rec_base, const long long *rej_base, long long max_rec)
+{
+	int buffer_len = 0;
+	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
+	hipLaunchKernelGGL(k_streams_count, dim3((unsigned)n_ch), dim3(1024), 0, s, edges, cap, counts);
+	hipLaunchKernelGGL(k_streams_first, dim3(1), dim3(1024), 0, s, n_ch, counts, (long long)1 << 62, first);
+	hipLaunchKernelGGL(k_bank_records, dim3((unsigned)n_ch), dim3(1024), 0, s, buffer_len, edges, cap, counts, first, rec, rec_src, rec_base, rej_base, max_rec);
+}
+
+// ---------------------------------------------------------------- the window move / the new samples of every channel
+// Range blockIdx.z * plane_stride + blockIdx.y (the planes: raw samples, analytic signal, DC states), given by address: whole waves
+// on 16-byte pieces from the first 16-byte boundary of the destination on (the source lies the same modulo 16), the bytes before it
+// and behind the last whole piece one by one.  Plain vector loads and stores.
+__global__ __launch_bounds__(256) void k_bank_copy(const long long *__restrict__ src, const long long *__restrict__ dst, const long long *__restrict__ bytes,
+	size_t plane_stride)
+{
+	const size_t q = (size_t)blockIdx.z * plane_stride + blockIdx.y;
+	const long long nb = bytes[q];
+	if (nb <= 0)
+		return;
+	const char *__restrict__ sp = (const char *)(uintptr_t)src[q];
+	char *__restrict__ dp = (char *)(uintptr_t)dst[q];
+	long long head = (long long)((16 - ((size_t)dp & 15)) & 15);
+	head = head < nb ? head : nb;
+	const long long pieces = (nb - head) / 16, tail0 = head + pieces * 16;
+	const long long t = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+	const uint4 *s4 = (const uint4 *)(sp + head);
+	uint4 *d4 = (uint4 *)(dp + head);
+	for (long long i = t; i < pieces; i += step)
+		d4[i] = s4[i];
+	if (t < head)
+		dp[t] = sp[t];
+	if (t < nb - tail0)
+		dp[tail0 + t] = sp[tail0 + t];
+}
+void launch_bank_copy(hipStream_t s, int n_ch, int planes, size_t plane_stride, long long max_bytes, const long long *src, const long long *dst,
+	const long long *bytes)
+{
+	// (16 pieces per thread where a range is long; never more blocks than the longest range has use for)
+	long long bx = (max_bytes / 16 + 256 * 16 - 1) / (256 * 16);
+	bx = bx < 1 ? 1 : bx > 4096 ? 4096 : bx;
+	hipLaunchKernelGGL(k_bank_copy, dim3((unsigned)bx, (unsigned)n_ch, (unsigned)planes), dim3(256), 0, s, src, dst, bytes, plane_stride);
 }
 
 }  // namespace rx

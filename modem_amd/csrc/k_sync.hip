@@ -113,19 +113,25 @@ __global__ __launch_bounds__(256) void k_mono_carries(FrameBatch fb, FrontCoef c
 constexpr int FE_STRETCH = 4 * 2048 - 256;
 // WIN (the live feed, one frame): block b is stretch stretch0 + b; fb.samples, ma.ck and z_all are the addresses position 0 would have
 // FB = SourceBatch (many recordings in one call): frame f is source f with its own length; the grid covers the longest one
+// FB = WindowBatch (with WIN; many live channels): block b of channel f = blockIdx.y is that channel's stretch fb.fe0[f] + b
 template <int RATE, bool WIN = false, class FB = FrameBatch>
 __global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FB fb, MonoArgs ma, cf *__restrict__ z_all, long stretch0 = 0)
 {
 	static_assert(MonoCfg<RATE>::REACH + MONO_CK <= 256, "a stretch and its lead-in fit four spans");
 	const int f = blockIdx.y, tid = threadIdx.x;
+	if constexpr (std::is_same<FB, WindowBatch>::value)
+		stretch0 = (long)fb.fe0[blockIdx.y];
 	const long lo = ((long)blockIdx.x + (WIN ? stretch0 : 0)) * FE_STRETCH;
 	__shared__ typename MonoCover<RATE, 256>::Shared msh;
 	MonoCover<RATE, 256> mc;
-	if constexpr (!std::is_same<FB, FrameBatch>::value) {
+	if constexpr (std::is_same<FB, SourceBatch>::value) {
 		if (lo >= fb.src_len[f])
 			return;
 	}
-	mc.init(mono_frame(fb, ma.ck, ma.ck_per_frame, f), ma, &msh, z_all + (size_t)f * fb.samples_per_frame, tid);
+	if constexpr (std::is_same<FB, WindowBatch>::value)           // (uniform: channel f forms fewer stretches in this push)
+		if ((long long)blockIdx.x >= fb.fe_at[f + 1] - fb.fe_at[f])
+			return;
+	mc.init(mono_frame(fb, ma.ck, ma.ck_per_frame, f), ma, &msh, mono_z(fb, z_all, f), tid);
 	mc.hi = lo + FE_STRETCH < mc.fr.n ? lo + FE_STRETCH : mc.fr.n;   // (cover() runs whole spans: they reach into the next workgroup's stretch)
 	mc.cover(ma, lo, lo + FE_STRETCH, tid);
 }
@@ -599,6 +605,10 @@ long front_end_stretch() { return FE_STRETCH; }
 void launch_front_end_window(hipStream_t s, int rate, FrameBatch fb, MonoArgs ma, cf *z, long stretch0, long n_stretch)
 {
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, true>), dim3((unsigned)n_stretch, 1), dim3(256), 0, s, fb, ma, z, stretch0));
+}
+void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z)
+{
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, true, WindowBatch>), dim3((unsigned)max_stretch, (unsigned)n_ch), dim3(256), 0, s, fb, ma, z, 0L));
 }
 #define SYNC_SPLIT_ROUNDS 2   // rates above 8 kHz: scan + accept pairs before the one-wave catch-all (a frame needs the catch-all only
                               // after that many rejected triggers; finished frames leave every later launch at once)

@@ -24,10 +24,32 @@ struct SourceBatch : FrameBatch {
 	const long long *tile0;        // the stream scan: [sources + 1] first tile of every source in the per-tile arrays (a running sum)
 	const long long *given0;       // ofdmrx_debug_streams_edges: [sources] where its sequence starts in the packed timing values
 };
+// Many live channels in one push (ofdmrx_bank_*): channel q is a WINDOW of its stream.  Position 0 of channel q would
+// lie at samples + org[q] (bytes; the channel's place in the slab minus its window's base, so it may be negative), the channel has
+// been fed len[q] sample frames and its window holds the positions from lo[q] on.  The scan of a push takes the tiles tile0[q] ..
+// of channel q, tile_at[q + 1] - tile_at[q] of them, at tile_at[q] in the per-tile arrays.  Frame f of a record launch reads
+// channel src_of[f].  Positions are 64-bit throughout.
+struct WindowBatch : FrameBatch {
+	const int *src_of;             // [frames of the launch], nullable
+	const long long *org;          // [channels]
+	const long long *len;          // [channels]
+	const long long *lo;           // [channels]
+	const long long *tile0;        // [channels]
+	const long long *tile_at;      // [channels + 1]
+	long long *below;              // [channels] k_stream_accept: set when an edge of the channel would read below lo[q]
+	// mono input: the analytic signal and the DC blocker's kept states, as org for the raw samples (bytes from z / ck of the launch);
+	// dc_from: the DC blocker resumes at that position (a multiple of MONO_CK), fe0: first stretch the front end forms, fe_at: running sum
+	const long long *z_org, *ck_org, *dc_from, *dc_at, *fe0, *fe_at;
+};
 __host__ __device__ inline int batch_source(const FrameBatch &, int f) { return f; }
 __host__ __device__ inline long batch_len(const FrameBatch &fb, int) { return fb.samples_per_frame; }
 __host__ __device__ inline int batch_source(const SourceBatch &fb, int f) { return fb.src_of ? fb.src_of[f] : f; }
 __host__ __device__ inline long batch_len(const SourceBatch &fb, int q) { return fb.src_len[q]; }
+__host__ __device__ inline int batch_source(const WindowBatch &fb, int f) { return fb.src_of ? fb.src_of[f] : f; }
+__host__ __device__ inline long batch_len(const WindowBatch &fb, int q) { return (long)fb.len[q]; }
+// where source q's position 0 lies
+__host__ __device__ inline const char *batch_base(const FrameBatch &fb, int q) { return (const char *)fb.samples + (size_t)q * fb.frame_stride_bytes; }
+__host__ __device__ inline const char *batch_base(const WindowBatch &fb, int q) { return (const char *)fb.samples + fb.org[q]; }
 
 struct FrontCoef {                 // BlockDC::samples(2*(symbol_len+guard_len)) + Hilbert<cmplx,filter_len> (decode.cc:386,193)
 	float dc_a, dc_b;
@@ -195,6 +217,9 @@ void launch_demod(hipStream_t s, int rate, int n, FrameBatch fb, cf *z, const Mo
 // the same two for records of many recordings (2-channel sources: mono input has been through launch_streams_front)
 void launch_header_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, SyncState *st, int8_t *hdr_soft);
 void launch_demod_sources(hipStream_t s, int rate, int n, SourceBatch fb, Tables tb, const SyncState *st, cf *cons, cf *carr);
+// ... and of many live channels (ofdmrx_bank_*): record f reads channel fb.src_of[f]'s window at its 64-bit absolute sc_start
+void launch_header_bank(hipStream_t s, int rate, int n, WindowBatch fb, Tables tb, SyncState *st, int8_t *hdr_soft);
+void launch_demod_bank(hipStream_t s, int rate, int n, WindowBatch fb, Tables tb, const SyncState *st, cf *cons, cf *carr);
 void launch_theil_sen(hipStream_t s, int n, const SyncState *st, cf *cons, const cf *carr, float *slope, float *yint, int *chunk_flags);
 void launch_theil_sen_raw(hipStream_t s, int rows, int cols, const float *y, float *slope, float *yint);
 // D5's rotation + D6-D8 + the syndrome certificate (k_finish.hip: k_back).  cert_mode 0: every frame with a header goes to the list
@@ -298,5 +323,27 @@ void launch_streams_accept(hipStream_t s, int rate, int n_src, SourceBatch fb, T
 // rec / rec_src: the SyncState of every packed record below max_rec and the recording it reads
 void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge *edges, long cap, long long *counts, long long *first,
 	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec);
+
+
+// ---- many live channels in one push (api_bank.cpp): the window forms with the channel as the second grid dimension.
+// Every array is per channel: edges [n_ch][cap], counts [n_ch][2], c_in / c_out [n_ch] (a channel without tiles in this push keeps
+// its carry).  max_tiles: the most tiles any channel brings (the grids' first dimension).  The caller clears counts and fb.below
+void launch_bank_scan(hipStream_t s, int rate, int n_ch, long max_tiles, WindowBatch fb, StreamFn *fn, StreamCarry *carry, const StreamCarry *c_in,
+	StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts);
+void launch_bank_accept(hipStream_t s, int rate, int n_ch, WindowBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
+// the packed records of the push in channel order: first [n_ch + 1] as launch_streams_records; record indices count from rec_base[q],
+// rejects from rej_base[q]; only the first max_rec are written
+void launch_bank_records(hipStream_t s, int rate, int n_ch, const StreamEdge *edges, long cap, long long *counts, long long *first, SyncState *rec,
+	int *rec_src, const long long *rec_base, const long long *rej_base, long long max_rec);
+// planes x n_ch byte ranges copied in one launch: range (p, q), at index p * plane_stride + q of the three arrays, is bytes[] bytes
+// from the address src[] to the address dst[], which are the same modulo 16 (the window move: both multiples of 16; the new
+// samples: packed that way by the host).  max_bytes: the longest range
+void launch_bank_copy(hipStream_t s, int n_ch, int planes, size_t plane_stride, long long max_bytes, const long long *src, const long long *dst,
+	const long long *bytes);
+// mono input: the window forms of the DC blocker and the front end with the channel as the second grid dimension.  Channel q's DC
+// blocker resumes at fb.dc_from[q] with fb.dc_at[q + 1] - fb.dc_at[q] tiles (tile_end / tile_in: at fb.dc_at[q]); its front end forms
+// the stretches fb.fe0[q] .. , fb.fe_at[q + 1] - fb.fe_at[q] of them.  ck, z (ma.ck likewise): the slabs fb.ck_org / fb.z_org count from
+void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
+void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z);
 
 }  // namespace rx

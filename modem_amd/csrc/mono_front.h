@@ -95,6 +95,14 @@ __device__ __forceinline__ MonoFrame mono_frame(const SourceBatch &fb, const dou
 {
 	return MonoFrame{ (const char *)fb.samples + (size_t)f * fb.frame_stride_bytes, fb.fmt, fb.src_len[f], ck_all + (size_t)f * ck_per_frame };
 }
+// (live channel f through its window: the addresses position 0 / state 0 would have, the samples fed so far)
+__device__ __forceinline__ MonoFrame mono_frame(const WindowBatch &fb, const double *ck_all, int, int f)
+{
+	return MonoFrame{ batch_base(fb, f), fb.fmt, (long)fb.len[f], (const double *)((const char *)ck_all + fb.ck_org[f]) };
+}
+// where frame f's analytic signal begins in z_all
+__device__ __forceinline__ cf *mono_z(const FrameBatch &fb, cf *z_all, int f) { return z_all + (size_t)f * fb.samples_per_frame; }
+__device__ __forceinline__ cf *mono_z(const WindowBatch &fb, cf *z_all, int f) { return (cf *)((char *)z_all + fb.z_org[f]); }
 __device__ __forceinline__ double mono_pow(double a, int e)   // a^e, e >= 0
 {
 	double pw = 1.0, bs = a;

@@ -27,6 +27,8 @@ EXPORTS = [
     "ofdmrx_callsign_value", "ofdmrx_decode_stream", "ofdmrx_decode_stream_device", "ofdmrx_debug_stream_edges",
     "ofdmrx_feed_begin", "ofdmrx_feed_push", "ofdmrx_feed_end", "ofdmrx_feed_lag", "ofdmrx_feed_resident_samples",
     "ofdmrx_decode_streams", "ofdmrx_decode_streams_device", "ofdmrx_debug_streams_edges",
+    "ofdmrx_bank_begin", "ofdmrx_bank_push", "ofdmrx_bank_end", "ofdmrx_bank_resident_samples", "ofdmrx_bank_preambles",
+    "ofdmrx_bank_last_stage_ops",
 ]
 
 
@@ -129,6 +131,16 @@ def load_library():
     L.ofdmrx_feed_lag.restype = C.c_longlong
     L.ofdmrx_feed_resident_samples.argtypes = [C.c_void_p]
     L.ofdmrx_feed_resident_samples.restype = C.c_longlong
+    L.ofdmrx_bank_begin.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+    L.ofdmrx_bank_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ofdmrx_bank_end.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
+                                  C.POINTER(C.c_size_t)]
+    for f in (L.ofdmrx_bank_resident_samples, L.ofdmrx_bank_preambles):
+        f.argtypes = [C.c_void_p, C.c_size_t]
+        f.restype = C.c_longlong
+    L.ofdmrx_bank_last_stage_ops.argtypes = [C.c_void_p]
+    L.ofdmrx_bank_last_stage_ops.restype = C.c_longlong
     L.ofdmrx_synchronize.argtypes = [C.c_void_p]
     L.ofdmrx_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.ofdmrx_chunk_frames.argtypes = [C.c_void_p]
@@ -282,6 +294,10 @@ class Receiver:
     def feed(self, channels, dtype=np.int16, esn0_rows=False):
         """open a live feed of `channels` interleaved values of dtype: push blocks as they arrive, take each record when it is due"""
         return Feed(self, channels, dtype, esn0_rows)
+
+    def bank(self, n_channels, channels, dtype=np.int16, esn0_rows=False):
+        """open a bank of n_channels live channels of `channels` interleaved values of dtype: push one block per channel per call"""
+        return Bank(self, n_channels, channels, dtype, esn0_rows)
 
     def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
         """device pointers (ints), or pinned host outputs; -> n_preambles (the call synchronises once, after the scan)"""
@@ -554,6 +570,103 @@ class Feed:
     def end(self, max_frames=None):
         """the stream is over -> the remaining records; the feed is closed once nothing is left"""
         return self._call(self._end, max_frames, ending=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        while self.open:
+            self.end()
+        return False
+
+
+class Bank:
+    """Many live channels pushed and decoded in one call (ofdmrx_bank_*): push(blocks) takes one block per channel and returns the
+    records that have become due on any of them, end() the rest.  The records of channel c over all calls are what a Feed of that
+    channel alone returns.  One bank per Receiver at a time, never beside a feed; a context manager ends a bank that was not ended."""
+
+    def __init__(self, rx, n_channels, channels, dtype=np.int16, esn0_rows=False):
+        self._rx, self._lib, self._h = rx, rx._lib, rx._h
+        self.n_channels, self.channels, self.dtype, self._rows = int(n_channels), int(channels), np.dtype(dtype), bool(esn0_rows)
+        rx._check(self._lib.ofdmrx_bank_begin(self._h, self.n_channels, rx._fmt(self.dtype), self.channels))
+        self.open = True
+        self.n_left = 0
+        self._ops = 0
+
+    def resident_samples(self, c):
+        return int(self._lib.ofdmrx_bank_resident_samples(self._h, int(c)))
+
+    def preambles(self, c):
+        return int(self._lib.ofdmrx_bank_preambles(self._h, int(c)))
+
+    @property
+    def last_stage_ops(self):
+        """launches + copies + synchronisations the bank's own stages enqueued in the last push / end (not the record pipeline's, and not
+        those of the further calls that only drain staged records)"""
+        return self._ops
+
+    def _call(self, f, max_records, ending=False):
+        """f(first, cap, payload, results, channel, index, n_records, n_left) until nothing is left (max_records None) or once"""
+        pays, ress, chans, idxs, rows = [], [], [], [], []
+        cap = 16 if max_records is None else int(max_records)
+        first = True
+        while first or (max_records is None and self.n_left > 0 and self.open):
+            out = np.zeros((max(cap, 1), PAYLOAD_BYTES), np.uint8)
+            res = np.zeros(max(cap, 1), RESULT_DTYPE)
+            ch = np.zeros(max(cap, 1), np.int32)
+            ix = np.zeros(max(cap, 1), np.int64)
+            rw = np.zeros((max(cap, 1), 126), np.float32) if self._rows else None
+            nrec, nleft = C.c_size_t(0), C.c_size_t(0)
+            if self._rows:
+                self._rx._check(self._lib.ofdmrx_set_esn0_rows(self._h, _ptr(rw)))
+            try:
+                self._rx._check(f(first, cap, _ptr(out) if cap else None, _ptr(res) if cap else None, _ptr(ch) if cap else None,
+                                  _ptr(ix) if cap else None, C.byref(nrec), C.byref(nleft)))
+            finally:
+                if self._rows:
+                    self._lib.ofdmrx_set_esn0_rows(self._h, None)
+            if first and not (ending and nleft.value == 0):       # (an end call that leaves nothing has closed the bank)
+                self._ops = int(self._lib.ofdmrx_bank_last_stage_ops(self._h))
+            first = False
+            self.n_left = nleft.value
+            pays.append(out[:nrec.value])
+            ress.append(res[:nrec.value])
+            chans.append(ch[:nrec.value])
+            idxs.append(ix[:nrec.value])
+            if self._rows:
+                rows.append(rw[:nrec.value])
+            if ending and nleft.value == 0:
+                self.open = False
+        ret = (np.concatenate(pays), np.concatenate(ress), np.concatenate(chans), np.concatenate(idxs))
+        return ret + ((np.concatenate(rows),) if self._rows else ())
+
+    def push(self, blocks, ends=None, max_records=None):
+        """one block [k, channels] (or [k] mono) per channel - None or an empty array: no samples for that channel; ends (nullable):
+        per channel, true = its stream is over after this block -> (payloads, results, record_channel, record_index[, esn0 rows])"""
+        if len(blocks) != self.n_channels:
+            raise ValueError("one block per channel")
+        arrs = [np.zeros((0, self.channels), self.dtype) if b is None else np.ascontiguousarray(b, dtype=self.dtype).reshape(-1, self.channels)
+                for b in blocks]
+        lens = np.array([a.shape[0] for a in arrs], dtype=np.uintp)
+        longest = int(lens.max())
+        buf = np.zeros((self.n_channels, max(longest, 1), self.channels), self.dtype)
+        for c, a in enumerate(arrs):
+            buf[c, :a.shape[0]] = a
+        zero = np.zeros(self.n_channels, dtype=np.uintp)
+        e = None if ends is None else np.ascontiguousarray(np.asarray(ends) != 0, dtype=np.uint8)
+        if e is not None and e.shape != (self.n_channels,):
+            raise ValueError("one end flag per channel")
+        stride = buf.strides[0]
+        return self._call(lambda first, cap, o, r, ch, ix, a, b: self._lib.ofdmrx_bank_push(
+            self._h, _ptr(buf) if longest and first else None, stride, _ptr(lens if first else zero), _ptr(e) if e is not None and first else None,
+            cap, o, r, ch, ix, a, b), max_records)
+
+    def _end(self, first, cap, o, r, ch, ix, a, b):
+        return self._lib.ofdmrx_bank_end(self._h, cap, o, r, ch, ix, a, b)
+
+    def end(self, max_records=None):
+        """every channel still open ends -> the remaining records; the bank is closed once nothing is left"""
+        return self._call(self._end, max_records, ending=True)
 
     def __enter__(self):
         return self

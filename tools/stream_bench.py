@@ -14,6 +14,12 @@ synchronises with the host, so the feed is the slower per sample; records and pa
 --batched: instead, the --streams recordings (a) through a loop of ofdmrx_decode_stream_device, one call per recording, and (b) through
 ONE ofdmrx_decode_streams_device call, alternating step by step: records/s and samples/s of both with the median and the range over the
 steps, and their ratio.  The records of (a) and (b) are checked to be the same bytes.
+
+--bank N BLOCK: N live channels of the same --count payload recording behind staggered leading silence, pushed BLOCK samples per channel
+per round through ONE bank (ofdmrx_bank_*), against (a) the only way without it: N handles (chunk_frames 4), each with its own feed,
+pushed in a loop (--feeds-cap M: only the first M channels, when N handles do not fit; reported as measured, never scaled), and (b) one
+ofdmrx_decode_streams call over the complete recordings - the floor: it has no liveness.  Wall time per round, records/s, the ratios;
+every channel's records are checked against (b).
 """
 import argparse
 import ctypes as C
@@ -39,6 +45,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--feed", type=int, default=0, metavar="BLOCK", help="the same recording through the live feed in pushes of BLOCK samples")
     ap.add_argument("--batched", action="store_true", help="a loop of one-call decodes over the recordings against one ofdmrx_decode_streams_device call")
+    ap.add_argument("--bank", type=int, nargs=2, default=None, metavar=("N", "BLOCK"), help="N live channels through one bank, BLOCK samples per channel per round")
+    ap.add_argument("--feeds-cap", type=int, default=0, help="--bank: baseline (a) on the first M channels only (0: all N)")
     a = ap.parse_args()
     import torch
     import modem_amd
@@ -65,6 +73,8 @@ def main():
     del clean
     if a.feed:
         return feed_bench(a, rx, pcm[0].cpu().numpy(), pay[0].cpu().numpy())
+    if a.bank:
+        return bank_bench(a, rx, pcm[0].cpu().numpy(), pay[0].cpu().numpy())
     out = torch.zeros((S, K, 5380), dtype=torch.uint8, device=dev)
     res = torch.zeros((S, K, M.RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
 
@@ -245,6 +255,103 @@ def feed_bench(a, rx, pcm, pay):
     if a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
+    rx.close()
+
+
+def bank_bench(a, rx, pcm, pay):
+    """N live channels of one recording behind staggered silence: one bank against N feeds in a loop and against one decode_streams call"""
+    import modem_amd
+    N, B = a.bank
+    K = len(pay)
+    leads = [(c * 997) % 8000 for c in range(N)]
+    chans = [np.concatenate([np.zeros((lead, 2), np.int16), pcm]) for lead in leads]
+    longest = max(len(c) for c in chans)
+    rounds = (longest + B - 1) // B
+
+    def floor():
+        return rx.decode_streams(chans)
+
+    def bank():
+        per = [[] for _ in range(N)]
+        t_round = []
+        with rx.bank(N, 2) as b:
+            for r in range(rounds):
+                t0 = time.perf_counter()
+                o, res, rc, ri = b.push([c[r * B:(r + 1) * B] for c in chans])
+                t_round.append(time.perf_counter() - t0)
+                for c in np.unique(rc):
+                    per[c].append((o[rc == c], res[rc == c]))
+            o, res, rc, ri = b.end()
+            for c in np.unique(rc):
+                per[c].append((o[rc == c], res[rc == c]))
+        return per, t_round
+
+    M = a.feeds_cap or N
+    rxs = [modem_amd.Receiver(device=0, chunk_frames=4) for _ in range(M)]
+
+    def feeds():
+        per = [[] for _ in range(M)]
+        t_round = []
+        fs = [r.feed(2) for r in rxs]
+        for r in range(rounds):
+            t0 = time.perf_counter()
+            for c in range(M):
+                per[c].append(fs[c].push(chans[c][r * B:(r + 1) * B]))
+            t_round.append(time.perf_counter() - t0)
+        for c in range(M):
+            per[c].append(fs[c].end())
+            while fs[c].open:
+                fs[c].end()
+        return per, t_round
+
+    def joined(parts):
+        return (np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 5380), np.uint8),
+                np.concatenate([p[1] for p in parts]) if parts else np.zeros(0))
+
+    res = {}
+    for name, fn in (("bank", bank), ("feeds", feeds)):
+        for _ in range(a.warmup):
+            fn()
+        walls, per_round = [], []
+        for _ in range(a.steps):
+            t0 = time.perf_counter()
+            out, t_round = fn()
+            walls.append(time.perf_counter() - t0)
+            per_round.append(float(np.median(t_round)))
+        res[name] = (out, walls, per_round)
+    for _ in range(a.warmup):
+        floor()
+    fl_walls = []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        want = floor()
+        fl_walls.append(time.perf_counter() - t0)
+    same_bank = all(joined(res["bank"][0][c])[0].tobytes() == want[c][0].tobytes() and joined(res["bank"][0][c])[1].tobytes() == want[c][1].tobytes()
+                    for c in range(N))
+    same_feeds = all(joined(res["feeds"][0][c])[0].tobytes() == want[c][0].tobytes() for c in range(M))
+    n_rec = sum(len(w[1]) for w in want)
+    med = lambda v: float(np.median(v))
+    bank_wall, feeds_wall = med(res["bank"][1]), med(res["feeds"][1])
+    rec = {
+        "metric": "live feed bank: N channels of one recording, mode-6 8 kHz 2-channel int16, AWGN %g dB, against N feeds and one decode_streams call" % a.noise_db,
+        "channels": N, "block": B, "payloads_per_channel": K, "rounds": rounds, "steps": a.steps, "warmup": a.warmup, "records": n_rec,
+        "bank_ms_per_round_median": med(res["bank"][2]) * 1e3, "bank_wall_ms_median": bank_wall * 1e3, "bank_wall_ms_min": min(res["bank"][1]) * 1e3,
+        "bank_wall_ms_max": max(res["bank"][1]) * 1e3, "bank_records_per_s": n_rec / bank_wall,
+        "feeds_channels": M, "feeds_ms_per_round_median": med(res["feeds"][2]) * 1e3, "feeds_wall_ms_median": feeds_wall * 1e3,
+        "feeds_wall_ms_min": min(res["feeds"][1]) * 1e3, "feeds_wall_ms_max": max(res["feeds"][1]) * 1e3,
+        "feeds_records_per_s": n_rec * M / N / feeds_wall,
+        "bank_vs_feeds_per_channel": (feeds_wall / M) / (bank_wall / N),
+        "one_call_wall_ms_median": med(fl_walls) * 1e3, "one_call_records_per_s": n_rec / med(fl_walls), "bank_vs_one_call": med(fl_walls) / bank_wall,
+        "bank_same_bytes_as_one_call": bool(same_bank), "feeds_same_payloads_as_one_call": bool(same_feeds),
+        "payloads_ok": int(sum((w[0][:K] == pay).all(axis=1).sum() for w in want)),
+    }
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+    for r in rxs:
+        r.close()
     rx.close()
 
 
