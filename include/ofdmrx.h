@@ -52,8 +52,9 @@ extern "C" {
  *      added within 1.7 (the minor number stays: a caller detects them by symbol): the live feed - ofdmrx_feed_begin, ofdmrx_feed_push,
  *      ofdmrx_feed_end, ofdmrx_feed_lag, ofdmrx_feed_resident_samples; many recordings in one call - ofdmrx_decode_streams,
  *      ofdmrx_decode_streams_device, ofdmrx_debug_streams_edges; a bank of live channels - ofdmrx_bank_begin, ofdmrx_bank_push,
- *      ofdmrx_bank_end, ofdmrx_bank_resident_samples, ofdmrx_bank_preambles, ofdmrx_bank_last_stage_ops */
-#define OFDMRX_ABI_MINOR 7
+ *      ofdmrx_bank_end, ofdmrx_bank_resident_samples, ofdmrx_bank_preambles, ofdmrx_bank_last_stage_ops
+ *   8: ofdmrx_debug_polar_modes, ofdmrx_debug_decode_cons_modes (the single-stage test entries for every mode of the mode table) */
+#define OFDMRX_ABI_MINOR 8
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
 #define OFDMRX_CODE_LEN 65536         /* decode.cc:309  code_order 16 */
@@ -439,7 +440,8 @@ enum {
 	OFDMRX_TAP_PRECISION = 6,  /* f32   [rows]              decode.cc:517 */
 	OFDMRX_TAP_LLR = 7,        /* f32   [65536]    decode.cc:529 */
 	OFDMRX_TAP_METRIC = 8,     /* f32   [8] */
-	OFDMRX_TAP_LANE_MESG = 9,  /* u8    [8][5476]  systematic message bits per lane, LE packed */
+	OFDMRX_TAP_LANE_MESG = 9,  /* u8    [8][5476]  systematic message bits per lane, LE packed: the first 5476 bytes of every lane (all of
+	                            *                   them in modes 6-9; modes 10-13 have 5512: ofdmrx_debug_polar_modes returns [8][5512]) */
 	OFDMRX_TAP_ANALYTIC = 10   /* cf32  [samples]  after D1 (mono only) */
 };
 int ofdmrx_debug_dump(ofdmrx_handle *h, int tap, size_t frame, void *dst, size_t dst_bytes);
@@ -448,6 +450,12 @@ int ofdmrx_debug_dump(ofdmrx_handle *h, int tap, size_t frame, void *dst, size_t
 /* D9+D10: CODE::PolarListDecoder + systematic() (decode.cc:530-531) */
 int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr /*n*65536*/, size_t n,
 	uint8_t *lane_mesg /*n*8*5476*/, float *metric /*n*8*/);
+/* the same for any mode of the mode table: vector i is a codeword of mode oper_modes[i] (6..13, else OFDMRX_E_ARG; NULL: all mode
+ * 6), which decides its frozen table and message length; neighbours i, i + 1 of the same table are decoded as a pair by a
+ * list_size 4 handle.  Every lane's message comes back complete: mesg_bits / 8 bytes (5476 in modes 6-9, 5512 in modes 10-13),
+ * zero-padded to 5512. */
+int ofdmrx_debug_polar_modes(ofdmrx_handle *h, const float *llr /*n*65536*/, size_t n, const int32_t *oper_modes /*n*/,
+	uint8_t *lane_mesg /*n*8*5512*/, float *metric /*n*8*/);
 /* the sign-following path of the list decoder alone (k_sc): n LLR vectors, vector i of the code of mode oper_modes[i] (NULL: all
  * mode 6) -> its re-encoded codeword (bit i = bit i % 8 of byte i / 8), the hard decisions of the LLRs packed alike, its path
  * metric, min over the information leaves of fl(metric so far + |llr|), and whether the rule "min_fork > metric, every |llr| <
@@ -460,6 +468,12 @@ int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr /*n*65536*/, size_t 
  * by the syndrome certificate, 2 = by the list-1 pass, 0 = by the list decoder (decode.cc:505-555) */
 int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons /*n*21600*2*/, size_t n, int use_cert,
 	uint8_t *payload /*n*5380*/, ofdmrx_frame_result *results /*n*/, int32_t *cert_out /*n*/);
+/* the same for any mode of the mode table: frame i is of mode oper_modes[i] (6..13, else OFDMRX_E_ARG; NULL: all mode 6) and
+ * supplies that mode's cols x rows rotated points (<= 32400) at cons + i * cons_stride_points (a stride smaller than a frame's
+ * point count: OFDMRX_E_ARG); results[i].oper_mode is oper_modes[i].  Frames of all modes may share a call: the list-1 pass and
+ * the list decoder's queue then hold both frozen tables. */
+int ofdmrx_debug_decode_cons_modes(ofdmrx_handle *h, const float *cons /*n*cons_stride_points*2*/, size_t cons_stride_points, size_t n,
+	const int32_t *oper_modes /*n*/, int use_cert, uint8_t *payload /*n*5380*/, ofdmrx_frame_result *results /*n*/, int32_t *cert_out /*n*/);
 /* DSP::TheilSenEstimator::compute on rows of y[cols], x = i - cols/2 (decode.cc:488) */
 int ofdmrx_debug_theil_sen(ofdmrx_handle *h, const float *y, size_t rows, int cols,
 	float *slope, float *yint);

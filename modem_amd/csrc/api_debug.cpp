@@ -77,16 +77,34 @@ static int queue_run_all(ofdmrx_handle *h, int list)
 		h->q_hard.as<uint8_t>(), h->dev, h->q_metric.as<float>());
 	return 0;
 }
-extern "C" int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr, size_t n, uint8_t *lane_mesg, float *metric)
+// the slots' modes decide the frozen table, the message length and who sits beside whom (list 4 decodes same-table neighbours as a pair)
+static hipError_t patch_slot_modes(ofdmrx_handle *h, void *slots, size_t n, const int32_t *oper_modes)
 {
-	if (!h || !llr || !n || n > (size_t)h->chunk)
+	hipError_t e = hipStreamSynchronize(h->stream);
+	std::vector<ListSlot> ls(n);
+	e = e == hipSuccess ? hipMemcpy(ls.data(), slots, n * sizeof(ListSlot), hipMemcpyDeviceToHost) : e;
+	for (size_t i = 0; i < n; ++i)
+		ls[i].oper_mode = oper_modes[i];
+	return e == hipSuccess ? hipMemcpy(slots, ls.data(), n * sizeof(ListSlot), hipMemcpyHostToDevice) : e;
+}
+static bool modes_ok(const int32_t *oper_modes, size_t n)
+{
+	for (size_t i = 0; oper_modes && i < n; ++i)
+		if (oper_modes[i] < 6 || oper_modes[i] > 13)
+			return false;
+	return true;
+}
+// stride: bytes per lane of lane_mesg (MESG_BYTES: the mode-6 entry; MESG_BYTES_MAX: every mode's message, zero-padded)
+static int debug_polar(ofdmrx_handle *h, const float *llr, size_t n, const int32_t *oper_modes, int stride, uint8_t *lane_mesg, float *metric)
+{
+	if (!h || !llr || !n || n > (size_t)h->chunk || !modes_ok(oper_modes, n))
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	int r = ensure_capacity(h, (int)n, false, 0);
 	if (r)
 		return r;
 	DevBuf lm;                                                // the per-lane messages: a buffer of this call's own
-	r = lm.ensure((size_t)h->q_cap * LIST * MESG_BYTES);
+	r = lm.ensure((size_t)h->q_cap * LIST * stride);
 	if (r)
 		return r;
 	if ((r = host_wait(h)))
@@ -95,13 +113,15 @@ extern "C" int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr, size_t n, 
 	HIP_OK(hipMemsetAsync(h->res[0].p, 0, n * sizeof(Result), h->stream));
 	launch_queue_reset(h->stream, h->queue(), h->q_cap);
 	launch_queue_fill(h->stream, h->queue(), h->q_slots.as<ListSlot>(), (int)n, h->payload[0].as<uint8_t>(), h->res[0].as<Result>(), 6);
+	if (oper_modes)
+		HIP_OK(patch_slot_modes(h, h->q_slots.p, n, oper_modes));
 	queue_run_all(h, h->list);
 	launch_finish(h->stream, h->list, (int)n, h->queue(), 0, h->q_slots.as<ListSlot>(), h->q_llr.as<float>(), h->q_hard.as<uint8_t>(), h->dev, 0,
-		lm.as<uint8_t>());
+		lm.as<uint8_t>(), stride);
 	hipError_t e = hipGetLastError();
 	e = e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
 	if (e == hipSuccess && lane_mesg)
-		e = hipMemcpy(lane_mesg, lm.p, n * LIST * MESG_BYTES, hipMemcpyDeviceToHost);
+		e = hipMemcpy(lane_mesg, lm.p, n * LIST * stride, hipMemcpyDeviceToHost);
 	if (e == hipSuccess && metric)
 		e = hipMemcpy(metric, h->q_metric.p, n * LIST * sizeof(float), hipMemcpyDeviceToHost);
 	if (e != hipSuccess) {
@@ -111,6 +131,14 @@ extern "C" int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr, size_t n, 
 	h->last_n = 0;
 	return 0;
 }
+extern "C" int ofdmrx_debug_polar(ofdmrx_handle *h, const float *llr, size_t n, uint8_t *lane_mesg, float *metric)
+{
+	return debug_polar(h, llr, n, nullptr, MESG_BYTES, lane_mesg, metric);
+}
+extern "C" int ofdmrx_debug_polar_modes(ofdmrx_handle *h, const float *llr, size_t n, const int32_t *oper_modes, uint8_t *lane_mesg, float *metric)
+{
+	return debug_polar(h, llr, n, oper_modes, MESG_BYTES_MAX, lane_mesg, metric);
+}
 
 // the sign-following path alone: n LLR vectors -> k_sc's outputs (codeword, hard decisions, metric, min_fork, rule)
 extern "C" int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr, size_t n, const int32_t *oper_modes, uint8_t *codeword, uint8_t *hard,
@@ -118,9 +146,8 @@ extern "C" int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr, size_t n
 {
 	if (!h || !llr || !n || n > (size_t)h->chunk)
 		return OFDMRX_E_ARG;
-	for (size_t i = 0; oper_modes && i < n; ++i)
-		if (oper_modes[i] < 6 || oper_modes[i] > 13)
-			return OFDMRX_E_ARG;
+	if (!modes_ok(oper_modes, n))
+		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	int r = ensure_capacity(h, (int)n, false, 0);
 	if (r)
@@ -141,14 +168,8 @@ extern "C" int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr, size_t n
 		hipError_t e = hipMemcpy(dl.p, llr, n * CODE_LEN * sizeof(float), hipMemcpyHostToDevice);
 		launch_queue_reset(h->stream, ctl.as<ListQueue>(), (unsigned)n);
 		launch_queue_fill(h->stream, ctl.as<ListQueue>(), slots.as<ListSlot>(), (int)n, h->payload[0].as<uint8_t>(), h->res[0].as<Result>(), 6);
-		if (oper_modes && e == hipSuccess) {                      // (the slots' modes decide the frozen table and who sits beside whom)
-			e = hipStreamSynchronize(h->stream);
-			std::vector<ListSlot> ls(n);
-			e = e == hipSuccess ? hipMemcpy(ls.data(), slots.p, n * sizeof(ListSlot), hipMemcpyDeviceToHost) : e;
-			for (size_t i = 0; i < n; ++i)
-				ls[i].oper_mode = oper_modes[i];
-			e = e == hipSuccess ? hipMemcpy(slots.p, ls.data(), n * sizeof(ListSlot), hipMemcpyHostToDevice) : e;
-		}
+		if (oper_modes && e == hipSuccess)
+			e = patch_slot_modes(h, slots.p, n, oper_modes);
 		launch_sc_plan(h->stream, ctl.as<ListQueue>());
 		launch_sc(h->stream, h->sc_lb ? h->sc_lb : 6, grid, grid, ctl.as<ListQueue>(), slots.as<ListSlot>(), dl.as<float>(), soft.as<float>(), cw.as<unsigned long long>(),
 			xw.as<unsigned long long>(), stat.as<ScStat>(), h->dev, h->sc_top);
@@ -175,15 +196,21 @@ extern "C" int ofdmrx_debug_sc_path(ofdmrx_handle *h, const float *llr, size_t n
 	return r;
 }
 
-// D5 output -> payload: ROTATED constellation rows of mode-6 frames through D6-D10 exactly as the pipeline chains them (the rows'
-// Theil-Sen lines are set to zero, so k_back's rotation is the identity), with the syndrome certificate (use_cert != 0: tried for
-// every frame, the list decoder only for the frames it leaves) or without (the list decoder for every frame); cert_out
-// (nullable) receives the certificate's verdict per frame (1 = finished by it)
-extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, size_t n, int use_cert, uint8_t *payload,
-	ofdmrx_frame_result *results, int32_t *cert_out)
+// D5 output -> payload: ROTATED constellation rows through D6-D10 exactly as the pipeline chains them (the rows' Theil-Sen lines are
+// set to zero, so k_back's rotation is the identity), with the syndrome certificate (use_cert != 0: tried for every frame, the list
+// decoder only for the frames it leaves) or without (the list decoder for every frame); cert_out (nullable) receives the
+// certificate's verdict per frame (1 = finished by it).  Frame i is of mode oper_modes[i] (NULL: all mode 6) and supplies that
+// mode's cols x rows points at cons + i * cons_stride_points.
+extern "C" int ofdmrx_debug_decode_cons_modes(ofdmrx_handle *h, const float *cons, size_t cons_stride_points, size_t n, const int32_t *oper_modes,
+	int use_cert, uint8_t *payload, ofdmrx_frame_result *results, int32_t *cert_out)
 {
-	if (!h || !cons || !n || n > (size_t)h->chunk || !payload || !results || h->list != 8 || use_cert < 0 || use_cert > 3)
+	if (!h || !cons || !n || n > (size_t)h->chunk || !payload || !results || h->list != 8 || use_cert < 0 || use_cert > 3 || !modes_ok(oper_modes, n))
 		return OFDMRX_E_ARG;
+	for (size_t i = 0; i < n; ++i) {
+		const ModeDesc md = mode_desc(oper_modes ? oper_modes[i] : 6);
+		if ((size_t)(md.cols * md.rows) > cons_stride_points)
+			return OFDMRX_E_ARG;
+	}
 	const bool with_sc = use_cert >= 2;                           // 2: syndrome certificate, list-1 pass, list decoder (the default chain); 3: without the first
 	if (with_sc && !h->sc_mode)
 		return OFDMRX_E_UNSUPPORTED;
@@ -193,11 +220,12 @@ extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, siz
 		return r;
 	std::vector<SyncState> st(n);
 	std::memset(st.data(), 0, n * sizeof(SyncState));
-	for (auto &s : st) { s.okay = 1; s.oper_mode = 6; }
+	for (size_t i = 0; i < n; ++i) { st[i].okay = 1; st[i].oper_mode = oper_modes ? oper_modes[i] : 6; }
 	if ((r = host_wait(h)))
 		return r;
+	const size_t width = std::min<size_t>(cons_stride_points, CONS_MAX) * sizeof(cf);   // (k_back reads a frame's cols x rows points only)
 	HIP_OK(hipMemcpy(h->st.p, st.data(), n * sizeof(SyncState), hipMemcpyHostToDevice));
-	HIP_OK(hipMemcpy2D(h->cons.p, CONS_MAX * sizeof(cf), cons, 21600 * sizeof(cf), 21600 * sizeof(cf), n, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy2D(h->cons.p, CONS_MAX * sizeof(cf), cons, cons_stride_points * sizeof(cf), width, n, hipMemcpyHostToDevice));
 	HIP_OK(hipMemsetAsync(h->res[0].p, 0, n * sizeof(Result), h->stream));
 	HIP_OK(hipMemsetAsync(h->slope.p, 0, n * ROWS_MAX * sizeof(float), h->stream));
 	HIP_OK(hipMemsetAsync(h->yint.p, 0, n * ROWS_MAX * sizeof(float), h->stream));
@@ -212,7 +240,7 @@ extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, siz
 	launch_queue_snap(h->stream, h->queue(), 0);
 	queue_run_all(h, 8);
 	launch_finish(h->stream, 8, (int)n, h->queue(), 0, h->q_slots.as<ListSlot>(), h->q_llr.as<float>(), h->q_hard.as<uint8_t>(), h->dev,
-		h->cfg.descramble, nullptr);
+		h->cfg.descramble, nullptr, 0);
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipStreamSynchronize(h->stream));
 	HIP_OK(hipMemcpy(payload, h->payload[0].p, n * PAYLOAD_BYTES, hipMemcpyDeviceToHost));
@@ -225,6 +253,11 @@ extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, siz
 	}
 	h->last_n = (int)n;
 	return 0;
+}
+extern "C" int ofdmrx_debug_decode_cons(ofdmrx_handle *h, const float *cons, size_t n, int use_cert, uint8_t *payload,
+	ofdmrx_frame_result *results, int32_t *cert_out)
+{
+	return ofdmrx_debug_decode_cons_modes(h, cons, 21600, n, nullptr, use_cert, payload, results, cert_out);
 }
 
 extern "C" int ofdmrx_debug_theil_sen(ofdmrx_handle *h, const float *y, size_t rows, int cols, float *slope, float *yint)

@@ -224,7 +224,7 @@ static int run_flush(ofdmrx_handle *h, hipStream_t s_polar, hipStream_t s_fin, i
 	{
 		Range r("ofdmrx:finish");
 		launch_finish(s_fin, h->list, (int)h->q_cap, h->queue(), par, h->q_slots.as<ListSlot>(), h->q_llr.as<float>(), h->q_hard.as<uint8_t>(),
-			h->dev, h->cfg.descramble, h->q_lane_mesg.as<uint8_t>());
+			h->dev, h->cfg.descramble, h->q_lane_mesg.as<uint8_t>(), MESG_BYTES);
 	}
 	size_t e9 = mark(h, s_fin);
 	h->spans.push_back({ OFDMRX_T_FINISH, e8, e9 });

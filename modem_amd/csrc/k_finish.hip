@@ -410,7 +410,8 @@ void launch_queue_fill(hipStream_t s, ListQueue *q, ListSlot *slots, int n, uint
 // (LE bit packing + flip count), decode.cc:613-615 (descramble).
 // One workgroup per entry of the flush `par` of the list decoder's queue; workgroups beyond the run leave at once.
 __global__ __launch_bounds__(256) void k_finish(const ListQueue *__restrict__ q, int par, const ListSlot *__restrict__ slots,
-	const float *__restrict__ llr_q, const uint8_t *__restrict__ hard_q, Tables tb, int descramble, int list, uint8_t *__restrict__ lane_mesg_q)
+	const float *__restrict__ llr_q, const uint8_t *__restrict__ hard_q, Tables tb, int descramble, int list, uint8_t *__restrict__ lane_mesg_q,
+	int lane_mesg_stride)
 {
 	const int rel = blockIdx.x, tid = threadIdx.x;
 	const unsigned run_n = q->run_n[par], run_head = q->run_head[par], cap = q->cap;
@@ -461,9 +462,10 @@ __global__ __launch_bounds__(256) void k_finish(const ListQueue *__restrict__ q,
 			mesg[k][bi] = (uint8_t)o[k];
 	}
 	__syncthreads();
-	if (lane_mesg_q)
-		for (int i = tid; i < LIST * MESG_BYTES; i += 256)
-			lane_mesg_q[(size_t)slot * LIST * MESG_BYTES + i] = mesg[i / MESG_BYTES][i % MESG_BYTES];
+	if (lane_mesg_q)                                              // debug copy (null in the pipeline unless the handle keeps taps): lane_mesg_stride
+		for (int k = 0; k < LIST; ++k)                            // bytes per lane, the mode's mesg_bits / 8 of them the message, zeros behind
+			for (int b = tid; b < lane_mesg_stride; b += 256)
+				lane_mesg_q[((size_t)slot * LIST + k) * lane_mesg_stride + b] = b < mesg_bytes ? mesg[k][b] : (uint8_t)0;
 	// CRC<uint32_t>(0xD419CC15) over the first 43072 bits of each lane (decode.cc:533-541), 32 threads per lane:
 	// every thread runs the byte-table CRC over its own 168-byte segment from a zero state, then the 32 partial
 	// states are folded in order with the "advance by 168 zero bytes" operator (CRC is linear: state(A|B) =
@@ -538,9 +540,10 @@ __global__ __launch_bounds__(256) void k_finish(const ListQueue *__restrict__ q,
 }
 
 void launch_finish(hipStream_t s, int list, int max_entries, const ListQueue *q, int par, const ListSlot *slots, const float *llr_q,
-	const uint8_t *hard_q, Tables tb, int descramble, uint8_t *lane_mesg_q)
+	const uint8_t *hard_q, Tables tb, int descramble, uint8_t *lane_mesg_q, int lane_mesg_stride)
 {
-	hipLaunchKernelGGL(k_finish, dim3(max_entries), dim3(256), 0, s, q, par, slots, llr_q, hard_q, tb, descramble, list == 4 ? 4 : 8, lane_mesg_q);
+	hipLaunchKernelGGL(k_finish, dim3(max_entries), dim3(256), 0, s, q, par, slots, llr_q, hard_q, tb, descramble, list == 4 ? 4 : 8, lane_mesg_q,
+		lane_mesg_stride);
 }
 void launch_back(hipStream_t s, int rate, int n, int cert_mode, const SyncState *st, const cf *cons, const float *slope, const float *yint,
 	float *precision, Result *res, float *esn0_rows, Tables tb, int descramble, uint8_t *payload, ListQueue *q, ListSlot *slots,

@@ -250,7 +250,7 @@ int sc_codewords_per_wave(int lb);
 void launch_polar(hipStream_t s, int list, int grid, ListQueue *q, int par, const ListSlot *slots, const float *llr_q, float *soft, uint8_t *hard_q,
 	Tables tb, float *metric_q);
 void launch_finish(hipStream_t s, int list, int max_entries, const ListQueue *q, int par, const ListSlot *slots, const float *llr_q,
-	const uint8_t *hard_q, Tables tb, int descramble, uint8_t *lane_mesg_q);
+	const uint8_t *hard_q, Tables tb, int descramble, uint8_t *lane_mesg_q, int lane_mesg_stride);   // (stride: bytes per lane of the debug copy)
 void launch_fft_debug(hipStream_t s, int rate, int n, int len, int sign, const cf *in, cf *out, Tables tb);
 void launch_awgn_tile(hipStream_t s, const int16_t *base, size_t n_base, int16_t *out, size_t n_out,
 	size_t spf, float sigma, uint64_t seed, uint64_t first_frame);

@@ -13,6 +13,8 @@ PAYLOAD_BYTES = 5380
 CODE_LEN = 65536
 FRAME_SAMPLES = 95200
 MESG_BYTES = 5476
+MESG_BYTES_MAX = 5512   # modes 10-13 (44096 message bits); Receiver.polar(modes=...) returns this many per lane
+CONS_MAX = 32400
 STATUS_NAMES = ["OK", "NO_SYNC", "OSD_ERROR", "HEADER_CRC", "BAD_MODE", "BAD_CALLSIGN", "PAYLOAD_CRC"]
 TAPS = dict(HDR_SOFT=1, CONS_RAW=2, CONS_ROT=3, SLOPE=4, YINT=5, PRECISION=6, LLR=7, METRIC=8, LANE_MESG=9, ANALYTIC=10)
 STAGES = ["front", "sync", "header", "demod", "theilsen", "llr", "polar", "finish", "total"]
@@ -21,7 +23,8 @@ STAGES = ["front", "sync", "header", "demod", "theilsen", "llr", "polar", "finis
 EXPORTS = [
     "ofdmrx_abi_version", "ofdmrx_abi_minor", "ofdmrx_strerror", "ofdmrx_create", "ofdmrx_destroy", "ofdmrx_decode_batch",
     "ofdmrx_decode_batch_device", "ofdmrx_synchronize", "ofdmrx_get_timing", "ofdmrx_chunk_frames", "ofdmrx_last_chunk_first_frame", "ofdmrx_list_decoded_frames", "ofdmrx_sc_decided_frames", "ofdmrx_get_sc_timing", "ofdmrx_set_esn0_rows", "ofdmrx_set_attempt_log",
-    "ofdmrx_debug_dump", "ofdmrx_debug_polar", "ofdmrx_debug_sc_path", "ofdmrx_debug_decode_cons", "ofdmrx_debug_theil_sen", "ofdmrx_debug_osd", "ofdmrx_debug_fft",
+    "ofdmrx_debug_dump", "ofdmrx_debug_polar", "ofdmrx_debug_sc_path", "ofdmrx_debug_decode_cons", "ofdmrx_debug_polar_modes",
+    "ofdmrx_debug_decode_cons_modes", "ofdmrx_debug_theil_sen", "ofdmrx_debug_osd", "ofdmrx_debug_fft",
     "ofdmrx_util_awgn_tile", "ofdmrx_util_channel", "ofdmrx_frame_samples", "ofdmrx_tx_frame_samples",
     "ofdmrx_tx_encode_device", "ofdmrx_stream_samples", "ofdmrx_tx_encode_stream_device", "ofdmrx_tx_encode_stream",
     "ofdmrx_callsign_value", "ofdmrx_decode_stream", "ofdmrx_decode_stream_device", "ofdmrx_debug_stream_edges",
@@ -157,6 +160,9 @@ def load_library():
     L.ofdmrx_debug_dump.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_debug_polar.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.ofdmrx_debug_decode_cons.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ofdmrx_debug_polar_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ofdmrx_debug_decode_cons_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
     L.ofdmrx_debug_theil_sen.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     L.ofdmrx_debug_osd.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.ofdmrx_debug_fft.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
@@ -423,12 +429,20 @@ class Receiver:
         return a
 
     # ---- single-stage entry points (parity tests)
-    def polar(self, llr):
+    def polar(self, llr, modes=None):
+        """the list decoder alone: per-lane messages and path metrics.  modes None: mode-6 codewords, messages [n, 8, 5476]
+        (ofdmrx_debug_polar); else the operation mode of every vector (6..13), messages [n, 8, 5512] with mesg_bits / 8 bytes of
+        message per lane and zeros behind (ofdmrx_debug_polar_modes)"""
         llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, CODE_LEN)
         n = llr.shape[0]
-        mesg = np.zeros((n, 8, MESG_BYTES), np.uint8)
         metric = np.zeros((n, 8), np.float32)
-        self._check(self._lib.ofdmrx_debug_polar(self._h, _ptr(llr), n, _ptr(mesg), _ptr(metric)))
+        if modes is None:
+            mesg = np.zeros((n, 8, MESG_BYTES), np.uint8)
+            self._check(self._lib.ofdmrx_debug_polar(self._h, _ptr(llr), n, _ptr(mesg), _ptr(metric)))
+        else:
+            mode = np.ascontiguousarray(np.broadcast_to(np.asarray(modes, np.int32), (n,)))
+            mesg = np.zeros((n, 8, MESG_BYTES_MAX), np.uint8)
+            self._check(self._lib.ofdmrx_debug_polar_modes(self._h, _ptr(llr), n, _ptr(mode), _ptr(mesg), _ptr(metric)))
         return mesg, metric
 
     def sc_path(self, llr, modes=None):
@@ -443,16 +457,25 @@ class Receiver:
         self._check(self._lib.ofdmrx_debug_sc_path(self._h, _ptr(llr), n, mode, _ptr(cw), _ptr(hd), _ptr(metric), _ptr(fork), _ptr(ok)))
         return np.unpackbits(cw, axis=1, bitorder="little"), np.unpackbits(hd, axis=1, bitorder="little"), metric, fork, ok
 
-    def decode_cons(self, cons, use_cert=True):
+    def decode_cons(self, cons, use_cert=True, modes=None):
         """rotated constellation rows (n x 21600 complex64, mode 6) -> payloads, results, who finished each frame (1 the syndrome
         certificate, 2 the list-1 pass, 0 the list decoder).  use_cert: 0 / False list decoder only, 1 / True syndrome certificate
-        first, 2 the default chain (certificate, list-1 pass, list decoder), 3 list-1 pass then list decoder"""
-        cons = np.ascontiguousarray(cons, dtype=np.complex64).reshape(-1, 21600)
-        n = cons.shape[0]
-        out = np.zeros((n, 5380), np.uint8)
-        res = np.zeros(n, RESULT_DTYPE)
-        cert = np.zeros(n, np.int32)
-        self._check(self._lib.ofdmrx_debug_decode_cons(self._h, _ptr(cons), n, int(use_cert), _ptr(out), _ptr(res), _ptr(cert)))
+        first, 2 the default chain (certificate, list-1 pass, list decoder), 3 list-1 pass then list decoder.  modes: the operation
+        mode of every frame (6..13); cons is then [n, stride] with a frame's cols x rows points first (stride <= 32400 will do)"""
+        out_res = lambda n: (np.zeros((n, 5380), np.uint8), np.zeros(n, RESULT_DTYPE), np.zeros(n, np.int32))
+        if modes is None:
+            cons = np.ascontiguousarray(cons, dtype=np.complex64).reshape(-1, 21600)
+            n = cons.shape[0]
+            out, res, cert = out_res(n)
+            self._check(self._lib.ofdmrx_debug_decode_cons(self._h, _ptr(cons), n, int(use_cert), _ptr(out), _ptr(res), _ptr(cert)))
+            return out, res, cert
+        cons = np.ascontiguousarray(cons, dtype=np.complex64)
+        assert cons.ndim == 2
+        n, stride = cons.shape
+        mode = np.ascontiguousarray(np.broadcast_to(np.asarray(modes, np.int32), (n,)))
+        out, res, cert = out_res(n)
+        self._check(self._lib.ofdmrx_debug_decode_cons_modes(self._h, _ptr(cons), stride, n, _ptr(mode), int(use_cert), _ptr(out), _ptr(res),
+                                                             _ptr(cert)))
         return out, res, cert
 
     def theil_sen(self, y):

@@ -28,7 +28,7 @@ from test_gpu_parity import _tie_class
 
 pytestmark = pytest.mark.gpu
 
-def _sweep(n, db, seed, channels=2, dc=0, chunk=1024, allow_row_ties=False, explain=True):
+def _sweep(n, db, seed, channels=2, dc=0, chunk=1024, allow_row_ties=False, explain=True, mode=6):
     import torch
     import modem_amd
     import modem_amd.ofdmrx as M
@@ -36,12 +36,12 @@ def _sweep(n, db, seed, channels=2, dc=0, chunk=1024, allow_row_ties=False, expl
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
         rx = modem_amd.Receiver(device=0, chunk_frames=chunk, stream=stream.cuda_stream)
-        spf = rx.tx_frame_samples(6)
+        spf = rx.tx_frame_samples(mode)
         g = torch.Generator(device=dev)
         g.manual_seed(seed)
         d_pay = torch.randint(0, 256, (n, 5380), dtype=torch.uint8, device=dev, generator=g)
         d_in = torch.empty((n, spf, 2), dtype=torch.int16, device=dev)
-        rx.tx_encode(d_pay.data_ptr(), n, d_in.data_ptr())
+        rx.tx_encode(d_pay.data_ptr(), n, d_in.data_ptr(), mode=mode)
         rx.awgn_tile(d_in.data_ptr(), n, d_in.data_ptr(), n, spf, db, seed + 1, 0)
         rx.synchronize()
         if channels == 1:       # the real part of the noisy analytic stream + a DC offset: what a 1-channel WAV holds (encode.cc:127-128)
@@ -70,7 +70,8 @@ def _sweep(n, db, seed, channels=2, dc=0, chunk=1024, allow_row_ties=False, expl
     # the flip count: identical, or explained position by position
     fl = np.nonzero(same & (res["bit_flips"] != ores["bit_flips"]))[0]
     if len(fl) and explain:
-        _explain_flips([pcm[i] for i in fl], channels, res["bit_flips"][fl], ores["bit_flips"][fl], allow_row_ties)
+        _explain_flips([pcm[i] for i in fl], channels, res["bit_flips"][fl], ores["bit_flips"][fl], allow_row_ties, mode=mode)
+    assert (res["oper_mode"][ok] == mode).all()
     return dict(differ=differ, classes=classes, routes=routes, ok=int(ok.sum()), flips_differ=len(fl), res=res, ores=ores)
 
 
@@ -106,3 +107,33 @@ def test_sweep_mono():
     s = _sweep(4096, -19.0, 3004, channels=1, dc=700, allow_row_ties=True)
     assert s["ok"] == 4096
     assert len(s["differ"]) <= 2 and all(c == "timing" for c in s["classes"]), (s["differ"], s["classes"])
+
+
+# ---- the same three regimes in every other mode of the mode table, small: the noise levels are mode_levels.py's (fixed with the oracle)
+@pytest.mark.parametrize("mode", [7, 8, 9, 10, 11, 12, 13])
+def test_sweep_certified_in_every_mode(mode):
+    """64 frames at -30 dB in modes 7 - 13: the syndrome certificate finishes every frame; nothing differs, not even a flip count"""
+    s = _sweep(64, -30.0, 3100 + mode, chunk=64, mode=mode)
+    assert s["routes"] == (64, 0, 0) and s["ok"] == 64
+    assert s["differ"] == [] and s["flips_differ"] == 0
+    assert (s["res"]["bit_flips"] == 0).all() and (s["res"]["best_lane"] == 0).all()
+
+
+@pytest.mark.parametrize("mode", [7, 8, 9, 10, 11, 12, 13])
+def test_sweep_list1_level_in_every_mode(mode):
+    """64 frames at the mode's list-1 level (raw bit errors in every frame, the sign-following path decides): everything decided
+    identical, every flip-count difference explained position by position"""
+    import mode_levels as ML
+    s = _sweep(64, ML.LEVELS[mode]["list1"][0], 3200 + mode, chunk=64, allow_row_ties=True, mode=mode)
+    assert s["ok"] == 64 and (s["ores"]["bit_flips"] > 0).all()
+    assert s["differ"] == [], (s["differ"], s["classes"])
+
+
+@pytest.mark.parametrize("mode", [7, 8, 9, 10, 11, 12, 13])
+def test_sweep_waterfall_in_every_mode(mode):
+    """64 frames at the mode's waterfall level (decoded and lost frames mixed): identical but for the documented tie classes.  Their
+    rate is 5 in 65 536 frames - about 0.1 frame over these seven sweeps - so at most one per sweep; a second one is a finding"""
+    import mode_levels as ML
+    s = _sweep(64, ML.LEVELS[mode]["waterfall"][0], 3300 + mode, chunk=64, allow_row_ties=True, mode=mode)
+    assert 0 < s["ok"] < 64 and s["routes"][2] >= 1
+    assert len(s["differ"]) <= 1 and all(s["classes"]), (s["differ"], s["classes"])
