@@ -485,7 +485,10 @@ int ofdmrx_debug_fft(ofdmrx_handle *h, const float *in, size_t n, int len, int s
 /* ---- build-owned channel model on device (aicodix/disorders is absent) ----
  * out frame f = base frame (f % n_base) + complex AWGN of power 10^(noise_db/10)
  * (re/im split equally), counter-based RNG keyed by (seed, first_frame+f).
- * 2-channel int16 in and out, DEVICE pointers, samples_per_frame each. */
+ * 2-channel int16 in and out, DEVICE pointers, samples_per_frame each.
+ * In place is allowed in one form only: d_out == d_base with n_out <= n_base, where frame f reads and writes only itself.
+ * Any other overlap of the two buffers, and a noise_db that is not finite, is OFDMRX_E_ARG.  What pins the noise to its
+ * definition, sample by sample: DESIGN.md section 4.8. */
 int ofdmrx_util_awgn_tile(ofdmrx_handle *h, const int16_t *d_base, size_t n_base,
 	int16_t *d_out, size_t n_out, size_t samples_per_frame, float noise_db,
 	uint64_t seed, uint64_t first_frame);

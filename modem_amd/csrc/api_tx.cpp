@@ -4,8 +4,15 @@
 extern "C" int ofdmrx_util_awgn_tile(ofdmrx_handle *h, const int16_t *d_base, size_t n_base, int16_t *d_out, size_t n_out,
 	size_t spf, float noise_db, uint64_t seed, uint64_t first_frame)
 {
-	if (!h || !d_base || !d_out || !n_base || !n_out || !spf)
+	if (!h || !d_base || !d_out || !n_base || !n_out || !spf || !std::isfinite(noise_db))
 		return OFDMRX_E_ARG;
+	{
+		const char *a = (const char *)d_base, *b = (const char *)d_out;
+		const size_t fb = spf * 2 * sizeof(int16_t);
+		const bool in_place = a == b && n_out <= n_base;       // frame f reads and writes only itself
+		if (!in_place && a < b + n_out * fb && b < a + n_base * fb)   // any other overlap: one block reads what another writes
+			return OFDMRX_E_ARG;
+	}
 	HIP_OK(hipSetDevice(h->cfg.device));
 	const float sigma = std::sqrt(0.5f * std::pow(10.f, noise_db / 10.f));
 	launch_awgn_tile(h->stream, d_base, n_base, d_out, n_out, spf, sigma, seed, first_frame);
