@@ -277,7 +277,8 @@ int ofdmrx_debug_streams_edges(ofdmrx_handle *h, const float *timing, size_t n_s
 
 /*
  * Live feed (added within revision 1.7): the same recording pushed block by block as it arrives, each record returned once its last
- * sample is in.  One feed per handle; HOST pointers; the calls block.
+ * sample is in.  One feed per handle; HOST pointers; the calls block.  A feed is a bank (below) of one channel whose records come
+ * without channel and index: the same driver and kernels serve both.
  *   begin   opens a feed of `channels` interleaved values of sample_format: position 0, record 0.
  *   push    n_samples more sample frames (0 is allowed); returns the records that have become due, in preamble order.
  *   end     the stream is over: the last partial tile is scanned with n = the samples fed and every pending preamble decoded with
@@ -300,8 +301,8 @@ int ofdmrx_debug_streams_edges(ofdmrx_handle *h, const float *timing, size_t n_s
  * end call push accepts n_samples == 0 only.  Es/N0 rows (ofdmrx_set_esn0_rows, a host pointer): row block i belongs to the i-th
  * record the call writes.  The attempt log is not written and OFDMRX_FLAG_TWO_LANES is ignored, as for stream calls;
  * ofdmrx_get_timing and the stage taps describe the last decode a feed call ran.
- * OFDMRX_E_ARG: push / end without begin, begin while a feed is open, any ofdmrx_decode_batch* / ofdmrx_decode_stream* while a feed
- * is open, a NULL handle, NULL samples with n_samples > 0, NULL n_records / n_left, NULL outputs with max_frames > 0, a bad format
+ * OFDMRX_E_ARG: push / end without begin, begin while a feed or a bank is open, any ofdmrx_bank_*, ofdmrx_decode_batch* /
+ * ofdmrx_decode_stream* while a feed is open, a NULL handle, NULL samples with n_samples > 0, NULL n_records / n_left, NULL outputs with max_frames > 0, a bad format
  * or channel count, samples not on a sample-frame boundary - all before any device call.  ofdmrx_destroy frees an open feed.
  * ofdmrx_feed_resident_samples: sample frames of the stream held on the device now: fed - base, where base is the largest multiple
  * of 4096 not above the smallest of
@@ -334,8 +335,8 @@ long long ofdmrx_feed_resident_samples(ofdmrx_handle *h);
  *           have become due.
  *   end     every channel still open ends; the bank closes when an end call leaves *n_left == 0.
  * Per channel: the records of channel c are the records returned for c (record_channel[i] == c) over all push and end calls,
- * concatenated in the order returned.  They equal what a single ofdmrx_feed_* returns when fed channel c's samples in the same
- * sequence of push lengths - every payload byte and every byte of every ofdmrx_frame_result, every format and every rate.  A
+ * concatenated in the order returned.  They equal what a single ofdmrx_feed_* (a bank of that channel alone) returns when fed
+ * channel c's samples in the same sequence of push lengths - every payload byte and every byte of every ofdmrx_frame_result, every format and every rate.  A
  * zero-length share counts as a zero-length push: the channel behaves as a single feed does with that push left out.  For 2-channel
  * input this is therefore also ofdmrx_decode_stream of the concatenation of channel c's samples, byte for byte.
  * Mono input inherits the feed's documented relation to the one-call decode and no more: every channel's DC-blocker states are
@@ -354,7 +355,7 @@ long long ofdmrx_feed_resident_samples(ofdmrx_handle *h);
  * Es/N0 rows (ofdmrx_set_esn0_rows, a host pointer): row block i belongs to the i-th record the call writes.  The attempt log is not
  * written and OFDMRX_FLAG_TWO_LANES is ignored; the other flags hold, as for the feed.
  * An ended channel accepts only n_samples[c] == 0 and stays closed until the bank closes.
- * OFDMRX_E_ARG, before any device call: push or end without begin; begin while a bank or a feed is open; ofdmrx_feed_begin, any
+ * OFDMRX_E_ARG, before any device call: push or end without begin; begin while a bank or a feed is open; any ofdmrx_feed_*,
  * ofdmrx_decode_batch* or ofdmrx_decode_stream* while a bank is open; a NULL handle, n_samples, n_records or n_left; NULL samples
  * while any length is non-zero; NULL outputs (any of the four arrays) with max_records > 0; n_channels outside 1 .. 65535; a bad
  * format or channel count; a length above 1 << 26; samples for an ended channel; a stride that is not a multiple of the

@@ -1,13 +1,19 @@
-// api_bank.cpp -- ofdmrx_bank_*: many live channels pushed and decoded in one call (added within revision 1.7).
-//   The structure of api_feed.cpp with every per-feed scalar a per-channel array, and every stage run ONCE for all channels:
+// api_bank.cpp -- the live entries: ofdmrx_bank_*, many live channels pushed and decoded in one call, and
+// ofdmrx_feed_*, one recording decoded block by block as it arrives: a bank of one channel, at the end of this file.
+//   push: the new samples join every channel's WINDOW of its stream in device memory (raw samples; mono input: the DC blocker's kept
+//   states and the analytic signal as well), and every stage runs ONCE for all channels:
 //   window move (one kernel) | the new samples (packed on the host, one copy, one kernel that places every channel's share in its
-//   window) | one scan, accept and records pass over every tile any channel completed (the window forms of k_stream.hip with the
-//   channel as the second grid dimension, a segmented scan from every channel's own carry) | one read-back of all counts and
-//   carries | one header pass over every pending preamble whose header symbol has arrived | ONE decode_records call over every
-//   record that is due on any channel: the records of many channels share chunks | delivery
+//   window) | one scan, accept and records pass over every tile any channel completed (the WindowBatch forms of k_stream.hip with
+//   the channel as the second grid dimension, a segmented scan from the trigger carry every channel's last push left) | one
+//   read-back of all counts and carries | one header pass over every pending preamble whose header symbol has arrived (its mode says
+//   when its frame is complete) | ONE decode_records call over every record that is due on any channel, in channel then preamble
+//   order: the records of many channels share chunks | delivery
+//   end:  the last partial tile of every channel with n = the samples fed, every pending preamble, delivery
 // The windows of all channels live in one slab pair [n_channels][cap] with a common capacity; channel c's window begins at its own
-// base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch), and before any launch the host
-// checks, for every channel the launch touches, that the channel's window holds every position the launch reads (covers()).
+// base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch: it is handed the address position 0
+// WOULD have and n = the samples fed, so a position past the end reads as zero as in a one-call decode); positions below the base are
+// not in memory, and before any launch the host checks, for every channel the launch touches, that the channel's window holds every
+// position the launch reads (covers()).
 #include "api_internal.h"
 #include <deque>
 
@@ -42,6 +48,7 @@ struct ofdmrx_bank {
 	std::vector<char> stage_h;
 	long long ops = 0;                                        // launches + copies + synchronisations of the last call's own stages
 	bool ending = false;
+	bool as_feed = false;                                     // opened by ofdmrx_feed_begin: the ofdmrx_feed_* entries serve it, ofdmrx_bank_* refuse it
 };
 
 void bank_free(ofdmrx_handle *h)
@@ -76,7 +83,13 @@ int covers(const ofdmrx_bank &b, size_t c, long long lo, const char *what)
 	return OFDMRX_E_ARG;
 }
 
-// api_feed.cpp's next_base for one channel: nothing that still looks back reaches below it
+// How far the base of a channel's window may advance: nothing that still looks back reaches below it.
+//   the scan and the accept step of the next tiles: BUFFER_LEN behind the frontier (the accept window of an edge at the frontier
+//   begins BUFFER_LEN - 1 before it; the tile sums reach MATCH_LEN + 4 STRIDE - 2, direct_P of a maximum at the frontier MATCH_DEL + 4 STRIDE - 2)
+//   while the trigger is on: direct_P of the run's maximum so far (the next edge's maximum is that one or a later one; while the
+//   trigger is off every value since the last edge is at most `hi`, so the next run's maximum lies at or behind the frontier)
+//   the oldest preamble not yet decoded: its Schmidl-Cox body (the header and the demodulator read from sc_start + STRIDE on)
+//   mono input: the front end recomputes the stretch the last push ended in from its kept state (at most 256 + 64 samples before it)
 long long next_base(const BankChannel &k, const Lens &L, bool mono)
 {
 	long long lim = k.scanned - L.buffer_len;
@@ -248,7 +261,8 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 		max_tiles = std::max(max_tiles, nt);
 		at(P_REC_BASE, c) = k.n_acc;
 		at(P_REJ_BASE, c) = k.n_edges - k.n_acc;
-		// mono: the DC blocker's states of the blocks the push completed, then the analytic signal of the new samples (api_feed.cpp: front_end)
+		// mono: the DC blocker's states of the blocks the push completed, then the analytic signal of the new samples (the stretch the
+		// last push ended in is formed again from its start: the same values, and its new samples with them)
 		long long dct = 0, fen = 0;
 		if (mono && k.z_done != k.fed) {
 			if (k.fed / MONO_CK_LEN * MONO_CK_LEN > k.ck_done) {
@@ -288,7 +302,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 		b.ops += 2;
 	}
 	HIP_OK(hipGetLastError());
-	// ---- 3. mono input: every channel's DC-blocker states and analytic signal, each composed as a single feed composes it
+	// ---- 3. mono input: every channel's DC-blocker states and analytic signal, each composed from that channel's own positions alone
 	if (fe_total > 0) {
 		for (size_t c = 0; c < C; ++c) {
 			const BankChannel &k = b.ch[c];
@@ -322,7 +336,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 			const BankChannel &k = b.ch[c];
 			if (at(P_TILE_AT, c + 1) == at(P_TILE_AT, c))
 				continue;
-			// the lowest position the tiles, the accept step and direct_P read (api_feed.cpp: next_base)
+			// the lowest position the tiles, the accept step and direct_P read (see next_base)
 			long long lo = k.scanned - (L.buffer_len - 1);
 			if (k.carry.s == 1 && k.carry.i >= 0)
 				lo = std::min(lo, k.carry.i - (L.md + 4 * L.stride - 2));
@@ -516,7 +530,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 	return 0;
 }
 
-// the first max_records staged records leave; the rest wait, in order
+// the first max_records staged records leave; the rest wait, in order (record_channel / record_index: nullable, a feed has neither)
 void deliver(ofdmrx_handle *h, size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results, int32_t *record_channel, int64_t *record_index,
 	size_t *n_records, size_t *n_left)
 {
@@ -526,8 +540,10 @@ void deliver(ofdmrx_handle *h, size_t max_records, uint8_t *payload_out, ofdmrx_
 		const BankReady &q = b.ready.front();
 		std::memcpy(payload_out + k * PAYLOAD_BYTES, q.payload.data(), PAYLOAD_BYTES);
 		std::memcpy(results + k, &q.res, sizeof(Result));
-		record_channel[k] = q.channel;
-		record_index[k] = q.index;
+		if (record_channel)
+			record_channel[k] = q.channel;
+		if (record_index)
+			record_index[k] = q.index;
 		if (h->esn0_user) {
 			if (q.rows.size() == ROWS_MAX)
 				std::memcpy(h->esn0_user + k * ROWS_MAX, q.rows.data(), ROWS_MAX * sizeof(float));
@@ -540,21 +556,24 @@ void deliver(ofdmrx_handle *h, size_t max_records, uint8_t *payload_out, ofdmrx_
 	*n_left = b.ready.size();
 }
 
-int out_args(const ofdmrx_handle *h, size_t max_records, const void *payload, const void *results, const void *record_channel, const void *record_index,
-	const size_t *n_records, const size_t *n_left)
+int out_args(const ofdmrx_handle *h, size_t max_records, const void *payload, const void *results, const size_t *n_records, const size_t *n_left)
 {
-	if (!h || !n_records || !n_left || (max_records && (!payload || !results || !record_channel || !record_index)))
+	if (!h || !n_records || !n_left || (max_records && (!payload || !results)))
 		return OFDMRX_E_ARG;
 	return 0;
 }
 
-}  // namespace
+// the handle's open bank, if it was opened as the caller's kind (a feed or a bank); else nullptr
+ofdmrx_bank *live(ofdmrx_handle *h, bool as_feed)
+{
+	return (h && h->bank && h->bank->as_feed == as_feed) ? h->bank : nullptr;
+}
 
-extern "C" int ofdmrx_bank_begin(ofdmrx_handle *h, size_t n_channels, int fmt, int channels)
+int begin(ofdmrx_handle *h, size_t n_channels, int fmt, int channels, bool as_feed)
 {
 	if (!h || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channels < 1 || channels > 2 || n_channels < 1 || n_channels > 65535)
 		return OFDMRX_E_ARG;
-	if (h->feed || h->bank)
+	if (h->bank)                                                  // one feed or bank per handle
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	ofdmrx_bank *b = new (std::nothrow) ofdmrx_bank;
@@ -563,6 +582,7 @@ extern "C" int ofdmrx_bank_begin(ofdmrx_handle *h, size_t n_channels, int fmt, i
 	b->fmt = fmt;
 	b->channels = channels;
 	b->C = n_channels;
+	b->as_feed = as_feed;
 	b->ch.resize(n_channels);
 	b->carry_h.assign(2 * n_channels, StreamCarry{ 0, -INFINITY, -1, 0 });
 	int r = b->carry.ensure(2 * n_channels * sizeof(StreamCarry));
@@ -576,12 +596,41 @@ extern "C" int ofdmrx_bank_begin(ofdmrx_handle *h, size_t n_channels, int fmt, i
 	return 0;
 }
 
+// every channel that has not ended ends: the last partial tiles, every pending preamble; what is staged leaves, and with the last
+// record the bank goes
+int end(ofdmrx_handle *h, ofdmrx_bank &b, size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results, int32_t *record_channel,
+	int64_t *record_index, size_t *n_records, size_t *n_left)
+{
+	HIP_OK(hipSetDevice(h->cfg.device));
+	b.ops = 0;
+	if (!b.ending) {
+		std::vector<uint8_t> fin(b.C, 0);
+		for (size_t c = 0; c < b.C; ++c)
+			fin[c] = !b.ch[c].ended;
+		int r = bank_step(h, nullptr, 0, nullptr, fin);
+		if (r)
+			return r;
+		b.ending = true;
+	}
+	deliver(h, max_records, payload_out, results, record_channel, record_index, n_records, n_left);
+	if (*n_left == 0)
+		bank_free(h);
+	return 0;
+}
+
+}  // namespace
+
+extern "C" int ofdmrx_bank_begin(ofdmrx_handle *h, size_t n_channels, int fmt, int channels)
+{
+	return begin(h, n_channels, fmt, channels, false);
+}
+
 extern "C" int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t stride_bytes, const size_t *n_samples, const uint8_t *ends,
 	size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results, int32_t *record_channel, int64_t *record_index, size_t *n_records,
 	size_t *n_left)
 {
-	int r = out_args(h, max_records, payload_out, results, record_channel, record_index, n_records, n_left);
-	if (r || !n_samples || !h->bank)
+	int r = out_args(h, max_records, payload_out, results, n_records, n_left);
+	if (r || (max_records && (!record_channel || !record_index)) || !n_samples || !live(h, false))
 		return OFDMRX_E_ARG;
 	ofdmrx_bank &b = *h->bank;
 	const size_t unit = frame_bytes(b);
@@ -612,38 +661,77 @@ extern "C" int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t st
 extern "C" int ofdmrx_bank_end(ofdmrx_handle *h, size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results, int32_t *record_channel,
 	int64_t *record_index, size_t *n_records, size_t *n_left)
 {
-	int r = out_args(h, max_records, payload_out, results, record_channel, record_index, n_records, n_left);
-	if (r || !h->bank)
+	int r = out_args(h, max_records, payload_out, results, n_records, n_left);
+	if (r || (max_records && (!record_channel || !record_index)) || !live(h, false))
 		return OFDMRX_E_ARG;
-	ofdmrx_bank &b = *h->bank;
-	HIP_OK(hipSetDevice(h->cfg.device));
-	b.ops = 0;
-	if (!b.ending) {
-		std::vector<uint8_t> fin(b.C, 0);
-		for (size_t c = 0; c < b.C; ++c)
-			fin[c] = !b.ch[c].ended;
-		r = bank_step(h, nullptr, 0, nullptr, fin);
-		if (r)
-			return r;
-		b.ending = true;
-	}
-	deliver(h, max_records, payload_out, results, record_channel, record_index, n_records, n_left);
-	if (*n_left == 0)
-		bank_free(h);
-	return 0;
+	return end(h, *h->bank, max_records, payload_out, results, record_channel, record_index, n_records, n_left);
 }
 
 extern "C" long long ofdmrx_bank_resident_samples(ofdmrx_handle *h, size_t channel)
 {
-	return (h && h->bank && channel < h->bank->C) ? h->bank->ch[channel].fed - h->bank->ch[channel].base : OFDMRX_E_ARG;
+	const ofdmrx_bank *b = live(h, false);
+	return (b && channel < b->C) ? b->ch[channel].fed - b->ch[channel].base : OFDMRX_E_ARG;
 }
 
 extern "C" long long ofdmrx_bank_preambles(ofdmrx_handle *h, size_t channel)
 {
-	return (h && h->bank && channel < h->bank->C) ? h->bank->ch[channel].n_acc : OFDMRX_E_ARG;
+	const ofdmrx_bank *b = live(h, false);
+	return (b && channel < b->C) ? b->ch[channel].n_acc : OFDMRX_E_ARG;
 }
 
 extern "C" long long ofdmrx_bank_last_stage_ops(ofdmrx_handle *h)
 {
-	return (h && h->bank) ? h->bank->ops : OFDMRX_E_ARG;
+	return live(h, false) ? h->bank->ops : OFDMRX_E_ARG;
+}
+
+// ---- ofdmrx_feed_*: one recording decoded block by block as it arrives - a bank of one channel, whose records
+// come without channel and index
+extern "C" int ofdmrx_feed_begin(ofdmrx_handle *h, int fmt, int channels)
+{
+	return begin(h, 1, fmt, channels, true);
+}
+
+extern "C" int ofdmrx_feed_push(ofdmrx_handle *h, const void *samples, size_t n_samples, size_t max_frames, uint8_t *payload_out,
+	ofdmrx_frame_result *results, size_t *n_records, size_t *n_left)
+{
+	constexpr size_t PUSH_SLICE = (size_t)1 << 26;                // (the longest share a bank's channel takes in one step)
+	int r = out_args(h, max_frames, payload_out, results, n_records, n_left);
+	if (r || (n_samples && !samples) || !live(h, true))
+		return OFDMRX_E_ARG;
+	ofdmrx_bank &b = *h->bank;
+	const size_t unit = frame_bytes(b);
+	if (n_samples && (b.ending || (size_t)samples % unit))
+		return OFDMRX_E_ARG;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	b.ops = 0;
+	if (!b.ending) {
+		const std::vector<uint8_t> fin(1, 0);
+		size_t done = 0;
+		do {                                                      // (a zero-length push still takes what has become due)
+			const size_t n = std::min(PUSH_SLICE, n_samples - done);
+			r = bank_step(h, (const char *)samples + done * unit, 0, &n, fin);
+			if (r)
+				return r;
+			done += n;
+		} while (done < n_samples);
+	}
+	deliver(h, max_frames, payload_out, results, nullptr, nullptr, n_records, n_left);
+	return 0;
+}
+
+extern "C" int ofdmrx_feed_end(ofdmrx_handle *h, size_t max_frames, uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_records,
+	size_t *n_left)
+{
+	int r = out_args(h, max_frames, payload_out, results, n_records, n_left);
+	if (r || !live(h, true))
+		return OFDMRX_E_ARG;
+	return end(h, *h->bank, max_frames, payload_out, results, nullptr, nullptr, n_records, n_left);
+}
+
+// Every kernel of the record pipeline reads inside the frame (the demodulator's last symbol ends on its last sample): no lag
+extern "C" long long ofdmrx_feed_lag(ofdmrx_handle *h) { return live(h, true) ? 0 : OFDMRX_E_ARG; }
+
+extern "C" long long ofdmrx_feed_resident_samples(ofdmrx_handle *h)
+{
+	return live(h, true) ? h->bank->ch[0].fed - h->bank->ch[0].base : OFDMRX_E_ARG;
 }

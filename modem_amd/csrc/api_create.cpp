@@ -151,8 +151,6 @@ extern "C" void ofdmrx_destroy(ofdmrx_handle *h)
 
 	if (h->stream)
 		(void)hipStreamSynchronize(h->stream);
-	if (h->feed)
-		feed_free(h);
 	if (h->bank)
 		bank_free(h);
 	for (hipStream_t sx : { h->stream_b, h->stream_fin, h->stream_c })

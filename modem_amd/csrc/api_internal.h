@@ -225,9 +225,8 @@ struct ofdmrx_handle {
 	std::vector<int> sxs_len_h;           // (host copies the uploads read: they live as long as the handle)
 	std::vector<long long> sxs_tile0_h, sxs_given0_h, sxs_counts_h;
 	long sxs_edge_cap = 0;    // every recording's share of the edge buffer
-	struct ofdmrx_feed *feed = nullptr;   // the open live feed (api_feed.cpp), one per handle
-	struct ofdmrx_bank *bank = nullptr;   // the open bank of live channels (api_bank.cpp), one per handle, never beside a feed
-	bool busy_live() const { return feed || bank; }   // a handle with an open feed or bank decodes nothing else
+	struct ofdmrx_bank *bank = nullptr;   // the open bank of live channels or - a bank of one - the open feed (api_bank.cpp): one per handle
+	bool busy_live() const { return bank != nullptr; }   // a handle with an open feed or bank decodes nothing else
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -266,5 +265,4 @@ int finish_call(ofdmrx_handle *h, int r);                                       
 // channel q would lie at fb.samples + org[q] bytes and the channel has len[q] sample frames so far (kernels.h: WindowBatch)
 struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; const long long *org = nullptr; const long long *len = nullptr; };
 int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources *srcs = nullptr);
-void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank and its windows go
-void feed_free(ofdmrx_handle *h);                                                           // api_feed.cpp: the open feed and its window go
+void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank (or feed) and its windows go

@@ -8,9 +8,9 @@
 //   k_stream_tile<.., true>   the tiles again, now with their incoming state: falling edges, t_max, index_max, in stream order
 //   k_stream_accept           decode.cc:110-151 for every edge (sc_accept_wg, shared with k_sync_accept)
 //   k_stream_records          a scan over accept / reject: record indices, cumulative rejects, the SyncState of every record
-// The live feed (api_feed.cpp) runs the same kernels push by push over a window of the stream: the WIN forms take
-// where the push's first tile / block lies in the stream and the state the last push left, and compute from the same absolute
-// positions as the one-call forms (whose instantiations are unchanged).
+// Live channels (api_bank.cpp; a feed is a bank of one channel) run the same kernels push by push over a
+// window of every channel's stream: the FB = WindowBatch forms take the channel from blockIdx.y - where the push's first tile / block
+// lies in its stream and the state its last push left - and compute from the same absolute positions as the one-call forms.
 // Many recordings in one call (api_streams.cpp): the FB = SourceBatch forms take the recording from blockIdx.y - its
 // own base, length and places in the per-tile and edge arrays - and run what the one-call forms run on it; the scans over tiles
 // are one workgroup per recording, so nothing is carried from one recording into the next.
@@ -49,14 +49,15 @@ struct Affine { double v, w; };                               // x -> w x + v
 __device__ __forceinline__ Affine aff_then(Affine l, Affine r) { return Affine{ r.v + r.w * l.v, l.w * r.w }; }
 
 // PASS 0: the state each tile ends on from a zero state; PASS 1: the kept states from the tile's true entry state tile_in[t]
-// WIN (the live feed): tile 0 starts at the absolute position `origin` (a multiple of MONO_CK), fb.samples and ck are
-// the addresses position 0 / state 0 would have, fb.samples_per_frame the samples fed so far; only the states of complete blocks
-// of MONO_CK samples are kept (ck_n is unused)
 // FB = SourceBatch: tile blockIdx.x of recording blockIdx.y; ck_n is then the states kept per recording (the row length of ck)
-template <int PASS, bool WIN = false, class FB = FrameBatch>
+// FB = WindowBatch (live channels): tile 0 of channel blockIdx.y starts at the absolute position fb.dc_from[q] (a
+// multiple of MONO_CK), the channel's samples and states are addressed from where position 0 / state 0 would lie, fb.len[q] is the
+// samples fed so far; only the states of complete blocks of MONO_CK samples are kept (ck_n is unused)
+template <int PASS, class FB = FrameBatch>
 __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *__restrict__ tile_end, const double *__restrict__ tile_in,
-	double *__restrict__ ck, int ck_n, long origin = 0)
+	double *__restrict__ ck, int ck_n)
 {
+	long origin = 0;
 	const int tid = threadIdx.x;
 	const long t = blockIdx.x;
 	MonoFrame fr{ (const char *)fb.samples, fb.fmt, fb.samples_per_frame, nullptr };
@@ -71,8 +72,7 @@ __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *_
 		ck += (size_t)q * ck_n;
 		ck_n = (int)((fr.n + MONO_CK - 1) / MONO_CK);               // (mono_ck_per_frame)
 	}
-	if constexpr (bank_v<FB>) {                                   // WIN, channel blockIdx.y: its window, its tiles from where its DC blocker stands
-		static_assert(WIN, "a bank reads windows");
+	if constexpr (bank_v<FB>) {                                   // channel blockIdx.y: its window, its tiles from where its DC blocker stands
 		const int q = blockIdx.y;
 		if ((long long)t >= fb.dc_at[q + 1] - fb.dc_at[q])          // (uniform)
 			return;
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *_
 	}
 	__shared__ Affine sh[256];
 	const double a = (double)co.dc_a, g = (double)co.dc_b * (1.0 - a) * (double)fr.scale();
-	const long s0 = (WIN ? origin : 0) + t * 4096 + (long)tid * 16;
+	const long s0 = (bank_v<FB> ? origin : 0) + t * 4096 + (long)tid * 16;
 	double sl = 0.0;
 	float x8[8];
 	fr.load8(s0, x8);
@@ -100,18 +100,15 @@ __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *_
 			tile_end[t] = me.v;
 	} else {
 		const double s_true = me.v + mono_pow(a, 16 * (tid + 1)) * tile_in[t];
-		const long m = (WIN ? origin / MONO_CK : 0) + t * (4096 / MONO_CK) + (tid >> 2);    // this thread ends sample 16 tid + 15 of its tile
-		if ((tid & 3) == 3 && (WIN ? (m + 1) * MONO_CK <= fr.n : m < ck_n))
+		const long m = (bank_v<FB> ? origin / MONO_CK : 0) + t * (4096 / MONO_CK) + (tid >> 2);    // this thread ends sample 16 tid + 15 of its tile
+		if ((tid & 3) == 3 && (bank_v<FB> ? (m + 1) * MONO_CK <= fr.n : m < ck_n))
 			ck[m] = s_true;
 	}
 }
 
 // the tiles' entry states C_0 = 0, C_{t+1} = tile_end[t] + a^4096 C_t: one workgroup, a range of tiles per thread composed as an
 // affine map, an exclusive scan of the maps, then each range in turn
-// entry (WIN; nullable): the state before the first tile, left by an earlier push
-template <bool WIN = false>
-__global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *__restrict__ tile_end, double *__restrict__ tile_in, long ntiles,
-	const double *__restrict__ entry = nullptr)
+__global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *__restrict__ tile_end, double *__restrict__ tile_in, long ntiles)
 {
 	const int tid = threadIdx.x;
 	__shared__ Affine sh[1024];
@@ -122,16 +119,12 @@ __global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *_
 		f = aff_then(f, Affine{ tile_end[k], A });
 	block_scan_incl<1024>(f, sh, tid, aff_then);
 	double c = tid ? sh[tid - 1].v : 0.0;                     // the maps applied to C_0 = 0
-	if constexpr (WIN) {
-		const double c0 = entry ? *entry : 0.0;                   // ... to C_0 = the entry state
-		c = tid ? sh[tid - 1].v + sh[tid - 1].w * c0 : c0;
-	}
 	for (long k = k0; k < k1; ++k) {
 		tile_in[k] = c;
 		c = tile_end[k] + A * c;
 	}
 }
-// Many recordings: one workgroup per recording runs k_sdc_scan<false> on that recording's tiles - the same ranges per thread, the
+// Many recordings: one workgroup per recording runs k_sdc_scan on that recording's tiles - the same ranges per thread, the
 // same order of composition as a call with that recording alone, so the same doubles.  (A kernel of its own rather than a shared
 // body: k_sdc_scan's code stays what it was.)
 __global__ __launch_bounds__(1024) void k_sdcs_scan(FrontCoef co, const double *__restrict__ tile_end_all, double *__restrict__ tile_in_all,
@@ -155,9 +148,10 @@ __global__ __launch_bounds__(1024) void k_sdcs_scan(FrontCoef co, const double *
 	}
 }
 
-// Many live channels: one workgroup per channel runs k_sdc_scan<true> on the tiles that channel brings in this push - the same
-// ranges per thread, the same order of composition as a single feed with that channel's push lengths, so the same doubles - from
-// the state kept before the channel's first tile.  (A kernel of its own, as k_sdcs_scan is.)
+// Many live channels: one workgroup per channel runs k_sdc_scan's scan on the tiles that channel brings in this push - the same
+// ranges per thread, the same order of composition whatever the other channels bring, so the same doubles - with the maps applied
+// to the state kept before the channel's first tile (left by its earlier pushes) instead of 0.  (A kernel of its own, as
+// k_sdcs_scan is.)
 __global__ __launch_bounds__(1024) void k_bank_sdc_scan(WindowBatch fb, FrontCoef co, const double *__restrict__ tile_end_all, double *__restrict__ tile_in_all,
 	const double *__restrict__ ck_all)
 {
@@ -176,7 +170,7 @@ __global__ __launch_bounds__(1024) void k_bank_sdc_scan(WindowBatch fb, FrontCoe
 	for (long k = k0; k < k1; ++k)
 		f = aff_then(f, Affine{ tile_end[k], A });
 	block_scan_incl<1024>(f, sh, tid, aff_then);
-	const double c0 = entry ? *entry : 0.0;
+	const double c0 = entry ? *entry : 0.0;                       // the maps applied to C_0 = the entry state
 	double c = tid ? sh[tid - 1].v + sh[tid - 1].w * c0 : c0;
 	for (long k = k0; k < k1; ++k) {
 		tile_in[k] = c;
@@ -188,32 +182,23 @@ void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_e
 {
 	const long ntiles = (fb.samples_per_frame + 4095) / 4096;
 	const int ck_n = mono_ck_per_frame(fb.samples_per_frame);
-	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n, 0L);
-	hipLaunchKernelGGL(k_sdc_scan<false>, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles, nullptr);
-	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n, 0L);
+	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
+	hipLaunchKernelGGL(k_sdc_scan, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles);
+	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
 }
 void launch_streams_dc(hipStream_t s, int n_src, long max_len, SourceBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, int ck_per_src)
 {
 	const dim3 grid((unsigned)((max_len + 4095) / 4096), (unsigned)n_src);
-	hipLaunchKernelGGL((k_sdc_tile<0, false, SourceBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_per_src, 0L);
+	hipLaunchKernelGGL((k_sdc_tile<0, SourceBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_per_src);
 	hipLaunchKernelGGL(k_sdcs_scan, dim3((unsigned)n_src), dim3(1024), 0, s, co, tile_end, tile_in, fb.tile0);
-	hipLaunchKernelGGL((k_sdc_tile<1, false, SourceBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_per_src, 0L);
+	hipLaunchKernelGGL((k_sdc_tile<1, SourceBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_per_src);
 }
-void launch_stream_dc_window(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, long origin)
-{
-	const long ntiles = (fb.samples_per_frame - origin + 4095) / 4096;
-	const double *entry = origin > 0 ? ck + origin / MONO_CK - 1 : nullptr;
-	hipLaunchKernelGGL((k_sdc_tile<0, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, origin);
-	hipLaunchKernelGGL(k_sdc_scan<true>, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles, entry);
-	hipLaunchKernelGGL((k_sdc_tile<1, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, origin);
-}
-
 void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck)
 {
 	const dim3 grid((unsigned)max_tiles, (unsigned)n_ch);
-	hipLaunchKernelGGL((k_sdc_tile<0, true, WindowBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, 0L);
+	hipLaunchKernelGGL((k_sdc_tile<0, WindowBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0);
 	hipLaunchKernelGGL(k_bank_sdc_scan, dim3((unsigned)n_ch), dim3(1024), 0, s, fb, co, tile_end, tile_in, ck);
-	hipLaunchKernelGGL((k_sdc_tile<1, true, WindowBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0, 0L);
+	hipLaunchKernelGGL((k_sdc_tile<1, WindowBatch>), grid, dim3(256), 0, s, fb, co, tile_end, tile_in, ck, 0);
 }
 
 // ---------------------------------------------------------------- the trigger as a scan
@@ -287,17 +272,18 @@ __device__ __forceinline__ void tile_trigger(TrigShared &sh, const int (&cls)[SP
 
 // EMIT = false: the timing metric of the tile and its function (StreamFn) for both incoming states; EMIT = true: the same metric and
 // the tile's falling edges from its incoming StreamCarry.  GIVEN: the metric is a caller's sequence (ofdmrx_debug_stream_edges).
-// WIN (the live feed): block b is tile tile0 + b of the stream - the same absolute sample positions as in a one-call scan, so the same
-// metric values - fb.samples is the address position 0 would have, n the samples fed so far; fn / carry are indexed by b, and the
-// edge positions count from the push's first edge (the carry that enters a push has count 0)
 // FB = SourceBatch: tile blockIdx.x of recording blockIdx.y, read from that recording's base with its length (n is unused): a position
 // below 0 or at or past the length reads as zero, exactly as in a call with that recording alone; edges is [recordings][cap]
-// FB = WindowBatch (with WIN): tile fb.tile0[q] + blockIdx.x of the live channel q = blockIdx.y (n and tile0 are unused); edges is [channels][cap]
-template <int RATE, bool GIVEN, bool EMIT, bool WIN = false, class FB = FrameBatch>
+// FB = WindowBatch: block b of the live channel q = blockIdx.y is tile fb.tile0[q] + b of its stream - the same absolute sample
+// positions as in a one-call scan, so the same metric values - read from where the channel's position 0 would lie, with the samples
+// fed so far as its length (n is unused); fn / carry are indexed from fb.tile_at[q], edges is [channels][cap], and the edge positions
+// count from the push's first edge (the carry that enters a push has count 0)
+template <int RATE, bool GIVEN, bool EMIT, class FB = FrameBatch>
 __global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
-	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap, long long tile0 = 0)
+	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap)
 {
 	const void *samples = fb.samples;
+	long long tile0 = 0;
 	if constexpr (many_v<FB>) {
 		const int q = blockIdx.y;
 		n = fb.src_len[q];
@@ -310,8 +296,8 @@ __global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restr
 		if constexpr (GIVEN)
 			given += fb.given0[q];
 	}
-	if constexpr (bank_v<FB>) {                                   // WIN, channel blockIdx.y: its window, its tiles of this push, its places
-		static_assert(WIN && !GIVEN, "a bank scans windows of sample streams");
+	if constexpr (bank_v<FB>) {                                   // channel blockIdx.y: its window, its tiles of this push, its places
+		static_assert(!GIVEN, "a bank scans windows of sample streams");
 		const int q = blockIdx.y;
 		if ((long long)blockIdx.x >= fb.tile_at[q + 1] - fb.tile_at[q])   // (uniform: this channel brings fewer tiles)
 			return;
@@ -327,7 +313,7 @@ __global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restr
 	constexpr int D = RC::BUFFER_LEN - 1 - (RC::SEARCH_POS + HS);   // P at time t: its newest pair is (t - D, t - D + HS)
 	constexpr int L = STREAM_TILE + ML - 1, PM = (L + 255) / 256;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const long long T0 = ((long long)blockIdx.x + (WIN ? tile0 : 0)) * STREAM_TILE;
+	const long long T0 = ((long long)blockIdx.x + (bank_v<FB> ? tile0 : 0)) * STREAM_TILE;
 	const float lo = (float)(0.17 * ML), hi = (float)(0.19 * ML);   // decode.cc:76
 	__shared__ TrigShared tsh;
 	float v[SPT];
@@ -506,7 +492,8 @@ __device__ __forceinline__ StreamCarry fn_apply(const StreamFn &f, StreamCarry c
 	return o;
 }
 
-// WIN: the scan starts from the carry the previous push left (*c_in, its edge count taken as 0) and leaves *c_out for the next
+// WIN (a live channel): the scan starts from the carry the previous push left (*c_in, its edge count taken as 0) and leaves *c_out
+// for the next
 template <bool WIN>
 __device__ __forceinline__ void fn_scan_wg(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts,
 	const StreamCarry *__restrict__ c_in, StreamCarry *__restrict__ c_out)
@@ -542,11 +529,9 @@ __device__ __forceinline__ void fn_scan_wg(const StreamFn *__restrict__ fn, long
 			*c_out = c;
 	}
 }
-template <bool WIN = false>
-__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts,
-	const StreamCarry *__restrict__ c_in = nullptr, StreamCarry *__restrict__ c_out = nullptr)
+__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts)
 {
-	fn_scan_wg<WIN>(fn, ntiles, carry, counts, c_in, c_out);
+	fn_scan_wg<false>(fn, ntiles, carry, counts, nullptr, nullptr);
 }
 // The segmented scan: one workgroup per recording composes that recording's tiles alone, from the initial carry (trigger off, no
 // maximum, no edges) - the reset at a recording's start is that nothing of its neighbour is ever composed with it.
@@ -579,15 +564,15 @@ void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *giv
 {
 	const long ntiles = (n + STREAM_TILE - 1) / STREAM_TILE;
 	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
 	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
 	}
-	hipLaunchKernelGGL(k_stream_fn_scan<false>, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts, nullptr, nullptr);
+	hipLaunchKernelGGL(k_stream_fn_scan, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts);
 	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
 	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
 	}
 }
 
@@ -596,46 +581,40 @@ void launch_streams_scan(hipStream_t s, int rate, int n_src, long max_len, Sourc
 {
 	const dim3 grid((unsigned)((max_len + STREAM_TILE - 1) / STREAM_TILE), (unsigned)n_src);
 	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap));
 	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap));
 	}
 	hipLaunchKernelGGL(k_streams_fn_scan, dim3((unsigned)n_src), dim3(1024), 0, s, fn, fb.tile0, carry, counts);
 	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap));
 	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, false, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap, 0LL));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, SourceBatch>), grid, dim3(256), 0, s, fb, given, 0L, fn, carry, edges, cap));
 	}
-}
-
-void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, long long tile0, long ntiles, StreamFn *fn, StreamCarry *carry,
-	const StreamCarry *c_in, StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts)
-{
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, nullptr, n, fn, carry, edges, cap, tile0));
-	hipLaunchKernelGGL(k_stream_fn_scan<true>, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts, c_in, c_out);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, nullptr, n, fn, carry, edges, cap, tile0));
 }
 
 void launch_bank_scan(hipStream_t s, int rate, int n_ch, long max_tiles, WindowBatch fb, StreamFn *fn, StreamCarry *carry, const StreamCarry *c_in,
 	StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts)
 {
 	const dim3 grid((unsigned)max_tiles, (unsigned)n_ch);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, true, WindowBatch>), grid, dim3(256), 0, s, fb, nullptr, 0L, fn, carry, edges, cap, 0LL));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false, WindowBatch>), grid, dim3(256), 0, s, fb, nullptr, 0L, fn, carry, edges, cap));
 	hipLaunchKernelGGL(k_bank_fn_scan, dim3((unsigned)n_ch), dim3(1024), 0, s, fn, fb.tile_at, carry, counts, c_in, c_out);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, true, WindowBatch>), grid, dim3(256), 0, s, fb, nullptr, 0L, fn, carry, edges, cap, 0LL));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true, WindowBatch>), grid, dim3(256), 0, s, fb, nullptr, 0L, fn, carry, edges, cap));
 }
 
 // ---------------------------------------------------------------- accept, records
 constexpr int ACCEPT_GRID = 2048;
-// WIN (the live feed): fb.samples is the address position 0 would have and only the positions from win_lo on are in memory.  The host
-// has checked that no edge of this push reads below it (api_feed.cpp); an edge that would is left rejected and reported in counts[2]
 // FB = SourceBatch: the edges of recording blockIdx.y (edges: [recordings][cap], counts: [recordings][2]), read from its base with its length
-template <int RATE, bool WIN = false, class FB = FrameBatch>
+// FB = WindowBatch: the edges of the live channel blockIdx.y, of whose stream only the positions from fb.lo[q] on are in memory.  The
+// host has checked that no edge of this push reads below it (api_bank.cpp); an edge that would is left rejected and reported in
+// fb.below[q]
+template <int RATE, class FB = FrameBatch>
 __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restrict__ tw, const cf *__restrict__ kern,
-	StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts, long long win_lo = 0)
+	StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts)
 {
 	const void *samples = fb.samples;
 	long n_src = fb.samples_per_frame;
+	long long win_lo = 0;
 	if constexpr (many_v<FB>) {
 		const int q = blockIdx.y;
 		samples = (const char *)fb.samples + (size_t)q * fb.frame_stride_bytes;
@@ -644,7 +623,6 @@ __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restri
 		counts += 2 * (size_t)q;
 	}
 	if constexpr (bank_v<FB>) {                                   // the edges of the live channel blockIdx.y, read through its window
-		static_assert(WIN, "a bank reads windows");
 		const int q = blockIdx.y;
 		samples = batch_base(fb, q);
 		n_src = (long)fb.len[q];
@@ -665,17 +643,13 @@ __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restri
 	for (long long e = blockIdx.x; e < ne; e += gridDim.x) {
 		__syncthreads();
 		StreamEdge ed = edges[e];
-		if constexpr (WIN) {
+		if constexpr (bank_v<FB>) {
 			// the lowest positions direct_P and sc_accept_wg read for this edge
 			const long long lo_p = ed.t_max - MATCH_DEL - (BUFFER_LEN - 1 - (SEARCH_POS + HALF_LEN)) - (HALF_LEN - 1);
 			const long long lo_w = ed.g - (BUFFER_LEN - 1) + (SEARCH_POS - ed.index_max) + HALF_LEN;
 			if (win_lo > 0 && (lo_p < win_lo || lo_w < win_lo)) {     // (uniform)
-				if (tid == 0) {
-					if constexpr (bank_v<FB>)
-						fb.below[blockIdx.y] = 1;
-					else
-						counts[2] = 1;
-				}
+				if (tid == 0)
+					fb.below[blockIdx.y] = 1;
 				continue;
 			}
 		}
@@ -715,28 +689,22 @@ __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restri
 void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
 {
 	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, false>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, 0LL));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL(k_stream_accept<RATE>, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts));
 }
 void launch_streams_accept(hipStream_t s, int rate, int n_src, SourceBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
 {
 	// (workgroups per recording: the one-call grid shared out, every recording's edges strided over its own)
 	long per = ACCEPT_GRID / n_src < cap ? ACCEPT_GRID / n_src : cap;
 	per = per > 0 ? per : 1;
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, false, SourceBatch>), dim3((unsigned)per, (unsigned)n_src), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
-		edges, cap, counts, 0LL));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, SourceBatch>), dim3((unsigned)per, (unsigned)n_src), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
+		edges, cap, counts));
 }
-void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts, long long win_lo)
-{
-	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, true>), dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts, win_lo));
-}
-
 void launch_bank_accept(hipStream_t s, int rate, int n_ch, WindowBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
 {
 	long per = ACCEPT_GRID / n_ch < cap ? ACCEPT_GRID / n_ch : cap;
 	per = per > 0 ? per : 1;
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, true, WindowBatch>), dim3((unsigned)per, (unsigned)n_ch), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
-		edges, cap, counts, 0LL));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, WindowBatch>), dim3((unsigned)per, (unsigned)n_ch), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
+		edges, cap, counts));
 }
 
 // rec_src (nullable) / src: the recording every record written reads (many recordings in one call)
@@ -763,7 +731,7 @@ __device__ __forceinline__ void stream_records_wg(int buffer_len, const StreamEd
 			st.found = 1;
 			st.symbol_pos = ed.symbol_pos;
 			st.cfo_rad = ed.cfo_rad;
-			st.rejects = (int)(rej_base + (e - k));               // the edges before it that decode.cc:140-145 rejected (rej_base: in earlier pushes of a feed)
+			st.rejects = (int)(rej_base + (e - k));               // the edges before it that decode.cc:140-145 rejected (rej_base: in earlier pushes of a live channel)
 			st.skip_left = 0;
 			st.status = 1;
 			st.oper_mode = 0;
@@ -844,12 +812,11 @@ __global__ __launch_bounds__(1024) void k_bank_records(int buffer_len, const Str
 	stream_records_wg(buffer_len, edges + (size_t)q * cap, cap, counts + 2 * (size_t)q, rec + at, (long)room, rec_base[q], rej_base[q], rec_src + at, q);
 }
 
-void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec,
-	long long rec_base, long long rej_base)
+void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec)
 {
 	int buffer_len = 0;
 	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
-	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec, rec_base, rej_base);
+	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec, 0LL, 0LL);
 }
 void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge *edges, long cap, long long *counts, long long *first,
 	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec)

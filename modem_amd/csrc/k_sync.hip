@@ -111,17 +111,18 @@ __global__ __launch_bounds__(256) void k_mono_carries(FrameBatch fb, FrontCoef c
 // starts on the kept state before it - four spans of 2048 samples cover a stretch and the filter's reach + the 63 samples back to
 // that state
 constexpr int FE_STRETCH = 4 * 2048 - 256;
-// WIN (the live feed, one frame): block b is stretch stretch0 + b; fb.samples, ma.ck and z_all are the addresses position 0 would have
 // FB = SourceBatch (many recordings in one call): frame f is source f with its own length; the grid covers the longest one
-// FB = WindowBatch (with WIN; many live channels): block b of channel f = blockIdx.y is that channel's stretch fb.fe0[f] + b
-template <int RATE, bool WIN = false, class FB = FrameBatch>
-__global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FB fb, MonoArgs ma, cf *__restrict__ z_all, long stretch0 = 0)
+// FB = WindowBatch (live channels): block b of channel f = blockIdx.y is that channel's stretch fb.fe0[f] + b; its
+// samples, kept states and analytic signal are addressed from where position 0 would lie (mono_front.h: mono_frame, mono_z)
+template <int RATE, class FB = FrameBatch>
+__global__ __launch_bounds__(256, RATE == 8000 ? 4 : 5) void k_front_end(FB fb, MonoArgs ma, cf *__restrict__ z_all)
 {
 	static_assert(MonoCfg<RATE>::REACH + MONO_CK <= 256, "a stretch and its lead-in fit four spans");
 	const int f = blockIdx.y, tid = threadIdx.x;
+	long stretch0 = 0;
 	if constexpr (std::is_same<FB, WindowBatch>::value)
 		stretch0 = (long)fb.fe0[blockIdx.y];
-	const long lo = ((long)blockIdx.x + (WIN ? stretch0 : 0)) * FE_STRETCH;
+	const long lo = ((long)blockIdx.x + stretch0) * FE_STRETCH;
 	__shared__ typename MonoCover<RATE, 256>::Shared msh;
 	MonoCover<RATE, 256> mc;
 	if constexpr (std::is_same<FB, SourceBatch>::value) {
@@ -593,22 +594,18 @@ void launch_front_end(hipStream_t s, int rate, int n, FrameBatch fb, MonoArgs ma
 		fbq.samples = (const char *)fb.samples + (size_t)f0 * fb.frame_stride_bytes;
 		MonoArgs maq = ma;
 		maq.ck = ma.ck + (size_t)f0 * ma.ck_per_frame;
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, false>), dim3(stretches, nf), dim3(256), 0, s, fbq, maq, z + (size_t)f0 * fb.samples_per_frame, 0L));
+		RX_RATE_SWITCH(rate, hipLaunchKernelGGL(k_front_end<RATE>, dim3(stretches, nf), dim3(256), 0, s, fbq, maq, z + (size_t)f0 * fb.samples_per_frame));
 	}
 }
 void launch_streams_front(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, MonoArgs ma, cf *z)
 {
 	const unsigned stretches = (unsigned)((max_len + FE_STRETCH - 1) / FE_STRETCH);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, false, SourceBatch>), dim3(stretches, (unsigned)n_src), dim3(256), 0, s, fb, ma, z, 0L));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, SourceBatch>), dim3(stretches, (unsigned)n_src), dim3(256), 0, s, fb, ma, z));
 }
 long front_end_stretch() { return FE_STRETCH; }
-void launch_front_end_window(hipStream_t s, int rate, FrameBatch fb, MonoArgs ma, cf *z, long stretch0, long n_stretch)
-{
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, true>), dim3((unsigned)n_stretch, 1), dim3(256), 0, s, fb, ma, z, stretch0));
-}
 void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z)
 {
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, true, WindowBatch>), dim3((unsigned)max_stretch, (unsigned)n_ch), dim3(256), 0, s, fb, ma, z, 0L));
+	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_front_end<RATE, WindowBatch>), dim3((unsigned)max_stretch, (unsigned)n_ch), dim3(256), 0, s, fb, ma, z));
 }
 #define SYNC_SPLIT_ROUNDS 2   // rates above 8 kHz: scan + accept pairs before the one-wave catch-all (a frame needs the catch-all only
                               // after that many rejected triggers; finished frames leave every later launch at once)

@@ -24,7 +24,7 @@ struct SourceBatch : FrameBatch {
 	const long long *tile0;        // the stream scan: [sources + 1] first tile of every source in the per-tile arrays (a running sum)
 	const long long *given0;       // ofdmrx_debug_streams_edges: [sources] where its sequence starts in the packed timing values
 };
-// Many live channels in one push (ofdmrx_bank_*): channel q is a WINDOW of its stream.  Position 0 of channel q would
+// Live channels in one push (ofdmrx_bank_*, and ofdmrx_feed_* as a bank of one): channel q is a WINDOW of its stream.  Position 0 of channel q would
 // lie at samples + org[q] (bytes; the channel's place in the slab minus its window's base, so it may be negative), the channel has
 // been fed len[q] sample frames and its window holds the positions from lo[q] on.  The scan of a push takes the tiles tile0[q] ..
 // of channel q, tile_at[q + 1] - tile_at[q] of them, at tile_at[q] in the per-tile arrays.  Frame f of a record launch reads
@@ -290,23 +290,8 @@ void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *giv
 	StreamEdge *edges, long cap, long long *counts);
 // decode.cc:110-151 for every edge (of the min(counts[0], cap) written), then the records: counts[1] = accepted edges, rec[k] = the
 // SyncState that k_header finds for the (k+1)-th accepted edge after a round with skip_left = 0 (k < max_rec)
-// rec_base / rej_base: records / rejected edges before the first edge (a feed's earlier pushes)
 void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
-void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec,
-	long long rec_base = 0, long long rej_base = 0);
-// ---- the live feed (api_feed.cpp): the same kernels over a WINDOW of the stream.  fb.samples (and ck, z) are the
-// addresses position 0 would have - the window's buffer minus its base - and fb.samples_per_frame the samples fed so far; the host
-// checks before every launch that the window holds every position the launch reads below that.
-// the DC blocker's states of the complete blocks of [origin, fb.samples_per_frame), origin a multiple of 64, from the state kept before origin
-void launch_stream_dc_window(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, long origin);
-// the analytic signal of the stretches stretch0 .. stretch0 + n_stretch - 1 (k_sync.hip: FE_STRETCH samples each, from position 0)
-long front_end_stretch();
-void launch_front_end_window(hipStream_t s, int rate, FrameBatch fb, MonoArgs ma, cf *z, long stretch0, long n_stretch);
-// tiles tile0 .. tile0 + ntiles - 1 from the carry *c_in (count taken as 0); *c_out: the carry behind them; counts[0]: their edges
-void launch_stream_scan_window(hipStream_t s, int rate, FrameBatch fb, long n, long long tile0, long ntiles, StreamFn *fn, StreamCarry *carry,
-	const StreamCarry *c_in, StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts);
-// counts[2] is set when an edge would read below win_lo (it is then left rejected: an internal error)
-void launch_stream_accept_window(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts, long long win_lo);
+void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec);
 
 // ---- many recordings in one call (api_streams.cpp): the same scan with the recording as a second grid dimension.
 // Every recording is scanned from its own position 0 with its own tile count, and nothing crosses from one to the next: what
@@ -325,9 +310,14 @@ void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge
 	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec);
 
 
-// ---- many live channels in one push (api_bank.cpp): the window forms with the channel as the second grid dimension.
+// ---- live channels (api_bank.cpp; a feed is a bank of one channel): the same kernels over a WINDOW of every
+// channel's stream, with the channel as the second grid dimension.  A channel's samples (and ck, z) are addressed from where its
+// position 0 would lie - its place in the slab minus its window's base - with the samples fed so far as its length; the host checks
+// before every launch that the window holds every position the launch reads below that.
 // Every array is per channel: edges [n_ch][cap], counts [n_ch][2], c_in / c_out [n_ch] (a channel without tiles in this push keeps
-// its carry).  max_tiles: the most tiles any channel brings (the grids' first dimension).  The caller clears counts and fb.below
+// its carry).  max_tiles: the most tiles any channel brings (the grids' first dimension).  The caller clears counts and fb.below.
+// The scan of channel q takes its tiles fb.tile0[q] .. from the carry c_in[q] (count taken as 0) and leaves c_out[q] behind them;
+// counts[q][0]: their edges.  fb.below[q] is set when an edge would read below fb.lo[q] (it is then left rejected: an internal error)
 void launch_bank_scan(hipStream_t s, int rate, int n_ch, long max_tiles, WindowBatch fb, StreamFn *fn, StreamCarry *carry, const StreamCarry *c_in,
 	StreamCarry *c_out, StreamEdge *edges, long cap, long long *counts);
 void launch_bank_accept(hipStream_t s, int rate, int n_ch, WindowBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
@@ -340,9 +330,11 @@ void launch_bank_records(hipStream_t s, int rate, int n_ch, const StreamEdge *ed
 // samples: packed that way by the host).  max_bytes: the longest range
 void launch_bank_copy(hipStream_t s, int n_ch, int planes, size_t plane_stride, long long max_bytes, const long long *src, const long long *dst,
 	const long long *bytes);
-// mono input: the window forms of the DC blocker and the front end with the channel as the second grid dimension.  Channel q's DC
-// blocker resumes at fb.dc_from[q] with fb.dc_at[q + 1] - fb.dc_at[q] tiles (tile_end / tile_in: at fb.dc_at[q]); its front end forms
-// the stretches fb.fe0[q] .. , fb.fe_at[q + 1] - fb.fe_at[q] of them.  ck, z (ma.ck likewise): the slabs fb.ck_org / fb.z_org count from
+// mono input: the DC blocker and the front end over the windows.  Channel q's DC blocker resumes at fb.dc_from[q] (a multiple of 64,
+// from the state kept before it) with fb.dc_at[q + 1] - fb.dc_at[q] tiles (tile_end / tile_in: at fb.dc_at[q]) and keeps the states
+// of the complete blocks; its front end forms the stretches fb.fe0[q] .. (k_sync.hip: front_end_stretch() samples each, from position
+// 0), fb.fe_at[q + 1] - fb.fe_at[q] of them.  ck, z (ma.ck likewise): the slabs fb.ck_org / fb.z_org count from
+long front_end_stretch();
 void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
 void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z);
 

@@ -1,4 +1,4 @@
-"""Model of the live feed's trigger scan (modem_amd/csrc/api_feed.cpp): the tile model of stream_model.py run push by
+"""Model of the live feed's trigger scan (modem_amd/csrc/api_bank.cpp with one channel): the tile model of stream_model.py run push by
 push.  A push scans the tiles it has completed - tiles stay on absolute multiples of the tile length - from the carry the last push
 left (Schmitt state, running maximum since the last falling edge and its index; the edge count starts at 0 in every push), and
 leaves the carry for the next; end() scans the last partial tile."""

@@ -1,12 +1,15 @@
 """The live feed bank (ofdmrx_bank_*): many live channels pushed and decoded in one call.  The truth of every test is
-the single-channel entry on the same handle configuration - ofdmrx_decode_stream for 2-channel input, one ofdmrx_feed_* with the same
-push lengths for mono input - never another run of the bank."""
+never another run of the bank: ofdmrx_decode_stream on the same handle configuration for 2-channel input; for mono input the answers
+the single-window feed gave for the same push lengths, recorded from the last commit that had one (tests/golden/feed_mono_parent.json,
+feed_fixture.py).  ofdmrx_feed_* is a bank of one channel since, so the mono tests' comparison with it says that a channel among
+neighbours equals the channel alone."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import bank_inputs as B
+import feed_fixture as F
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -121,12 +124,15 @@ def test_mixed_modes_and_failures(rx):
         assert all(len(truth[c][1]) - 1 not in ri_[rc_ == c].tolist() for rc_, ri_ in calls[:-1])
 
 
-def _mono_compare(rx, chans, blocks, rate=8000, relation=True):
+def _mono_compare(rx, chans, blocks, fixture, rate=8000, relation=True):
     lens = [len(c) for c in chans]
     rounds = B.block_rounds(lens, blocks)
     per, calls, _ = B.run_bank(rx, chans, rounds)
     for c, ch in enumerate(chans):
-        want = B.run_feed(rx, ch, [r[c] for r in rounds])
+        pushes = [r[c] for r in rounds]
+        F.check(fixture % c, ch, pushes, per[c][:2])             # the recorded single-window feed, byte for byte
+        want = B.run_feed(rx, ch, pushes)                        # the channel alone (a bank of one)
+        F.check(fixture % c, ch, pushes, want)
         B.same(per[c][:2], want)
         assert per[c][2].tolist() == list(range(len(want[1])))
         if relation:                                             # the feed's documented relation to the one-call decode
@@ -145,7 +151,7 @@ def _mono_compare(rx, chans, blocks, rate=8000, relation=True):
 def test_mono(rx):
     real = B.mixed(1).reshape(-1)
     chans = [np.concatenate([np.zeros(lead, np.int16), real]) for lead in (0, 1, 4097)]
-    per = _mono_compare(rx, chans, [8000, 4095, 7937])
+    per = _mono_compare(rx, chans, [8000, 4095, 7937], "bank_mono_c%d")
     assert all(len(p[1]) >= 9 for p in per)
 
 
@@ -278,7 +284,7 @@ def test_rate_44k_mono():
         pcm = O.impair(O.encode_pcm(O.payload_for(61), channels=2, rate=44100), noise_db=-30, seed=2, frame=0, rate=44100)
         mono = np.ascontiguousarray(pcm[:, 0])
         chans = [mono, np.concatenate([np.zeros(4097, np.int16), mono])]
-        per = _mono_compare(r, chans, 44100, rate=44100)
+        per = _mono_compare(r, chans, 44100, "bank_44k_mono_c%d", rate=44100)
         assert all(len(p[1]) == 1 and (p[0][0] == O.payload_for(61)).all() for p in per)
     finally:
         r.close()
@@ -399,7 +405,11 @@ def test_lifecycle(rx, staggered_truth):
     assert L.ofdmrx_bank_begin(h, 2, 0, 2) == 0
     try:
         assert L.ofdmrx_bank_begin(h, 2, 0, 2) == E_ARG          # one bank per handle
-        assert L.ofdmrx_feed_begin(h, 0, 2) == E_ARG             # ... and no feed beside it
+        assert L.ofdmrx_feed_begin(h, 0, 2) == E_ARG             # ... and no feed beside it; the feed entries refuse the bank
+        fa = (M._ptr(out), M._ptr(res), C.byref(nrec), C.byref(nleft))
+        assert L.ofdmrx_feed_push(h, None, 0, 4, *fa) == E_ARG and L.ofdmrx_feed_end(h, 4, *fa) == E_ARG
+        assert L.ofdmrx_feed_lag(h) == E_ARG and L.ofdmrx_feed_resident_samples(h) == E_ARG
+        assert L.ofdmrx_bank_resident_samples(h, 0) == 0         # (still open)
         assert push(None, 4000, M._ptr(lens), None, 4, *a) == E_ARG
         assert push(M._ptr(buf), 4000, None, None, 4, *a) == E_ARG
         for k in range(4):                                       # any of the four arrays

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import feed_fixture as F
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -184,6 +185,7 @@ def test_mixed_mono(rx):
     pcm, _ = _mixed(1)
     out, res, npre = rx.decode_stream(pcm)
     fo, fr = _feed_cuts(rx, pcm, _blocks(len(pcm), 8000))
+    F.check("feed_mixed_mono", pcm, np.diff([0] + _blocks(len(pcm), 8000) + [len(pcm)]), (fo, fr))   # the recorded single-window feed
     assert len(fr) == npre == len(res)
     assert fo.tobytes() == out.tobytes()
     for name in ("status", "sc_start", "symbol_pos", "n_sync_rejects", "oper_mode", "call_sign", "best_lane"):
@@ -311,6 +313,7 @@ def test_rate_44k_mono():
         pcm = O.impair(O.encode_pcm(pay, channels=2, rate=44100), noise_db=-30, seed=2, frame=0, rate=44100)
         pcm = np.ascontiguousarray(pcm[:, :1])
         fo, fr = _feed_cuts(r, pcm, _blocks(len(pcm), 44100))
+        F.check("feed_44k_mono", pcm, np.diff([0] + _blocks(len(pcm), 44100) + [len(pcm)]), (fo, fr))
         assert _check_records(fo, fr, len(fr), pcm, rate=44100, payloads=pay.reshape(2, -1)) == 2
     finally:
         r.close()
@@ -344,6 +347,13 @@ def test_lifecycle(rx, three_truth):
     assert L.ofdmrx_feed_begin(h, 0, 2) == 0
     try:
         assert L.ofdmrx_feed_begin(h, 0, 2) == E_ARG             # one feed per handle
+        assert L.ofdmrx_bank_begin(h, 1, 0, 2) == E_ARG          # ... and no bank beside it; the bank entries refuse the feed
+        rc, ri, one_len = np.zeros(4, np.int32), np.zeros(4, np.int64), np.zeros(1, np.uintp)
+        ba = (M._ptr(out), M._ptr(res), M._ptr(rc), M._ptr(ri), C.byref(nrec), C.byref(nleft))
+        assert L.ofdmrx_bank_push(h, None, 0, M._ptr(one_len), None, 4, *ba) == E_ARG and L.ofdmrx_bank_end(h, 4, *ba) == E_ARG
+        assert L.ofdmrx_bank_resident_samples(h, 0) == E_ARG and L.ofdmrx_bank_preambles(h, 0) == E_ARG
+        assert L.ofdmrx_bank_last_stage_ops(h) == E_ARG
+        assert L.ofdmrx_feed_lag(h) == 0                         # (still open)
         assert L.ofdmrx_feed_push(h, None, 100, 4, *a) == E_ARG
         assert L.ofdmrx_feed_push(h, M._ptr(pcm), 100, 4, None, M._ptr(res), C.byref(nrec), C.byref(nleft)) == E_ARG
         assert L.ofdmrx_feed_push(h, M._ptr(pcm), 100, 4, M._ptr(out), None, C.byref(nrec), C.byref(nleft)) == E_ARG

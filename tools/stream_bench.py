@@ -9,7 +9,8 @@ copies of it with skip counts 0 .. n-1).  Every payload is checked.  Prints one 
 
 --feed BLOCK: instead, ONE such recording from host memory through the live feed (ofdmrx_feed_*) in pushes of BLOCK samples, beside the
 host-pointer one-call entry (ofdmrx_decode_stream) on the same samples: samples/s and records/s of both and their ratio.  Every push
-synchronises with the host, so the feed is the slower per sample; records and payloads are checked to be the same.
+synchronises with the host, so the feed is the slower per sample; records and payloads are checked to be the same.  feed_ms_per_push*
+is a whole run (begin to end) divided by its pushes, feed_push_call_ms_* the median time of one push call, both over the steps.
 
 --batched: instead, the --streams recordings (a) through a loop of ofdmrx_decode_stream_device, one call per recording, and (b) through
 ONE ofdmrx_decode_streams_device call, alternating step by step: records/s and samples/s of both with the median and the range over the
@@ -224,23 +225,30 @@ def feed_bench(a, rx, pcm, pay):
     def one_call():
         return rx.decode_stream(pcm, max_frames=K)[:2]
 
+    push_medians = []                                            # per run of the feed: the median time of one push call
+
     def fed():
-        got = []
+        got, t_push = [], []
         with rx.feed(2) as f:
             for p in range(0, n, B):
+                t0 = time.perf_counter()
                 got.append(f.push(pcm[p:p + B]))
+                t_push.append(time.perf_counter() - t0)
             got.append(f.end())
+        push_medians.append(float(np.median(t_push)))
         return np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got])
 
-    times = {}
+    times, per_step = {}, {}
     outs = {}
     for name, fn in (("one_call", one_call), ("feed", fed)):
         for _ in range(a.warmup):
             fn()
-        t0 = time.perf_counter()
+        per_step[name] = []
         for _ in range(a.steps):
+            t0 = time.perf_counter()
             outs[name] = fn()
-        times[name] = (time.perf_counter() - t0) / a.steps
+            per_step[name].append(time.perf_counter() - t0)
+        times[name] = float(np.mean(per_step[name]))
     same = outs["feed"][0].tobytes() == outs["one_call"][0].tobytes() and outs["feed"][1].tobytes() == outs["one_call"][1].tobytes()
     rec = {
         "metric": "live feed against the one-call host entry, mode-6 8 kHz 2-channel int16, AWGN %g dB" % a.noise_db,
@@ -248,6 +256,10 @@ def feed_bench(a, rx, pcm, pay):
         "one_call_ms": times["one_call"] * 1e3, "one_call_samples_per_s": n / times["one_call"], "one_call_records_per_s": K / times["one_call"],
         "feed_ms": times["feed"] * 1e3, "feed_samples_per_s": n / times["feed"], "feed_records_per_s": len(outs["feed"][1]) / times["feed"],
         "feed_vs_one_call": times["one_call"] / times["feed"], "feed_ms_per_push": times["feed"] * 1e3 / ((n + B - 1) // B),
+        "feed_ms_per_push_median": float(np.median(per_step["feed"])) * 1e3 / ((n + B - 1) // B),
+        "feed_ms_per_push_min": min(per_step["feed"]) * 1e3 / ((n + B - 1) // B), "feed_ms_per_push_max": max(per_step["feed"]) * 1e3 / ((n + B - 1) // B),
+        "feed_push_call_ms_median": float(np.median(push_medians[-a.steps:])) * 1e3, "feed_push_call_ms_min": min(push_medians[-a.steps:]) * 1e3,
+        "feed_push_call_ms_max": max(push_medians[-a.steps:]) * 1e3,
         "records": len(outs["feed"][1]), "payloads_ok": int((outs["feed"][0] == pay).all(axis=1).sum()), "same_bytes_as_one_call": bool(same),
     }
     line = json.dumps(rec)
@@ -335,7 +347,9 @@ def bank_bench(a, rx, pcm, pay):
     rec = {
         "metric": "live feed bank: N channels of one recording, mode-6 8 kHz 2-channel int16, AWGN %g dB, against N feeds and one decode_streams call" % a.noise_db,
         "channels": N, "block": B, "payloads_per_channel": K, "rounds": rounds, "steps": a.steps, "warmup": a.warmup, "records": n_rec,
-        "bank_ms_per_round_median": med(res["bank"][2]) * 1e3, "bank_wall_ms_median": bank_wall * 1e3, "bank_wall_ms_min": min(res["bank"][1]) * 1e3,
+        "bank_ms_per_round_median": med(res["bank"][2]) * 1e3, "bank_ms_per_round_min": min(res["bank"][2]) * 1e3,
+        "bank_ms_per_round_max": max(res["bank"][2]) * 1e3, "feeds_ms_per_round_min": min(res["feeds"][2]) * 1e3,
+        "feeds_ms_per_round_max": max(res["feeds"][2]) * 1e3, "bank_wall_ms_median": bank_wall * 1e3, "bank_wall_ms_min": min(res["bank"][1]) * 1e3,
         "bank_wall_ms_max": max(res["bank"][1]) * 1e3, "bank_records_per_s": n_rec / bank_wall,
         "feeds_channels": M, "feeds_ms_per_round_median": med(res["feeds"][2]) * 1e3, "feeds_wall_ms_median": feeds_wall * 1e3,
         "feeds_wall_ms_min": min(res["feeds"][1]) * 1e3, "feeds_wall_ms_max": max(res["feeds"][1]) * 1e3,
