@@ -53,8 +53,10 @@ extern "C" {
  *      ofdmrx_feed_end, ofdmrx_feed_lag, ofdmrx_feed_resident_samples; many recordings in one call - ofdmrx_decode_streams,
  *      ofdmrx_decode_streams_device, ofdmrx_debug_streams_edges; a bank of live channels - ofdmrx_bank_begin, ofdmrx_bank_push,
  *      ofdmrx_bank_end, ofdmrx_bank_resident_samples, ofdmrx_bank_preambles, ofdmrx_bank_last_stage_ops
- *   8: ofdmrx_debug_polar_modes, ofdmrx_debug_decode_cons_modes (the single-stage test entries for every mode of the mode table) */
-#define OFDMRX_ABI_MINOR 8
+ *   8: ofdmrx_debug_polar_modes, ofdmrx_debug_decode_cons_modes (the single-stage test entries for every mode of the mode table)
+ *   9: the three transmitter entries refuse a freq_off outside encode.cc:389's band with OFDMRX_E_ARG (they used to fold the
+ *      carriers round Nyquist) */
+#define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
 #define OFDMRX_CODE_LEN 65536         /* decode.cc:309  code_order 16 */
@@ -521,7 +523,11 @@ long ofdmrx_tx_frame_samples(int oper_mode);
  * bits = 8 (unsigned, offset 128) or 16.  ofdmrx_stream_samples: sample frames of one such stream.
  * _device: n_streams x count x 5380 payload bytes in, n_streams x samples x channels PCM out, DEVICE pointers;
  * asynchronous on the handle's stream like the decode entry (scratch is kept in the handle: no allocation per call).
- * ofdmrx_tx_encode_stream: the same for ONE stream with HOST pointers (what the `encode` CLI calls). */
+ * ofdmrx_tx_encode_stream: the same for ONE stream with HOST pointers (what the `encode` CLI calls).
+ * Arguments main() refuses are refused here with OFDMRX_E_ARG and nothing is written: a mode outside 6..13 (encode.cc:353), a call
+ * sign outside 0 < value < 129961739795077 (encode.cc:358), a freq_off that is no multiple of 50 (encode.cc:394) or, since 1.9, one
+ * that puts part of the band outside the spectrum (encode.cc:389, with band_width of encode.cc:363-387 and rate = the handle's):
+ * freq_off < band_width / 2 - rate / 2, freq_off > rate / 2 - band_width / 2, or with one channel freq_off < band_width / 2. */
 long ofdmrx_stream_samples(int sample_rate, int oper_mode, int count);
 /* call sign -> the base-37 integer of the header (encode.cc:320-335: ' ' = 0, digits 1..10, letters of either case
  * 11..36), -1 if the string holds any other character.  Valid call signs are 0 < value < 129961739795077

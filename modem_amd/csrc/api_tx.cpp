@@ -1,5 +1,6 @@
 // api_tx.cpp -- channel models (N3) and the device transmitter (N2) behind include/ofdmrx.h (encode.cc:205-291, 399-441).
 #include "api_internal.h"
+#include "tx_band.h"
 
 extern "C" int ofdmrx_util_awgn_tile(ofdmrx_handle *h, const int16_t *d_base, size_t n_base, int16_t *d_out, size_t n_out,
 	size_t spf, float noise_db, uint64_t seed, uint64_t first_frame)
@@ -63,16 +64,31 @@ extern "C" long ofdmrx_frame_samples(int sample_rate, int oper_mode) { return of
 
 extern "C" long ofdmrx_tx_frame_samples(int oper_mode) { return ofdmrx_frame_samples(8000, oper_mode); }
 
-extern "C" int ofdmrx_tx_encode_stream_device(ofdmrx_handle *h, const uint8_t *d_payload, size_t n_streams, int count,
-	int oper_mode, int freq_off, const char *call_sign, int channels, int bits, void *d_pcm)
+// what main() refuses (encode.cc:353, 358, 389, 394) and what no entry can work with, before anything touches the device
+static int tx_check_args(const ofdmrx_handle *h, int count, int oper_mode, int freq_off, const char *call_sign, int channels, int bits,
+	long long *cs_out)
 {
-	if (!h || !d_payload || !d_pcm || !n_streams || !call_sign || channels < 1 || channels > 2 || (bits != 8 && bits != 16))
+	if (!h || !call_sign || channels < 1 || channels > 2 || (bits != 8 && bits != 16))
 		return OFDMRX_E_ARG;
 	if (oper_mode < 6 || oper_mode > 13 || freq_off % 50 || count < 1 || count > 4096)   // encode.cc:353,394
 		return OFDMRX_E_ARG;
-	long long cs = callsign_value(call_sign);
-	if (cs <= 0 || cs >= 129961739795077LL)               // encode.cc:358
+	if (!tx_offset_in_band(h->rate, oper_mode, channels, freq_off))                        // encode.cc:389
 		return OFDMRX_E_ARG;
+	const long long cs = callsign_value(call_sign);
+	if (cs <= 0 || cs >= 129961739795077LL)                                                // encode.cc:358
+		return OFDMRX_E_ARG;
+	*cs_out = cs;
+	return 0;
+}
+
+extern "C" int ofdmrx_tx_encode_stream_device(ofdmrx_handle *h, const uint8_t *d_payload, size_t n_streams, int count,
+	int oper_mode, int freq_off, const char *call_sign, int channels, int bits, void *d_pcm)
+{
+	if (!d_payload || !d_pcm || !n_streams)
+		return OFDMRX_E_ARG;
+	long long cs = 0;
+	if (int r = tx_check_args(h, count, oper_mode, freq_off, call_sign, channels, bits, &cs))
+		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	struct { int oper_mode, offset, channels, nsym; unsigned long long md; long frame_samples; int count, bits, symbol_len; } tp;
 	ModeDesc md = mode_desc(oper_mode);
@@ -123,10 +139,13 @@ extern "C" int ofdmrx_tx_encode_device(ofdmrx_handle *h, const uint8_t *d_payloa
 extern "C" int ofdmrx_tx_encode_stream(ofdmrx_handle *h, const uint8_t *payload, int count, int oper_mode, int freq_off,
 	const char *call_sign, int channels, int bits, void *pcm)
 {
-	if (!h || !payload || !pcm || count < 1)
+	if (!payload || !pcm)
 		return OFDMRX_E_ARG;
+	long long cs = 0;
+	if (int r = tx_check_args(h, count, oper_mode, freq_off, call_sign, channels, bits, &cs))   // before any allocation or copy
+		return r;
 	const long spf = ofdmrx_stream_samples(h->rate, oper_mode, count);
-	if (spf < 0 || channels < 1 || channels > 2 || (bits != 8 && bits != 16))
+	if (spf < 0)
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	DevBuf dp, dx;

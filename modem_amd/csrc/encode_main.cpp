@@ -3,6 +3,7 @@
 // "-" = /dev/stdout | /dev/stdin handling, same exit codes; the WAV it writes is the reference's stream:
 // RATE samples of silence, pilot | per input file: Schmidl-Cox, meta data, pilot, payload rows | zero symbol, silence.
 #include "../../include/ofdmrx.h"
+#include "tx_band.h"
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -32,10 +33,7 @@ int main(int argc, char **argv)
 		std::fprintf(stderr, "Unsupported call sign.\n");
 		return 1;
 	}
-	static const int bw[14] = { 0, 0, 0, 0, 0, 0, 2700, 2500, 2500, 2250, 3200, 2400, 2400, 1600 };   // encode.cc:363-387
-	const int band_width = bw[oper_mode];
-	if ((output_chan == 1 && freq_off < band_width / 2) || freq_off < band_width / 2 - output_rate / 2 ||
-		freq_off > output_rate / 2 - band_width / 2) {
+	if (!tx_offset_in_band(output_rate, oper_mode, output_chan, freq_off)) {   // encode.cc:363-392
 		std::fprintf(stderr, "Unsupported frequency offset.\n");
 		return 1;
 	}

@@ -526,6 +526,12 @@ class Receiver:
                                                       channels, bits, _ptr(pcm)))
         return pcm
 
+    def tx_encode_streams(self, d_payload, n_streams, count, d_pcm, mode=6, freq_off=2000, call_sign="ANONYMOUS", channels=2, bits=16):
+        """device transmitter, streams of `count` payloads: n_streams x count x 5380 payload bytes -> n_streams x
+        ofdmrx_stream_samples(rate, mode, count) x channels samples of 8 (unsigned) or 16 bits (device pointers; asynchronous)"""
+        self._check(self._lib.ofdmrx_tx_encode_stream_device(self._h, d_payload, n_streams, count, mode, freq_off, call_sign.encode(),
+                                                             channels, bits, d_pcm))
+
     def tx_encode(self, d_payload, n, d_pcm, mode=6, freq_off=2000, call_sign="ANONYMOUS", channels=2):
         """device transmitter: n x 5380 payload bytes -> n x tx_frame_samples(mode) x channels int16 (device pointers)"""
         self._check(self._lib.ofdmrx_tx_encode_device(self._h, d_payload, n, mode, freq_off, call_sign.encode(), channels, d_pcm))

@@ -79,6 +79,20 @@ def test_argument_validation_without_device(lib):
     assert lib.ofdmrx_frame_samples(8000, 6) == 95200 and lib.ofdmrx_tx_frame_samples(6) == 95200
     assert lib.ofdmrx_frame_samples(48000, 6) == 571200 and lib.ofdmrx_frame_samples(44100, 13) == 1128078
     assert lib.ofdmrx_frame_samples(22050, 6) == -1 and lib.ofdmrx_frame_samples(8000, 5) == -1
+    # the three transmitter entries: no handle is an argument error before anything touches a device
+    assert lib.ofdmrx_tx_encode_stream_device(None, None, 1, 1, 6, 2000, b"A", 2, 16, None) == -1
+    assert lib.ofdmrx_tx_encode_stream(None, None, 1, 6, 2000, b"A", 2, 16, None) == -1
+    assert lib.ofdmrx_tx_encode_device(None, None, 1, 6, 2000, b"A", 2, None) == -1
+
+
+def test_minor_9_is_the_transmitters_offset_check(lib):
+    """revision 1.9 tightens a check (the band of encode.cc:389 in the transmitter entries): the header says so in the list of minors
+    and next to the entries; test_gpu_tx.py holds the refusals themselves on a device"""
+    text = open(os.path.join(ROOT, "include", "ofdmrx.h")).read()
+    assert lib.ofdmrx_abi_minor() == 9 and "#define OFDMRX_ABI_MINOR 9" in text
+    minors, rest = text.split("#define OFDMRX_ABI_MINOR")
+    assert "encode.cc:389" in minors.split(" *   9:")[1]
+    assert "encode.cc:389" in rest.split("long ofdmrx_stream_samples")[0].split("ofdmrx_tx_encode_stream:")[1]
 
 
 def test_product_does_not_reference_the_oracle():

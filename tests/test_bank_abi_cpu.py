@@ -23,7 +23,7 @@ def test_bank_symbols_exported(lib):
     for name in NAMES:
         assert name in M.EXPORTS
         getattr(lib, name)
-    assert lib.ofdmrx_abi_minor() == 8                           # additions within 1.7: detected by symbol
+    assert lib.ofdmrx_abi_minor() == 9                           # additions within 1.7: detected by symbol
     assert hasattr(M.Receiver, "bank") and hasattr(M, "Bank")
 
 

@@ -20,7 +20,7 @@ def test_stream_symbols_exported(lib):
     for name in ("ofdmrx_decode_stream", "ofdmrx_decode_stream_device", "ofdmrx_debug_stream_edges"):
         assert name in M.EXPORTS
         getattr(lib, name)
-    assert lib.ofdmrx_abi_minor() == 8
+    assert lib.ofdmrx_abi_minor() == 9
 
 
 @pytest.mark.parametrize("entry", ["ofdmrx_decode_stream", "ofdmrx_decode_stream_device"])
