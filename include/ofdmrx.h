@@ -246,7 +246,7 @@ int ofdmrx_debug_stream_edges(ofdmrx_handle *h, const float *timing, size_t n, s
  * The records of recording s are, byte for byte - payload and every byte of every ofdmrx_frame_result - what ofdmrx_decode_stream
  * returns for that recording alone, for 2-channel and for mono input, every format and rate, however the recordings are batched:
  * sc_start is an index into recording s, n_sync_rejects counts from its start, n_preambles[s] is its own count.  Mono input keeps
- * that because every recording runs the arithmetic of the one-call entry with its own tile count: the DC blocker's scan over tiles
+ * that because every recording runs with its own tile count (ofdmrx_decode_stream is this call with one recording): the DC blocker's scan over tiles
  * of 4096 samples composes per recording, in the order a call with that recording alone composes it, and the analytic signal is
  * formed in stretches on multiples of 7936 samples from that recording's position 0.
  * Packing: records in recording order, then preamble order; recording s contributes min(n_preambles[s], max_frames_per_stream)

@@ -503,7 +503,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 		const WindowBatch wb = window_batch(b, nullptr);
 		const RecordSources srcs{ b.seed_src.as<int>(), nullptr, 0, wb.org, wb.len };
 		const FrameBatch all{ wb.samples, 0, 0, wb.fmt, 2 };          // (mono input: the analytic signal, read as I/Q pairs)
-		r = r ? r : decode_records(h, all, b.seeds.as<SyncState>(), n, Outputs{ h->sx_pay.as<uint8_t>(), h->sx_res.as<Result>(), rows_user ? h->sx_esn0.as<float>() : nullptr }, &srcs);
+		r = r ? r : decode_records(h, all, b.seeds.as<SyncState>(), n, Outputs{ h->sx_pay.as<uint8_t>(), h->sx_res.as<Result>(), rows_user ? h->sx_esn0.as<float>() : nullptr }, srcs);
 		if (r)
 			return r;
 		std::vector<uint8_t> pay(n * PAYLOAD_BYTES);

@@ -217,14 +217,13 @@ struct ofdmrx_handle {
 	int lanes = 1;
 	size_t split_at = 0;      // frames of the last call that went through this handle's own pipeline (0: all of them)
 	hipEvent_t ev_lane_in = nullptr, ev_lane_done = nullptr;
-	// stream decode (api_stream.cpp): scratch kept between calls, grown on demand
+	// stream decode (api_streams.cpp; the live entries of api_bank.cpp share the output staging): scratch kept between calls, grown on demand
 	DevBuf sx_in, sx_z, sx_ck, sx_dc_end, sx_dc_in, sx_fn, sx_carry, sx_edges, sx_counts, sx_rec, sx_pay, sx_res, sx_esn0, sx_timing;
-	long sx_edge_cap = 0;     // edges the edge buffer holds
-	// many recordings in one call (api_streams.cpp): the per-recording lengths and tile places, the packed order, the record -> recording map
+	// ... the per-recording lengths and tile places, the packed order, the record -> recording map
 	DevBuf sxs_len, sxs_tile0, sxs_given0, sxs_first, sxs_rec_src;
 	std::vector<int> sxs_len_h;           // (host copies the uploads read: they live as long as the handle)
 	std::vector<long long> sxs_tile0_h, sxs_given0_h, sxs_counts_h;
-	long sxs_edge_cap = 0;    // every recording's share of the edge buffer
+	long sxs_edge_cap = 0;    // every recording's share of the edge buffer (one recording: all of it)
 	struct ofdmrx_bank *bank = nullptr;   // the open bank of live channels or - a bank of one - the open feed (api_bank.cpp): one per handle
 	bool busy_live() const { return bank != nullptr; }   // a handle with an open feed or bank decodes nothing else
 };
@@ -257,12 +256,13 @@ inline void begin_call(ofdmrx_handle *h)
 	h->split_at = 0;
 }
 int finish_call(ofdmrx_handle *h, int r);                                                   // api_pipeline.cpp: a call ends: r, or the sticky event error
-// the chunk pipeline for n records of a stream decode: every frame is the whole stream fb (stride 0), record k starts from
-// d_records[k] (header, demod, ...); device or pinned host outputs like ofdmrx_decode_batch_device; keeps the call's events so far
-// srcs (nullable): the records of several recordings in one chunk plan - record k reads recording src_of[k], src_len[..] sample
-// frames at fb.samples + src_of[k] * stride_bytes (device arrays; fb has stride 0, fb.samples_per_frame the longest recording)
+// the chunk pipeline for n records of a stream decode: record k starts from d_records[k] (header, demod, ...); device or pinned
+// host outputs like ofdmrx_decode_batch_device; keeps the call's events so far.  fb has stride 0 and, as samples_per_frame, the
+// longest source; what record k reads is srcs:
+// the records of one or several recordings in one chunk plan - record k reads recording src_of[k], src_len[..] sample frames at
+// fb.samples + src_of[k] * stride_bytes (device arrays)
 // org (nullable; then src_len and stride_bytes are unused): the sources are live channels read through their windows - position 0 of
 // channel q would lie at fb.samples + org[q] bytes and the channel has len[q] sample frames so far (kernels.h: WindowBatch)
 struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; const long long *org = nullptr; const long long *len = nullptr; };
-int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources *srcs = nullptr);
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources &srcs);
 void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank (or feed) and its windows go

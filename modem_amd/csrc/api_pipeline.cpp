@@ -95,29 +95,24 @@ static int run_front1_rounds(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 	return front1_done(h, fb, n);
 }
 
-// front1 for a chunk of records of a stream decode (api_stream.cpp): the chunk's frames start from the SyncStates `seed` -
-// preambles already found and accepted, as a round with skip_left = 0 leaves them - instead of the sync rounds: header + OSD
-// once, then demod.  The header launch stands where the first sync launch would (wait_before_sync, *ev_after_sync as above).
-// srcs (nullable; its src_of already at this chunk's first record): the records read several recordings (ofdmrx_decode_streams)
+// front1 for a chunk of records of a stream decode (api_streams.cpp, api_bank.cpp): the chunk's frames start from the SyncStates
+// `seed` - preambles already found and accepted, as a round with skip_left = 0 leaves them - instead of the sync rounds: header +
+// OSD once, then demod.  The header launch stands where the first sync launch would (wait_before_sync, *ev_after_sync as above).
+// srcs (its src_of already at this chunk's first record): the recordings or live channels the records read
 static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int n, const SyncState *seed, size_t *t_begin,
-	size_t wait_before_sync, size_t *ev_after_sync, const RecordSources *srcs)
+	size_t wait_before_sync, size_t *ev_after_sync, const RecordSources &srcs)
 {
-	SourceBatch sb{ fb, nullptr, nullptr, nullptr, nullptr };
-	if (srcs) {
-		sb.frame_stride_bytes = srcs->stride_bytes;
-		sb.src_of = srcs->src_of;
-		sb.src_len = srcs->src_len;
-	}
+	SourceBatch sb{ fb, srcs.src_of, srcs.src_len, nullptr, nullptr };
+	sb.frame_stride_bytes = srcs.stride_bytes;
 	WindowBatch wb{};
-	const bool windows = srcs && srcs->org;
+	const bool windows = srcs.org != nullptr;
 	if (windows) {
 		static_cast<FrameBatch &>(wb) = fb;
-		wb.src_of = srcs->src_of;
-		wb.org = srcs->org;
-		wb.len = srcs->len;
+		wb.src_of = srcs.src_of;
+		wb.org = srcs.org;
+		wb.len = srcs.len;
 	}
 	SyncState *st = h->st.as<SyncState>();
-	const MonoArgs ma = mono_args(h->host.front, nullptr, 0);
 	size_t e0 = mark(h, s);
 	launch_init_sync(s, n, st, nullptr, h->chunk_flags.as<int>(), nullptr);
 	HIP_OK(hipMemcpyAsync(st, seed, (size_t)n * sizeof(SyncState), hipMemcpyDeviceToDevice, s));
@@ -129,10 +124,8 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 		Range r("ofdmrx:header_osd");
 		if (windows)
 			launch_header_bank(s, h->rate, n, wb, h->dev, st, h->hdr_soft.as<int8_t>());
-		else if (srcs)
-			launch_header_sources(s, h->rate, n, sb, h->dev, st, h->hdr_soft.as<int8_t>());
 		else
-			launch_header(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->hdr_soft.as<int8_t>(), nullptr, nullptr);
+			launch_header_sources(s, h->rate, n, sb, h->dev, st, h->hdr_soft.as<int8_t>());
 	}
 	size_t c = mark(h, s);
 	h->spans.push_back({ OFDMRX_T_HEADER, b, c });
@@ -140,10 +133,8 @@ static int run_front1_seeded(ofdmrx_handle *h, hipStream_t s, FrameBatch fb, int
 		Range r("ofdmrx:demod");
 		if (windows)
 			launch_demod_bank(s, h->rate, n, wb, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
-		else if (srcs)
-			launch_demod_sources(s, h->rate, n, sb, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
 		else
-			launch_demod(s, h->rate, n, fb, nullptr, ma, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
+			launch_demod_sources(s, h->rate, n, sb, h->dev, st, h->cons.as<cf>(), h->carr.as<cf>());
 	}
 	size_t d = mark(h, s);
 	h->spans.push_back({ OFDMRX_T_DEMOD, c, d });
@@ -321,8 +312,9 @@ struct PipeHooks {
 //   entry's output staging of that parity.
 // A call of one chunk (and OFDMRX_NO_OVERLAP=1, the profiler's setting: every kernel alone on the machine) runs all of it on A.
 // batch: the call's frames but for where chunk c's are (before_front1).  seed (nullable, stream decode): the frames are records
-// that start from these SyncStates instead of the sync rounds (run_front1_seeded); srcs (nullable, with seed): record k reads the
-// recording srcs->src_of[k] - batch then has stride 0 and a chunk takes whichever recordings its records belong to.
+// that start from these SyncStates instead of the sync rounds (run_front1_seeded), and srcs (null exactly when seed is) says what
+// they read: record k the recording or live channel srcs->src_of[k] - batch then has stride 0 and a chunk takes whichever sources
+// its records belong to.
 static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &plan, FrameBatch batch, const int32_t *d_skip, int max_skip,
 	const SyncState *seed, const RecordSources *srcs = nullptr)
 {
@@ -376,12 +368,12 @@ static int run_pipeline(ofdmrx_handle *h, PipeHooks &hooks, const ChunkPlan &pla
 		if (att && overlap && c >= 2)                             // (host entry: the log's staging of this parity has left with chunk c - 2)
 			HIP_OK(hipStreamWaitEvent(sa, h->ev_pool[ev_fin[c - 2]], 0));
 		const size_t slot_free = (scan_slot && c >= 2) ? ev_polar[c - 2] : NONE;
-		RecordSources chunk_srcs;
-		if (srcs) {
+		RecordSources chunk_srcs{};
+		if (seed) {
 			chunk_srcs = *srcs;
 			chunk_srcs.src_of += plan.first(c);
 		}
-		r = seed ? run_front1_seeded(h, sa, fb, n, seed + plan.first(c), &t0s[c], slot_free, &ev_sync, srcs ? &chunk_srcs : nullptr)
+		r = seed ? run_front1_seeded(h, sa, fb, n, seed + plan.first(c), &t0s[c], slot_free, &ev_sync, chunk_srcs)
 			: run_front1_rounds(h, sa, fb, n, d_skip ? d_skip + plan.first(c) : nullptr, max_skip, &t0s[c], att, att_counts, slot_free, &ev_sync);
 		h->last_first = plan.first(c);
 		if (!r && overlap && c >= 1)                              // flush(c - 1): its LLRs are in the queue, sync(c) is on its way
@@ -490,8 +482,8 @@ struct PinnedOutHooks : DeviceHooks {
 	}
 };
 
-// n_frames frames through one handle's pipeline, samples in HBM.  seed (nullable): the frames are records of a stream decode that
-// start from these SyncStates (run_front1_seeded)
+// n_frames frames through one handle's pipeline, samples in HBM.  seed, srcs (both null, or neither): the frames are records of a
+// stream decode that start from these SyncStates and read these sources (run_front1_seeded)
 static int decode_device_lane(ofdmrx_handle *h, FrameBatch fb, size_t n_frames, const int32_t *d_skip, Outputs out, const SyncState *seed,
 	const RecordSources *srcs = nullptr)
 {
@@ -522,9 +514,9 @@ static int decode_device_lane(ofdmrx_handle *h, FrameBatch fb, size_t n_frames, 
 	return finish_call(h, run_pipeline(h, hooks, plan, fb, d_skip, max_skip, seed, srcs));
 }
 
-int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources *srcs)
+int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources &srcs)
 {
-	return decode_device_lane(h, fb, n, nullptr, out, d_records, srcs);
+	return decode_device_lane(h, fb, n, nullptr, out, d_records, &srcs);
 }
 
 // what the setters left in the handle, beside the call's own two arrays

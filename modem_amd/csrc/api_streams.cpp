@@ -1,10 +1,14 @@
-// api_streams.cpp -- ofdmrx_decode_streams*: many recordings in one call (added within revision 1.7).
-//   the stream scan of api_stream.cpp with the recording as a second grid dimension (k_stream.hip, the SourceBatch forms): every
-//   recording from its own position 0, with its own tile count, nothing carried from one into the next
-//   | records: every recording's accepted preambles at their place in the packed order, with the recording each one reads
+// api_streams.cpp -- the stream entries: ofdmrx_decode_streams*, many recordings in one call, and
+// ofdmrx_decode_stream*, every preamble of one recording in one call: a batch of one recording, at the end of this file.
+//   the stream scan (k_stream.hip, the SourceBatch forms) with the recording as a second grid dimension: [mono: the DC blocker's kept
+//   states by a scan over tiles, the analytic signal of every recording] | the timing metric and the trigger as a scan over tiles |
+//   decode.cc:110-151 for every falling edge - every recording from its own position 0, with its own tile count, nothing carried
+//   from one into the next
+//   | records: the SyncState of every accepted preamble, as a SKIP round with skip_left = 0 leaves it, at its place in the packed
+//   order, with the recording it reads
 //   one read-back of all recordings' edge / preamble counts (the call's host synchronisation)
-//   the packed records through the chunk pipeline (decode_records with RecordSources): a chunk takes whichever recordings its
-//   records belong to
+//   the packed records through the chunk pipeline of the batch entries (api_pipeline.cpp: decode_records): a chunk takes whichever
+//   recordings its records belong to
 #include "api_internal.h"
 
 namespace {
@@ -97,9 +101,9 @@ int decode_streams_dev(ofdmrx_handle *h, FrameBatch fb, const StreamsCall &call,
 	int r = ensure_events(h, 16);
 	if (r)
 		return r;
-	// Every recording's share of the edge buffer: what the one-call entry starts with, max(4096, n / 2048), while all shares together
-	// stay within 64 MiB (S <= 512), then less, down to 256 edges (S = 65535: 0.5 GiB).  A share that proved too small has been grown
-	// (below) and stays grown for the handle's later calls, like the one-call entry's buffer.
+	// Every recording's share of the edge buffer: a preamble every frame and a few noise triggers fit in max(4096, n / 2048), while all
+	// shares together stay within 64 MiB (S <= 512), then less, down to 256 edges (S = 65535: 0.5 GiB).  A share that proved too small
+	// has been grown (below) and stays grown for the handle's later calls.
 	const long share0 = std::max(256L, std::min(4096L, (long)((64u << 20) / sizeof(StreamEdge) / S)));
 	h->sxs_edge_cap = std::max(h->sxs_edge_cap, std::max(share0, max_len / 2048));
 	const size_t e0 = mark(h, s);
@@ -172,40 +176,34 @@ int decode_streams_dev(ofdmrx_handle *h, FrameBatch fb, const StreamsCall &call,
 	}
 	const RecordSources srcs{ h->sxs_rec_src.as<int>(), h->sxs_len.as<int>(), fb2.frame_stride_bytes };
 	const FrameBatch all{ fb2.samples, 0, max_len, fb2.fmt, fb2.channels };
-	return decode_records(h, all, h->sx_rec.as<SyncState>(), n_rec, out, &srcs);
+	return decode_records(h, all, h->sx_rec.as<SyncState>(), n_rec, out, srcs);
 }
 
-}  // namespace
-
-extern "C" int ofdmrx_decode_streams_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels, size_t n_streams,
-	size_t stride, const size_t *n_samples, size_t max_per_stream, size_t max_records, uint8_t *d_payload_out,
-	ofdmrx_frame_result *d_results, size_t *n_preambles, size_t *first_record)
+// a call that has passed its checks begins: its device, its events and spans, the lengths on the device
+int begin_streams(ofdmrx_handle *h, const size_t *n_samples, StreamsCall *call)
 {
-	StreamsCall call;
-	int r = streams_args(h, d_samples, fmt, channels, n_streams, stride, n_samples, max_records, d_payload_out, d_results, n_preambles, first_record, &call);
-	if (r || h->busy_live())                                      // (a handle with an open feed or bank decodes nothing else)
-		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	begin_call(h);
-	r = upload_lengths(h, n_samples, nullptr, &call);
-	if (r)
+	return upload_lengths(h, n_samples, nullptr, call);
+}
+
+// the device entries behind their checks: the scan and the records
+int streams_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels, size_t stride, const size_t *n_samples, StreamsCall call,
+	size_t max_per_stream, size_t max_records, uint8_t *d_payload_out, ofdmrx_frame_result *d_results, size_t *n_preambles, size_t *first_record)
+{
+	if (int r = begin_streams(h, n_samples, &call))
 		return r;
 	size_t n_written = 0;
 	return decode_streams_dev(h, FrameBatch{ d_samples, stride, call.max_len, fmt, channels }, call, max_per_stream, max_records,
 		Outputs{ d_payload_out, (Result *)d_results, h->esn0_user }, n_preambles, first_record, &n_written);
 }
 
-extern "C" int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t n_streams,
-	size_t stride, const size_t *n_samples, size_t max_per_stream, size_t max_records, uint8_t *payload_out,
-	ofdmrx_frame_result *results, size_t *n_preambles, size_t *first_record)
+// the host entries behind their checks: the recordings go up, the outputs come back from device staging
+int streams_host(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t stride, const size_t *n_samples, StreamsCall call,
+	size_t max_per_stream, size_t max_records, uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_preambles, size_t *first_record)
 {
-	StreamsCall call;
-	int r = streams_args(h, samples, fmt, channels, n_streams, stride, n_samples, max_records, payload_out, results, n_preambles, first_record, &call);
-	if (r || h->busy_live())
-		return OFDMRX_E_ARG;
-	HIP_OK(hipSetDevice(h->cfg.device));
-	begin_call(h);
-	r = upload_lengths(h, n_samples, nullptr, &call);
+	const size_t n_streams = call.n_streams;
+	int r = begin_streams(h, n_samples, &call);
 	if (r)
 		return r;
 	hipStream_t s = h->stream;
@@ -218,7 +216,8 @@ extern "C" int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int 
 		if (n_samples[q])
 			HIP_OK(hipMemcpyAsync((char *)h->sx_in.p + q * stride, (const char *)samples + q * stride, n_samples[q] * frame_bytes, hipMemcpyHostToDevice, s));
 	const FrameBatch fb{ h->sx_in.p, stride, call.max_len, fmt, channels };
-	// outputs: device staging for as many records as the recordings are likely to hold, copied out behind the call; the Es/N0 rows likewise
+	// outputs: device staging for as many records as the recordings are likely to hold, copied out behind the call; the Es/N0 rows
+	// likewise, in place of the caller's host array
 	float *const rows_user = h->esn0_user;
 	auto stage = [&](size_t frames) -> int {
 		int rr = h->sx_pay.ensure(std::max<size_t>(1, frames) * PAYLOAD_BYTES);
@@ -227,6 +226,8 @@ extern "C" int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int 
 		return (rr || !rows_user) ? rr : h->sx_esn0.ensure(std::max<size_t>(1, cap) * ROWS_MAX * sizeof(float));
 	};
 	auto staged = [&] { return Outputs{ h->sx_pay.as<uint8_t>(), h->sx_res.as<Result>(), rows_user ? h->sx_esn0.as<float>() : nullptr }; };
+	// the first guess: 4 records and one per 16384 samples of every recording - more than three for every frame the recording can
+	// hold (the shortest frame of the mode table is 64800 samples at 8 kHz)
 	size_t guess = 0;
 	for (size_t q = 0; q < n_streams; ++q)
 		guess += std::min<size_t>(max_per_stream, 4 + n_samples[q] / 16384);
@@ -254,6 +255,30 @@ extern "C" int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int 
 	}
 	HIP_OK(hipStreamSynchronize(s));
 	return 0;
+}
+
+}  // namespace
+
+extern "C" int ofdmrx_decode_streams_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels, size_t n_streams,
+	size_t stride, const size_t *n_samples, size_t max_per_stream, size_t max_records, uint8_t *d_payload_out,
+	ofdmrx_frame_result *d_results, size_t *n_preambles, size_t *first_record)
+{
+	StreamsCall call;
+	int r = streams_args(h, d_samples, fmt, channels, n_streams, stride, n_samples, max_records, d_payload_out, d_results, n_preambles, first_record, &call);
+	if (r || h->busy_live())                                      // (a handle with an open feed or bank decodes nothing else)
+		return OFDMRX_E_ARG;
+	return streams_device(h, d_samples, fmt, channels, stride, n_samples, call, max_per_stream, max_records, d_payload_out, d_results, n_preambles, first_record);
+}
+
+extern "C" int ofdmrx_decode_streams(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t n_streams,
+	size_t stride, const size_t *n_samples, size_t max_per_stream, size_t max_records, uint8_t *payload_out,
+	ofdmrx_frame_result *results, size_t *n_preambles, size_t *first_record)
+{
+	StreamsCall call;
+	int r = streams_args(h, samples, fmt, channels, n_streams, stride, n_samples, max_records, payload_out, results, n_preambles, first_record, &call);
+	if (r || h->busy_live())
+		return OFDMRX_E_ARG;
+	return streams_host(h, samples, fmt, channels, stride, n_samples, call, max_per_stream, max_records, payload_out, results, n_preambles, first_record);
 }
 
 extern "C" int ofdmrx_debug_streams_edges(ofdmrx_handle *h, const float *timing, size_t n_streams, const size_t *n, size_t max_edges,
@@ -308,4 +333,52 @@ extern "C" int ofdmrx_debug_streams_edges(ofdmrx_handle *h, const float *timing,
 		}
 	}
 	return 0;
+}
+
+// ---- one recording: a batch of one.  The recording is the batch's only one, a whole number of sample frames apart from a next
+// that does not exist; every record may be its own (max_per_stream = max_records = max_frames).  What these entries refuse and the
+// batched ones take - an empty recording, an empty sequence - is refused here, before the handle is looked at.
+namespace {
+
+int one_stream_args(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t n_samples, size_t max_frames, const void *payload,
+	const void *results, size_t *n_preambles, size_t *first, size_t *stride, StreamsCall *call)
+{
+	if (n_samples == 0 || n_samples > (size_t)0x7fffffff / 2)
+		return OFDMRX_E_ARG;
+	*stride = n_samples * sample_bytes(fmt) * (size_t)channels;
+	int r = streams_args(h, samples, fmt, channels, 1, *stride, &n_samples, max_frames, payload, results, n_preambles, first, call);
+	return (r || h->busy_live()) ? OFDMRX_E_ARG : 0;
+}
+
+}  // namespace
+
+extern "C" int ofdmrx_decode_stream_device(ofdmrx_handle *h, const void *d_samples, int fmt, int channels, size_t n_samples,
+	size_t max_frames, uint8_t *d_payload_out, ofdmrx_frame_result *d_results, size_t *n_preambles)
+{
+	StreamsCall call;
+	size_t stride = 0, first[2];
+	if (int r = one_stream_args(h, d_samples, fmt, channels, n_samples, max_frames, d_payload_out, d_results, n_preambles, first, &stride, &call))
+		return r;
+	return streams_device(h, d_samples, fmt, channels, stride, &n_samples, call, max_frames, max_frames, d_payload_out, d_results, n_preambles, first);
+}
+
+extern "C" int ofdmrx_decode_stream(ofdmrx_handle *h, const void *samples, int fmt, int channels, size_t n_samples,
+	size_t max_frames, uint8_t *payload_out, ofdmrx_frame_result *results, size_t *n_preambles)
+{
+	StreamsCall call;
+	size_t stride = 0, first[2], n_pre = 0;
+	if (int r = one_stream_args(h, samples, fmt, channels, n_samples, max_frames, payload_out, results, n_preambles, first, &stride, &call))
+		return r;
+	if (int r = streams_host(h, samples, fmt, channels, stride, &n_samples, call, max_frames, max_frames, payload_out, results, &n_pre, first))
+		return r;
+	*n_preambles = n_pre;                                         // (written when the call has succeeded, outputs copied)
+	return 0;
+}
+
+extern "C" int ofdmrx_debug_stream_edges(ofdmrx_handle *h, const float *timing, size_t n, size_t max_edges,
+	int64_t *t_edge, int64_t *t_max, int32_t *index_max, size_t *n_edges)
+{
+	if (n == 0)
+		return OFDMRX_E_ARG;
+	return ofdmrx_debug_streams_edges(h, timing, 1, &n, max_edges, t_edge, t_max, index_max, n_edges);
 }

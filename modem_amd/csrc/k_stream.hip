@@ -1,19 +1,20 @@
-// k_stream.hip -- the stream scan: every Schmidl-Cox preamble of one long recording (decode.cc:84-151 over the whole stream), with
+// k_stream.hip -- the stream scan: every Schmidl-Cox preamble of a long recording (decode.cc:84-151 over the whole stream), with
 // all CUs on it.  No stage walks the stream in one wave or one workgroup:
-//   k_sdc_tile / k_sdc_scan   mono input: the DC blocker's kept states (k_mono_carries' layout) by tiles from a zero state, a scan of
+//   k_sdc_tile / k_sdcs_scan  mono input: the DC blocker's kept states (k_mono_carries' layout) by tiles from a zero state, a scan of
 //                             the tile carries with the a^4096 weights, and a fix-up
 //   k_stream_tile<.., false>  per tile of STREAM_TILE sample times: the timing metric (decode.cc:86-90) from window sums the tile
 //                             forms itself in double, then what the tile does to the trigger state for either incoming Schmitt state
-//   k_stream_fn_scan          one workgroup scans those per-tile functions (a tile is 4096 samples: 1/4096 of the stream)
+//   k_streams_fn_scan         one workgroup per recording scans those per-tile functions (a tile is 4096 samples: 1/4096 of the stream)
 //   k_stream_tile<.., true>   the tiles again, now with their incoming state: falling edges, t_max, index_max, in stream order
 //   k_stream_accept           decode.cc:110-151 for every edge (sc_accept_wg, shared with k_sync_accept)
-//   k_stream_records          a scan over accept / reject: record indices, cumulative rejects, the SyncState of every record
+//   k_streams_count / _first / _records   a scan over accept / reject: record indices, cumulative rejects, the SyncState of every
+//                             record, at its place in the packed order of the call's recordings
+// Recordings (api_streams.cpp; one recording is a batch of one): the FB = SourceBatch forms take the recording
+// from blockIdx.y - its own base, length and places in the per-tile and edge arrays; the scans over tiles are one workgroup per
+// recording, so nothing is carried from one recording into the next.
 // Live channels (api_bank.cpp; a feed is a bank of one channel) run the same kernels push by push over a
 // window of every channel's stream: the FB = WindowBatch forms take the channel from blockIdx.y - where the push's first tile / block
-// lies in its stream and the state its last push left - and compute from the same absolute positions as the one-call forms.
-// Many recordings in one call (api_streams.cpp): the FB = SourceBatch forms take the recording from blockIdx.y - its
-// own base, length and places in the per-tile and edge arrays - and run what the one-call forms run on it; the scans over tiles
-// are one workgroup per recording, so nothing is carried from one recording into the next.
+// lies in its stream and the state its last push left - and compute from the same absolute positions as a recording's scan.
 #include <type_traits>
 #include "dev_common.h"
 #include "kernels.h"
@@ -53,10 +54,11 @@ __device__ __forceinline__ Affine aff_then(Affine l, Affine r) { return Affine{ 
 // FB = WindowBatch (live channels): tile 0 of channel blockIdx.y starts at the absolute position fb.dc_from[q] (a
 // multiple of MONO_CK), the channel's samples and states are addressed from where position 0 / state 0 would lie, fb.len[q] is the
 // samples fed so far; only the states of complete blocks of MONO_CK samples are kept (ck_n is unused)
-template <int PASS, class FB = FrameBatch>
+template <int PASS, class FB>
 __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *__restrict__ tile_end, const double *__restrict__ tile_in,
 	double *__restrict__ ck, int ck_n)
 {
+	static_assert(many_v<FB> || bank_v<FB>, "recordings or live channels");
 	long origin = 0;
 	const int tid = threadIdx.x;
 	const long t = blockIdx.x;
@@ -106,27 +108,10 @@ __global__ __launch_bounds__(256) void k_sdc_tile(FB fb, FrontCoef co, double *_
 	}
 }
 
-// the tiles' entry states C_0 = 0, C_{t+1} = tile_end[t] + a^4096 C_t: one workgroup, a range of tiles per thread composed as an
-// affine map, an exclusive scan of the maps, then each range in turn
-__global__ __launch_bounds__(1024) void k_sdc_scan(FrontCoef co, const double *__restrict__ tile_end, double *__restrict__ tile_in, long ntiles)
-{
-	const int tid = threadIdx.x;
-	__shared__ Affine sh[1024];
-	const double A = mono_pow((double)co.dc_a, 4096);
-	const long per = (ntiles + 1023) / 1024, k0 = (long)tid * per, k1 = k0 + per < ntiles ? k0 + per : ntiles;
-	Affine f{ 0.0, 1.0 };
-	for (long k = k0; k < k1; ++k)
-		f = aff_then(f, Affine{ tile_end[k], A });
-	block_scan_incl<1024>(f, sh, tid, aff_then);
-	double c = tid ? sh[tid - 1].v : 0.0;                     // the maps applied to C_0 = 0
-	for (long k = k0; k < k1; ++k) {
-		tile_in[k] = c;
-		c = tile_end[k] + A * c;
-	}
-}
-// Many recordings: one workgroup per recording runs k_sdc_scan on that recording's tiles - the same ranges per thread, the
-// same order of composition as a call with that recording alone, so the same doubles.  (A kernel of its own rather than a shared
-// body: k_sdc_scan's code stays what it was.)
+// the tiles' entry states C_0 = 0, C_{t+1} = tile_end[t] + a^4096 C_t: one workgroup per recording, on that recording's tiles -
+// a range of tiles per thread composed as an affine map, an exclusive scan of the maps, then each range in turn.  The ranges per
+// thread and the order of composition depend on the recording's own tile count alone, so a recording's doubles are the same
+// whatever else the call holds.
 __global__ __launch_bounds__(1024) void k_sdcs_scan(FrontCoef co, const double *__restrict__ tile_end_all, double *__restrict__ tile_in_all,
 	const long long *__restrict__ tile0)
 {
@@ -141,17 +126,16 @@ __global__ __launch_bounds__(1024) void k_sdcs_scan(FrontCoef co, const double *
 	for (long k = k0; k < k1; ++k)
 		f = aff_then(f, Affine{ tile_end[k], A });
 	block_scan_incl<1024>(f, sh, tid, aff_then);
-	double c = tid ? sh[tid - 1].v : 0.0;
+	double c = tid ? sh[tid - 1].v : 0.0;                     // the maps applied to C_0 = 0
 	for (long k = k0; k < k1; ++k) {
 		tile_in[k] = c;
 		c = tile_end[k] + A * c;
 	}
 }
 
-// Many live channels: one workgroup per channel runs k_sdc_scan's scan on the tiles that channel brings in this push - the same
+// Many live channels: one workgroup per channel runs k_sdcs_scan's scan on the tiles that channel brings in this push - the same
 // ranges per thread, the same order of composition whatever the other channels bring, so the same doubles - with the maps applied
-// to the state kept before the channel's first tile (left by its earlier pushes) instead of 0.  (A kernel of its own, as
-// k_sdcs_scan is.)
+// to the state kept before the channel's first tile (left by its earlier pushes) instead of 0.
 __global__ __launch_bounds__(1024) void k_bank_sdc_scan(WindowBatch fb, FrontCoef co, const double *__restrict__ tile_end_all, double *__restrict__ tile_in_all,
 	const double *__restrict__ ck_all)
 {
@@ -178,14 +162,6 @@ __global__ __launch_bounds__(1024) void k_bank_sdc_scan(WindowBatch fb, FrontCoe
 	}
 }
 
-void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck)
-{
-	const long ntiles = (fb.samples_per_frame + 4095) / 4096;
-	const int ck_n = mono_ck_per_frame(fb.samples_per_frame);
-	hipLaunchKernelGGL(k_sdc_tile<0>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
-	hipLaunchKernelGGL(k_sdc_scan, dim3(1), dim3(1024), 0, s, co, tile_end, tile_in, ntiles);
-	hipLaunchKernelGGL(k_sdc_tile<1>, dim3((unsigned)ntiles), dim3(256), 0, s, fb, co, tile_end, tile_in, ck, ck_n);
-}
 void launch_streams_dc(hipStream_t s, int n_src, long max_len, SourceBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, int ck_per_src)
 {
 	const dim3 grid((unsigned)((max_len + 4095) / 4096), (unsigned)n_src);
@@ -271,17 +247,18 @@ __device__ __forceinline__ void tile_trigger(TrigShared &sh, const int (&cls)[SP
 }
 
 // EMIT = false: the timing metric of the tile and its function (StreamFn) for both incoming states; EMIT = true: the same metric and
-// the tile's falling edges from its incoming StreamCarry.  GIVEN: the metric is a caller's sequence (ofdmrx_debug_stream_edges).
+// the tile's falling edges from its incoming StreamCarry.  GIVEN: the metric is a caller's sequence (ofdmrx_debug_streams_edges).
 // FB = SourceBatch: tile blockIdx.x of recording blockIdx.y, read from that recording's base with its length (n is unused): a position
-// below 0 or at or past the length reads as zero, exactly as in a call with that recording alone; edges is [recordings][cap]
+// below 0 or at or past the length reads as zero, whatever lies behind the recording; edges is [recordings][cap]
 // FB = WindowBatch: block b of the live channel q = blockIdx.y is tile fb.tile0[q] + b of its stream - the same absolute sample
-// positions as in a one-call scan, so the same metric values - read from where the channel's position 0 would lie, with the samples
+// positions as in a recording's scan, so the same metric values - read from where the channel's position 0 would lie, with the samples
 // fed so far as its length (n is unused); fn / carry are indexed from fb.tile_at[q], edges is [channels][cap], and the edge positions
 // count from the push's first edge (the carry that enters a push has count 0)
-template <int RATE, bool GIVEN, bool EMIT, class FB = FrameBatch>
+template <int RATE, bool GIVEN, bool EMIT, class FB>
 __global__ __launch_bounds__(256) void k_stream_tile(FB fb, const float *__restrict__ given, long n, StreamFn *__restrict__ fn,
 	const StreamCarry *__restrict__ carry, StreamEdge *__restrict__ edges, long cap)
 {
+	static_assert(many_v<FB> || bank_v<FB>, "recordings or live channels");
 	const void *samples = fb.samples;
 	long long tile0 = 0;
 	if constexpr (many_v<FB>) {
@@ -529,10 +506,6 @@ __device__ __forceinline__ void fn_scan_wg(const StreamFn *__restrict__ fn, long
 			*c_out = c;
 	}
 }
-__global__ __launch_bounds__(1024) void k_stream_fn_scan(const StreamFn *__restrict__ fn, long ntiles, StreamCarry *__restrict__ carry, long long *__restrict__ counts)
-{
-	fn_scan_wg<false>(fn, ntiles, carry, counts, nullptr, nullptr);
-}
 // The segmented scan: one workgroup per recording composes that recording's tiles alone, from the initial carry (trigger off, no
 // maximum, no edges) - the reset at a recording's start is that nothing of its neighbour is ever composed with it.
 // counts: [recordings][2], cleared by the caller before the scan (a recording without tiles writes nothing)
@@ -557,23 +530,6 @@ __global__ __launch_bounds__(1024) void k_bank_fn_scan(const StreamFn *__restric
 		return;
 	}
 	fn_scan_wg<true>(fn + t0, nt, carry + t0, counts + 2 * (size_t)blockIdx.x, c_in + blockIdx.x, c_out + blockIdx.x);
-}
-
-void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
-	StreamEdge *edges, long cap, long long *counts)
-{
-	const long ntiles = (n + STREAM_TILE - 1) / STREAM_TILE;
-	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
-	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, false>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
-	}
-	hipLaunchKernelGGL(k_stream_fn_scan, dim3(1), dim3(1024), 0, s, fn, ntiles, carry, counts);
-	if (given) {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, true, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
-	} else {
-		RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_tile<RATE, false, true>), dim3((unsigned)ntiles), dim3(256), 0, s, fb, given, n, fn, carry, edges, cap));
-	}
 }
 
 void launch_streams_scan(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, const float *given, StreamFn *fn, StreamCarry *carry,
@@ -608,10 +564,11 @@ constexpr int ACCEPT_GRID = 2048;
 // FB = WindowBatch: the edges of the live channel blockIdx.y, of whose stream only the positions from fb.lo[q] on are in memory.  The
 // host has checked that no edge of this push reads below it (api_bank.cpp); an edge that would is left rejected and reported in
 // fb.below[q]
-template <int RATE, class FB = FrameBatch>
+template <int RATE, class FB>
 __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restrict__ tw, const cf *__restrict__ kern,
 	StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts)
 {
+	static_assert(many_v<FB> || bank_v<FB>, "recordings or live channels");
 	const void *samples = fb.samples;
 	long n_src = fb.samples_per_frame;
 	long long win_lo = 0;
@@ -686,14 +643,9 @@ __global__ __launch_bounds__(256) void k_stream_accept(FB fb, const cf *__restri
 	}
 }
 
-void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
-{
-	const int grid = (int)(cap < ACCEPT_GRID ? cap : ACCEPT_GRID);
-	RX_RATE_SWITCH(rate, hipLaunchKernelGGL(k_stream_accept<RATE>, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern, edges, cap, counts));
-}
 void launch_streams_accept(hipStream_t s, int rate, int n_src, SourceBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts)
 {
-	// (workgroups per recording: the one-call grid shared out, every recording's edges strided over its own)
+	// (workgroups per recording: ACCEPT_GRID shared out, every recording's edges strided over its own)
 	long per = ACCEPT_GRID / n_src < cap ? ACCEPT_GRID / n_src : cap;
 	per = per > 0 ? per : 1;
 	RX_RATE_SWITCH(rate, hipLaunchKernelGGL((k_stream_accept<RATE, SourceBatch>), dim3((unsigned)per, (unsigned)n_src), dim3(256), 0, s, fb, tb.tw_sym, tb.sc_kern,
@@ -707,9 +659,9 @@ void launch_bank_accept(hipStream_t s, int rate, int n_ch, WindowBatch fb, Table
 		edges, cap, counts));
 }
 
-// rec_src (nullable) / src: the recording every record written reads (many recordings in one call)
+// rec_src (nullable) / src: the recording (or live channel) every record written reads
 __device__ __forceinline__ void stream_records_wg(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
-	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base, int *__restrict__ rec_src = nullptr, int src = 0)
+	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base, int *__restrict__ rec_src, int src)
 {
 	const int tid = threadIdx.x;
 	__shared__ long long sh[1024];
@@ -751,13 +703,8 @@ __device__ __forceinline__ void stream_records_wg(int buffer_len, const StreamEd
 	if (tid == 0)
 		counts[1] = base;
 }
-__global__ __launch_bounds__(1024) void k_stream_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
-	SyncState *__restrict__ rec, long max_rec, long long rec_base, long long rej_base)
-{
-	stream_records_wg(buffer_len, edges, cap, counts, rec, max_rec, rec_base, rej_base);
-}
 
-// Many recordings: their accepted preambles counted (counts[q][1]), ...
+// The recordings' accepted preambles counted (counts[q][1]), ...
 __global__ __launch_bounds__(1024) void k_streams_count(const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts)
 {
 	const int tid = threadIdx.x, q = blockIdx.x;
@@ -789,8 +736,8 @@ __global__ __launch_bounds__(1024) void k_streams_first(int n_src, const long lo
 	if (tid == 1023)
 		first[n_src] = sh[1023];
 }
-// ... and every recording's records at its place in it, as k_stream_records writes them for that recording alone (record indices
-// and cumulative rejects count from the recording's own start), with the recording each one reads
+// ... and every recording's records at its place in it (record indices and cumulative rejects count from the recording's own
+// start), with the recording each one reads
 __global__ __launch_bounds__(1024) void k_streams_records(int buffer_len, const StreamEdge *__restrict__ edges, long cap, long long *__restrict__ counts,
 	const long long *__restrict__ first, SyncState *__restrict__ rec, int *__restrict__ rec_src, long long max_per_src, long long max_rec)
 {
@@ -812,12 +759,6 @@ __global__ __launch_bounds__(1024) void k_bank_records(int buffer_len, const Str
 	stream_records_wg(buffer_len, edges + (size_t)q * cap, cap, counts + 2 * (size_t)q, rec + at, (long)room, rec_base[q], rej_base[q], rec_src + at, q);
 }
 
-void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec)
-{
-	int buffer_len = 0;
-	RX_RATE_SWITCH(rate, buffer_len = RateCfg<RATE>::BUFFER_LEN);
-	hipLaunchKernelGGL(k_stream_records, dim3(1), dim3(1024), 0, s, buffer_len, edges, cap, counts, rec, max_rec, 0LL, 0LL);
-}
 void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge *edges, long cap, long long *counts, long long *first,
 	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec)
 {

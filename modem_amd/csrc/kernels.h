@@ -261,10 +261,11 @@ void launch_tx(hipStream_t s, int rate, int n, const uint8_t *payload, Tables tb
 // chunk_flags (nullable): per-chunk device flags cleared here ([0]: the largest row count k_theil_sen met, when above 50)
 void launch_init_sync(hipStream_t s, int n, SyncState *st, const int32_t *skip_counts, int *chunk_flags = nullptr, int32_t *attempt_counts = nullptr);
 
-// ---- stream decode (k_stream.hip, api_stream.cpp): one recording, every preamble in it.  The timing metric is formed tile by tile
-// (STREAM_TILE sample times per workgroup), the trigger (decode.cc:93-116) resolved by a scan over the tiles: each tile publishes
-// what it does to an incoming (Schmitt state, running maximum since the last falling edge, edge count) for either incoming state,
-// one workgroup scans those functions, and the tiles then emit their falling edges in stream order.
+// ---- stream decode (k_stream.hip, api_streams.cpp): every preamble of every recording of a call - one
+// recording is a batch of one.  The timing metric is formed tile by tile (STREAM_TILE sample times per workgroup), the trigger
+// (decode.cc:93-116) resolved by a scan over the tiles: each tile publishes what it does to an incoming (Schmitt state, running
+// maximum since the last falling edge, edge count) for either incoming state, one workgroup per recording scans those functions,
+// and the tiles then emit their falling edges in stream order.
 constexpr int STREAM_TILE = 4096;
 struct StreamFn {                  // a tile (or a run of tiles) as a function of the incoming Schmitt state s = 0 / 1
 	int s_out[2];                  // the state after it
@@ -281,31 +282,24 @@ struct StreamEdge {                // one falling edge, in stream order
 	int symbol_pos;                // window coordinate after pos_err, when accepted
 	float cfo_rad;
 };
-// mono input: the DC blocker's kept states of the whole stream (the layout of k_mono_carries, one frame) by a scan over tiles of
-// 4096 samples; tile_end / tile_in: one double per tile
-void launch_stream_dc(hipStream_t s, FrameBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
-// the trigger scan over n sample times of the 2-channel stream fb (given != nullptr: over that timing sequence instead); counts[0]:
-// falling edges; edges: the first `cap` of them.  fn / carry: one per tile
-void launch_stream_scan(hipStream_t s, int rate, FrameBatch fb, const float *given, long n, StreamFn *fn, StreamCarry *carry,
-	StreamEdge *edges, long cap, long long *counts);
-// decode.cc:110-151 for every edge (of the min(counts[0], cap) written), then the records: counts[1] = accepted edges, rec[k] = the
-// SyncState that k_header finds for the (k+1)-th accepted edge after a round with skip_left = 0 (k < max_rec)
-void launch_stream_accept(hipStream_t s, int rate, FrameBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
-void launch_stream_records(hipStream_t s, int rate, const StreamEdge *edges, long cap, long long *counts, SyncState *rec, long max_rec);
-
-// ---- many recordings in one call (api_streams.cpp): the same scan with the recording as a second grid dimension.
-// Every recording is scanned from its own position 0 with its own tile count, and nothing crosses from one to the next: what
-// enters tile 0 of each is the initial state.  fb.tile0 places a recording's tiles in tile_end / tile_in / fn / carry; ck is
-// [n_src][ck_per_src], z [n_src][fb.samples_per_frame], edges [n_src][cap], counts [n_src][2] (falling edges, accepted preambles).
-// max_len: the longest recording (the grids' first dimension).  The caller clears counts before launch_streams_scan: a recording
-// without tiles writes none
+// The recording is the second grid dimension.  Every recording is scanned from its own position 0 with its own tile count, and
+// nothing crosses from one to the next: what enters tile 0 of each is the initial state.  fb.tile0 places a recording's tiles in
+// tile_end / tile_in / fn / carry; ck is [n_src][ck_per_src], z [n_src][fb.samples_per_frame], edges [n_src][cap], counts
+// [n_src][2] (falling edges, accepted preambles).  max_len: the longest recording (the grids' first dimension).  The caller clears
+// counts before launch_streams_scan: a recording without tiles writes none
+// _dc: mono input: the DC blocker's kept states of every recording (the layout of k_mono_carries, a recording as a frame) by a scan
+// over tiles of 4096 samples; tile_end / tile_in: one double per tile
+// _scan: the trigger scan over the 2-channel recordings fb (given != nullptr: over those timing sequences instead, packed from
+// fb.given0); counts[q][0]: falling edges; edges: the first `cap` of them
+// _accept: decode.cc:110-151 for every edge (of the min(counts[q][0], cap) written)
 void launch_streams_dc(hipStream_t s, int n_src, long max_len, SourceBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck, int ck_per_src);
 void launch_streams_front(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, MonoArgs ma, cf *z);
 void launch_streams_scan(hipStream_t s, int rate, int n_src, long max_len, SourceBatch fb, const float *given, StreamFn *fn, StreamCarry *carry,
 	StreamEdge *edges, long cap, long long *counts);
 void launch_streams_accept(hipStream_t s, int rate, int n_src, SourceBatch fb, Tables tb, StreamEdge *edges, long cap, long long *counts);
-// first[q] (n_src + 1): where recording q's records begin in the packed order, a running sum of min(accepted, max_per_src);
-// rec / rec_src: the SyncState of every packed record below max_rec and the recording it reads
+// the records: counts[q][1] = accepted edges; first[q] (n_src + 1): where recording q's records begin in the packed order, a running
+// sum of min(accepted, max_per_src); rec / rec_src: for every packed record below max_rec, the SyncState that k_header finds for
+// that accepted edge after a round with skip_left = 0, and the recording it reads
 void launch_streams_records(hipStream_t s, int rate, int n_src, const StreamEdge *edges, long cap, long long *counts, long long *first,
 	SyncState *rec, int *rec_src, long long max_per_src, long long max_rec);
 
