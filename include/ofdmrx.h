@@ -55,7 +55,8 @@ extern "C" {
  *      ofdmrx_bank_end, ofdmrx_bank_resident_samples, ofdmrx_bank_preambles, ofdmrx_bank_last_stage_ops
  *   8: ofdmrx_debug_polar_modes, ofdmrx_debug_decode_cons_modes (the single-stage test entries for every mode of the mode table)
  *   9: the three transmitter entries refuse a freq_off outside encode.cc:389's band with OFDMRX_E_ARG (they used to fold the
- *      carriers round Nyquist) */
+ *      carriers round Nyquist);
+ *      added within 1.9 (the minor number stays: a caller detects it by symbol): the Watterson fading channel - ofdmrx_util_fading */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -508,6 +509,30 @@ typedef struct {
 /* delays must lie in [0, samples_per_frame); d_in and d_out must not overlap (else OFDMRX_E_ARG) */
 int ofdmrx_util_channel(ofdmrx_handle *h, const int16_t *d_in, int16_t *d_out, size_t n_frames,
 	size_t samples_per_frame, const ofdmrx_channel *ch);
+
+/* Watterson / ITU-R F.520 fading channel (added within revision 1.9), a new realisation per frame: out frame f is in frame
+ * (f % n_in) - the tiling of ofdmrx_util_awgn_tile, so one transmission can be reused under many fades - through ntaps paths
+ * whose gains are complex Gaussian processes with a Gaussian Doppler spectrum of frequency spread (2 sigma) spread_hz[t] and
+ * mean power |gain|^2, realised by the sum-of-sinusoids method as closed forms of (seed, first_frame + f, sample index): DESIGN.md
+ * section 4.13 is the definition, held sample by sample.  The same seed gives fading that is independent of the noise of
+ * ofdmrx_util_awgn_tile.  A path with spread_hz == 0 is specular: its gain is the constant `gain`.  No per-path Doppler shift: a
+ * common shift is ofdmrx_channel.cfo_hz.  2-channel int16 in and out, DEVICE pointers, asynchronous on the handle's stream.
+ * OFDMRX_E_ARG, before any device call: NULL pointers or zero counts; ntaps outside 1..8; a delay that is negative, >=
+ * samples_per_frame or above OFDMRX_FADING_MAX_DELAY; a gain or spread that is not finite; a spread outside 0 .. rate / 800 (the
+ * gain is interpolated linearly between knots OFDMRX_FADING_KNOT samples apart, which holds while the phase advance per knot stays
+ * well below a radian); ANY overlap of the two buffers (paths read neighbouring samples: there is no in-place form); what the
+ * launch cannot hold: n_out above 2^31 - 1, samples_per_frame above 65535 * 4096. */
+#define OFDMRX_FADING_SINES 16        /* sinusoids per path */
+#define OFDMRX_FADING_KNOT 32         /* samples between two knots of a path's gain */
+#define OFDMRX_FADING_MAX_DELAY 1024  /* samples */
+typedef struct {
+	int32_t ntaps;                                          /* 1..8 */
+	int32_t delays[8];                                      /* samples */
+	float gains_re[8], gains_im[8], spread_hz[8];
+} ofdmrx_fading;
+int ofdmrx_util_fading(ofdmrx_handle *h, const int16_t *d_in, size_t n_in,
+	int16_t *d_out, size_t n_out, size_t samples_per_frame,
+	const ofdmrx_fading *fd, uint64_t seed, uint64_t first_frame);
 
 /* ---- N2: the transmitter on the device (replaces Encoder<value,cmplx,rate>(pcm, inp, count=1, freq_off,
  * call_sign, oper_mode), encode.cc:271,424-436, for batches; rate = the handle's sample_rate).  d_payload:

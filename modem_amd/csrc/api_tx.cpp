@@ -47,6 +47,44 @@ extern "C" int ofdmrx_util_channel(ofdmrx_handle *h, const int16_t *d_in, int16_
 	return 0;
 }
 
+// Watterson fading: everything the kernel relies on is checked here, before any device call
+extern "C" int ofdmrx_util_fading(ofdmrx_handle *h, const int16_t *d_in, size_t n_in, int16_t *d_out, size_t n_out, size_t spf,
+	const ofdmrx_fading *fd, uint64_t seed, uint64_t first_frame)
+{
+	if (!h || !d_in || !d_out || !n_in || !n_out || !spf || !fd || fd->ntaps < 1 || fd->ntaps > 8)
+		return OFDMRX_E_ARG;
+	if (n_out > 0x7fffffffu || (spf + fading_tile_samples() - 1) / fading_tile_samples() > 65535)   // the launch: frames on x, tiles on y
+		return OFDMRX_E_ARG;
+	const float max_spread = (float)h->rate / 800.f;              // a phase advance per knot well below a radian
+	for (int i = 0; i < fd->ntaps; ++i) {
+		if (fd->delays[i] < 0 || (size_t)fd->delays[i] >= spf || fd->delays[i] > OFDMRX_FADING_MAX_DELAY)
+			return OFDMRX_E_ARG;
+		if (!std::isfinite(fd->gains_re[i]) || !std::isfinite(fd->gains_im[i]) || !std::isfinite(fd->spread_hz[i]))
+			return OFDMRX_E_ARG;
+		if (fd->spread_hz[i] < 0.f || fd->spread_hz[i] > max_spread)
+			return OFDMRX_E_ARG;
+	}
+	{
+		const char *a = (const char *)d_in, *b = (const char *)d_out;
+		const size_t fb = spf * 2 * sizeof(int16_t);
+		if (a < b + n_out * fb && b < a + n_in * fb)              // paths read neighbours of what other blocks write: no in-place form
+			return OFDMRX_E_ARG;
+	}
+	HIP_OK(hipSetDevice(h->cfg.device));
+	struct { int ntaps; int delays[8]; float gre[8], gim[8], spread[8]; } fp;
+	fp.ntaps = fd->ntaps;
+	for (int i = 0; i < 8; ++i) {
+		const bool on = i < fd->ntaps;
+		fp.delays[i] = on ? fd->delays[i] : 0;
+		fp.gre[i] = on ? fd->gains_re[i] : 0.f;
+		fp.gim[i] = on ? fd->gains_im[i] : 0.f;
+		fp.spread[i] = on ? fd->spread_hz[i] : 0.f;
+	}
+	launch_fading(h->stream, h->rate, d_in, n_in, d_out, n_out, spf, &fp, seed, first_frame);
+	HIP_OK(hipGetLastError());
+	return 0;
+}
+
 // ---- N2: transmitter on the device (Encoder<value,cmplx,rate>, encode.cc:271-317) -------------------
 extern "C" long long ofdmrx_callsign_value(const char *call_sign) { return call_sign ? callsign_value(call_sign) : -1; }
 

@@ -1,4 +1,4 @@
-// k_channel.hip -- N3: build-owned channel models on the device (AWGN tile; multipath -> CFO -> SFO chain).
+// k_channel.hip -- N3: build-owned channel models on the device (AWGN tile; multipath -> CFO -> SFO chain; Watterson fading).
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -121,6 +121,143 @@ void launch_channel(hipStream_t s, int rate, const int16_t *in, int16_t *out, si
 {
 	ChannelParams cp = *(const ChannelParams *)params;
 	hipLaunchKernelGGL(k_channel, dim3(128, (unsigned)n), dim3(256), 0, s, (const short2 *)in, (short2 *)out, spf, cp, rate);
+}
+
+}  // namespace rx
+
+// ---------------------------------------------------------------- Watterson fading
+// Every path's gain is a sum of FADING_SINES unit phasors whose frequencies are Gaussian (Hoeher), formed at knots FADING_KNOT
+// samples apart and interpolated linearly between them; every quantity is a closed form of (seed, frame, sample index).
+// One workgroup makes FADING_TILE samples of one frame: the frame's (increment, start phase) pairs, then the tile's knot gains
+// into LDS (16 lanes per knot, one phasor each, summed by a butterfly so that the order of the sum is fixed), then one
+// interpolated complex MAC per path and sample.  The delayed input is read through L2: the tile's own 16 KiB and its halo.
+namespace rx {
+
+constexpr int FADING_SINES = 16, FADING_KNOT = 32, FADING_TILE = 4096, FADING_KNOTS = FADING_TILE / FADING_KNOT + 1;
+
+struct __attribute__((packed, aligned(4))) Short2x4 { unsigned a, b, c, d; };   // four I/Q pairs, I in the low half
+
+struct FadingParams {
+	int ntaps;
+	int delays[8];
+	float gre[8], gim[8], spread[8];
+};
+
+__global__ __launch_bounds__(256) void k_fading(const short2 *__restrict__ in, size_t n_in, short2 *__restrict__ out, size_t spf,
+	FadingParams fp, int rate, unsigned long long seed, unsigned long long first_frame)
+{
+	__shared__ unsigned s_inc[8 * FADING_SINES], s_ph0[8 * FADING_SINES];
+	__shared__ float2 s_gain[8][FADING_KNOTS];
+	const size_t f = blockIdx.x;
+	const size_t m0 = (size_t)blockIdx.y * FADING_TILE;
+	const int tid = threadIdx.x;
+	const int len = (int)min((size_t)FADING_TILE, spf - m0);      // the launch has no tile that starts at or past spf
+	const int nk = ((len - 1) >> 5) + 2;                          // knots this tile reads: sample l uses l >> 5 and the next
+	const unsigned long long key = splitmix64(seed ^ splitmix64(first_frame + f + 0x46414445ull));
+	if (tid < FADING_SINES * fp.ntaps) {
+		const int t = tid >> 4;
+		const float spread = fp.spread[t];
+		unsigned inc = 0, ph0 = 0;
+		if (spread != 0.f) {                                      // (a specular path forms no sinusoids)
+			const unsigned long long wf = splitmix64(key + 2ull * tid), wp = splitmix64(key + 2ull * tid + 1ull);
+			const float u1 = ((float)(unsigned)(wf >> 40) + 0.5f) * (1.f / 16777216.f);
+			const float u2 = ((float)(unsigned)((wf >> 8) & 0xffffff) + 0.5f) * (1.f / 16777216.f);
+			const double z = sqrt(-2.0 * log((double)u1)) * cos(2.0 * 3.14159265358979323846 * (double)u2);
+			const double f_hz = 0.5 * (double)spread * z;
+			inc = (unsigned)(unsigned long long)llrint(f_hz * 4294967296.0 / (double)rate);
+			ph0 = (unsigned)(wp >> 32);
+		}
+		s_inc[tid] = inc;
+		s_ph0[tid] = ph0;
+	}
+	__syncthreads();
+	// knot gains: item i = ((t * nk) + j) * 16 + k; its 16 lanes are neighbours of one wave and run every pass together
+	const int items = fp.ntaps * nk * FADING_SINES;
+	for (int base = 0; base < items; base += 256) {
+		const int i = min(base + tid, items - 1);
+		const int k = i & 15, tj = i >> 4, t = tj / nk, j = tj - t * nk;
+		const unsigned phase = s_ph0[t * FADING_SINES + k] + s_inc[t * FADING_SINES + k] * ((unsigned)m0 + (unsigned)(FADING_KNOT * j));
+		// the phase as a signed fraction of a turn, |x| <= 1/2: the conversion is off by at most 2^-26 turns
+		const float x = (float)(int)phase * (1.f / 4294967296.f);
+		float sn, cs;
+		sincospif(2.f * x, &sn, &cs);
+		#pragma unroll
+		for (int m = 1; m < FADING_SINES; m <<= 1) {
+			cs += __shfl_xor(cs, m);
+			sn += __shfl_xor(sn, m);
+		}
+		if (k == 0 && base + tid < items) {
+			const float gr = fp.gre[t], gi = fp.gim[t];
+			const float cr = 0.25f * gr, ci = 0.25f * gi;         // 1 / sqrt(FADING_SINES), exact
+			s_gain[t][j] = fp.spread[t] != 0.f ? make_float2(cr * cs - ci * sn, cr * sn + ci * cs) : make_float2(gr, gi);
+		}
+	}
+	__syncthreads();
+	const short2 *src = in + (f % n_in) * spf;
+	short2 *dst = out + f * spf;
+	// four consecutive samples per thread and pass: they lie between the same two knots, and each path's samples and the result
+	// move as one 16-byte access (frames start on sample boundaries only, so the accesses are 4-byte aligned and no more).
+	// WHOLE = 0: the tile's last one to three samples, when the frame does not end on a group.
+	auto group = [&](int l, auto whole_c) {
+		constexpr bool WHOLE = decltype(whole_c)::value != 0;
+		const size_t m = m0 + l;
+		const int j = l >> 5, r0 = l & (FADING_KNOT - 1);
+		float re[4] = {0.f, 0.f, 0.f, 0.f}, im[4] = {0.f, 0.f, 0.f, 0.f};
+		for (int t = 0; t < fp.ntaps; ++t) {
+			const size_t d = (size_t)fp.delays[t];
+			unsigned x[4] = {0u, 0u, 0u, 0u};
+			if (WHOLE && m >= d) {
+				const Short2x4 q = *(const Short2x4 *)(src + (m - d));
+				x[0] = q.a; x[1] = q.b; x[2] = q.c; x[3] = q.d;
+			} else {                                              // the frame's first samples and its last: x is zero outside the frame
+				#pragma unroll
+				for (int i = 0; i < 4; ++i)
+					if ((WHOLE || l + i < len) && m + i >= d)
+						x[i] = ((const unsigned *)src)[m + i - d];
+			}
+			const float2 g0 = s_gain[t][j], g1 = s_gain[t][j + 1];
+			const float dr = g1.x - g0.x, di = g1.y - g0.y;
+			#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const float fr = (float)(r0 + i) * (1.f / FADING_KNOT);
+				const float gr = g0.x + dr * fr, gi = g0.y + di * fr;
+				const float xr = div_32767((float)(short)(x[i] & 0xffffu)), xi = div_32767((float)(short)(x[i] >> 16));
+				re[i] += xr * gr - xi * gi;
+				im[i] += xr * gi + xi * gr;
+			}
+		}
+		unsigned y[4];
+		#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const float a = fminf(fmaxf(re[i], -1.f), 1.f), b = fminf(fmaxf(im[i], -1.f), 1.f);
+			y[i] = ((unsigned)(int)nearbyintf(32767.f * a) & 0xffffu) | ((unsigned)(int)nearbyintf(32767.f * b) << 16);
+		}
+		if (WHOLE) {
+			Short2x4 q;
+			q.a = y[0]; q.b = y[1]; q.c = y[2]; q.d = y[3];
+			*(Short2x4 *)(dst + m) = q;
+		} else {
+			#pragma unroll
+			for (int i = 0; i < 3; ++i)
+				if (l + i < len)
+					((unsigned *)dst)[m + i] = y[i];
+		}
+	};
+	for (int l = tid * 4; l + 4 <= len; l += 1024)
+		group(l, IntC<1>{});
+	if ((len & 3) && tid == ((len >> 2) & 255))
+		group(len & ~3, IntC<0>{});
+}
+
+size_t fading_tile_samples() { return FADING_TILE; }
+
+void launch_fading(hipStream_t s, int rate, const int16_t *in, size_t n_in, int16_t *out, size_t n_out, size_t spf, const void *params,
+	uint64_t seed, uint64_t first_frame)
+{
+	FadingParams fp = *(const FadingParams *)params;
+	const size_t tiles = (spf + FADING_TILE - 1) / FADING_TILE;
+	hipLaunchKernelGGL(k_fading, dim3((unsigned)n_out, (unsigned)tiles), dim3(256), 0, s, (const short2 *)in, n_in, (short2 *)out, spf, fp,
+		rate, (unsigned long long)seed, (unsigned long long)first_frame);
 }
 
 }  // namespace rx

@@ -255,6 +255,9 @@ void launch_fft_debug(hipStream_t s, int rate, int n, int len, int sign, const c
 void launch_awgn_tile(hipStream_t s, const int16_t *base, size_t n_base, int16_t *out, size_t n_out,
 	size_t spf, float sigma, uint64_t seed, uint64_t first_frame);
 void launch_channel(hipStream_t s, int rate, const int16_t *in, int16_t *out, size_t n, size_t spf, const void *params);
+size_t fading_tile_samples();   // samples per workgroup of k_fading: the launch holds 65535 of them per frame
+void launch_fading(hipStream_t s, int rate, const int16_t *in, size_t n_in, int16_t *out, size_t n_out, size_t spf, const void *params,
+	uint64_t seed, uint64_t first_frame);
 size_t tx_big_scratch_bytes(int rate, int n, int nsym);
 void launch_tx(hipStream_t s, int rate, int n, const uint8_t *payload, Tables tb, const void *tp, const cf *tw_sym4,
 	uint32_t *code, cf *rowsym, cf *tdom, cf *big_scratch, void *pcm);

@@ -31,7 +31,7 @@ EXPORTS = [
     "ofdmrx_feed_begin", "ofdmrx_feed_push", "ofdmrx_feed_end", "ofdmrx_feed_lag", "ofdmrx_feed_resident_samples",
     "ofdmrx_decode_streams", "ofdmrx_decode_streams_device", "ofdmrx_debug_streams_edges",
     "ofdmrx_bank_begin", "ofdmrx_bank_push", "ofdmrx_bank_end", "ofdmrx_bank_resident_samples", "ofdmrx_bank_preambles",
-    "ofdmrx_bank_last_stage_ops",
+    "ofdmrx_bank_last_stage_ops", "ofdmrx_util_fading",
 ]
 
 
@@ -66,6 +66,27 @@ MAX_SKIP = 64
 class Channel(C.Structure):
     _fields_ = [("cfo_hz", C.c_float), ("sfo_ppm", C.c_float), ("ntaps", C.c_int32), ("delays", C.c_int32 * 8),
                 ("gains_re", C.c_float * 8), ("gains_im", C.c_float * 8)]
+
+
+class Fading(C.Structure):
+    _fields_ = [("ntaps", C.c_int32), ("delays", C.c_int32 * 8), ("gains_re", C.c_float * 8), ("gains_im", C.c_float * 8),
+                ("spread_hz", C.c_float * 8)]
+
+
+FADING_SINES, FADING_KNOT, FADING_MAX_DELAY = 16, 32, 1024
+# ITU-R F.520 presets: two paths of equal mean power, (differential delay in ms, frequency spread (2 sigma) in Hz)
+WATTERSON = {"good": (0.5, 0.1), "moderate": (1.0, 0.5), "poor": (2.0, 1.0)}
+
+
+def watterson(preset, sample_rate):
+    """the paths [(delay, complex gain, spread_hz), ...] of an F.520 preset for Receiver.fading: two paths of gain 1 / sqrt 2, the
+    second delayed by round(ms * rate / 1000) samples"""
+    try:
+        ms, spread = WATTERSON[preset]
+    except KeyError:
+        raise ValueError("watterson: preset must be one of %s" % ", ".join(WATTERSON))
+    g = complex(0.5 ** 0.5, 0.0)
+    return [(0, g, spread), (int(round(ms * sample_rate / 1000.0)), g, spread)]
 
 
 class Timing(C.Structure):
@@ -169,6 +190,8 @@ def load_library():
     L.ofdmrx_util_awgn_tile.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                         C.c_float, C.c_uint64, C.c_uint64]
     L.ofdmrx_util_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(Channel)]
+    L.ofdmrx_util_fading.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(Fading),
+                                     C.c_uint64, C.c_uint64]
     L.ofdmrx_tx_frame_samples.restype = C.c_long
     L.ofdmrx_tx_frame_samples.argtypes = [C.c_int]
     L.ofdmrx_frame_samples.restype = C.c_long
@@ -510,6 +533,17 @@ class Receiver:
         for i, (d, g) in enumerate(multipath):
             ch.delays[i], ch.gains_re[i], ch.gains_im[i] = int(d), float(complex(g).real), float(complex(g).imag)
         self._check(self._lib.ofdmrx_util_channel(self._h, d_in, d_out, n, spf, C.byref(ch)))
+
+    def fading(self, d_in, n_in, d_out, n_out, spf, paths, seed, first_frame=0):
+        """Watterson fading on device-resident 2-channel int16 frames: out frame f = in frame f % n_in under the realisation of
+        (seed, first_frame + f); paths = [(delay, complex gain, spread_hz), ...] (watterson() gives the F.520 presets); asynchronous"""
+        fd = Fading()
+        if len(paths) > 8:
+            raise OfdmRxError("fading: at most 8 paths")
+        fd.ntaps = len(paths)
+        for i, (d, g, s) in enumerate(paths):
+            fd.delays[i], fd.gains_re[i], fd.gains_im[i], fd.spread_hz[i] = int(d), float(complex(g).real), float(complex(g).imag), float(s)
+        self._check(self._lib.ofdmrx_util_fading(self._h, d_in, n_in, d_out, n_out, spf, C.byref(fd), seed, first_frame))
 
     def tx_frame_samples(self, mode=6):
         return int(self._lib.ofdmrx_frame_samples(self.sample_rate, mode))

@@ -2,7 +2,8 @@
 """BER / FER sweep over the AWGN noise LEVEL (BASELINE.json configs[4]): Monte-Carlo throughput + BER curve.
 
 Every point decodes `--frames` frames made entirely on the device: random payloads -> device transmitter (N2) ->
-independent AWGN (N3, counter RNG keyed by the global frame index, never reused across points).
+[Watterson fading with --fading, a realisation per frame ->] independent AWGN (N3, counter RNGs keyed by the global frame index,
+never reused across points).
 With torchrun the frames of every point are sharded over the ranks; the only reduction is the sum of four
 integer counters per point (no collective on the data path).  Prints one JSON line per point and a summary.
 
@@ -29,6 +30,9 @@ def main():
     ap.add_argument("--tx-reuse", type=int, default=1,
                     help="decode every transmitted batch this many times, each with fresh noise (1 = every frame freshly "
                          "transmitted, the default; the noise realisations are always distinct)")
+    ap.add_argument("--fading", choices=("good", "moderate", "poor"), default=None,
+                    help="Watterson / ITU-R F.520 fading between the transmitter and the noise: every frame sees a channel realisation "
+                         "of its own, keyed by its global frame index (default: off, every frame sees the clean transmission)")
     ap.add_argument("--levels", type=float, nargs="*", default=None, help="explicit noise levels in dB (overrides --lo/--hi/--step)")
     ap.add_argument("--resume", default=None,
                     help="file: every finished point is appended to it as a JSON line; points already in it are skipped "
@@ -74,7 +78,8 @@ def main():
     if args.resume and os.path.exists(args.resume):
         with open(args.resume) as fh:
             done_pts = [json.loads(ln) for ln in fh if ln.startswith("{") and "noise_db" in ln]
-        done_pts = [p for p in done_pts if p.get("frames") == args.frames and p.get("seed", args.seed) == args.seed]
+        done_pts = [p for p in done_pts if p.get("frames") == args.frames and p.get("seed", args.seed) == args.seed
+                    and p.get("fading") == args.fading]
     all_levels = levels
     skip = {round(p["noise_db"], 6) for p in done_pts}
     # (the noise seed of a frame is keyed by its level's index in the FULL list, so a resumed point equals a fresh one)
@@ -91,12 +96,14 @@ def main():
             f += n
     gli = [level_index[round(float(db), 6)] for db in levels]   # position of each remaining level in the full list
 
-    d_clean = torch.empty((nb, spf, 2), dtype=torch.int16, device=dev) if args.tx_reuse > 1 else None
+    # fading reads neighbouring samples, so it has no in-place form: the transmitter then writes to a buffer of its own as well
+    paths = modem_amd.watterson(args.fading, 8000) if args.fading else None
+    d_clean = torch.empty((nb, spf, 2), dtype=torch.int16, device=dev) if args.tx_reuse > 1 or paths else None
     made, made_n = [0], [0]
 
     def make(w, q):
-        """random payloads -> device transmitter -> AWGN for batch w into buffer q, on the tx stream.  With --tx-reuse K
-        the clean waveforms (and payloads) of a batch serve K consecutive batches of the same size, each with its own noise"""
+        """random payloads -> device transmitter [-> fading] -> AWGN for batch w into buffer q, on the tx stream.  With --tx-reuse K
+        the clean waveforms (and payloads) of a batch serve K consecutive batches of the same size, each with its own noise (and fade)"""
         li, db, f, n = w
         gidx = gli[li] * args.frames + f         # global frame index: distinct noise everywhere
         with torch.cuda.stream(tx_stream):
@@ -112,6 +119,9 @@ def main():
             else:
                 d_pay[q][:n] = d_pay[q ^ 1][:n]
             src = d_clean if d_clean is not None else d_in[q]
+            if paths:
+                tx.fading(src.data_ptr(), n, d_in[q].data_ptr(), n, spf, paths, args.seed, gidx)   # a channel per frame
+                src = d_in[q]
             tx.awgn_tile(src.data_ptr(), n, d_in[q].data_ptr(), n, spf, db, args.seed, gidx)   # in place when not reusing
             made[0] += 1
             ev_ready[q].record(tx_stream)
@@ -157,6 +167,8 @@ def main():
                 pt = {"noise_db": db, "frames": counters[0], "fer": counters[1] / counters[0],
                       "ber": counters[2] / (43040.0 * counters[0]), "declared_lost": counters[3],
                       "frames_per_s": counters[0] / secs, "seed": args.seed}
+                if args.fading:
+                    pt["fading"] = args.fading
                 summary.append(pt)
                 print(json.dumps(pt), flush=True)
                 if args.resume:
