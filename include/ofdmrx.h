@@ -56,7 +56,9 @@ extern "C" {
  *   8: ofdmrx_debug_polar_modes, ofdmrx_debug_decode_cons_modes (the single-stage test entries for every mode of the mode table)
  *   9: the three transmitter entries refuse a freq_off outside encode.cc:389's band with OFDMRX_E_ARG (they used to fold the
  *      carriers round Nyquist);
- *      added within 1.9 (the minor number stays: a caller detects it by symbol): the Watterson fading channel - ofdmrx_util_fading */
+ *      added within 1.9 (the minor number stays: a caller detects it by symbol): the Watterson fading channel - ofdmrx_util_fading;
+ *      the wideband front end - ofdmrx_util_channelize_taps, ofdmrx_util_channelize, ofdmrx_bank_begin_wideband,
+ *      ofdmrx_bank_push_wideband */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -385,6 +387,32 @@ long long ofdmrx_bank_resident_samples(ofdmrx_handle *h, size_t channel);
 long long ofdmrx_bank_preambles(ofdmrx_handle *h, size_t channel);
 long long ofdmrx_bank_last_stage_ops(ofdmrx_handle *h);
 
+/*
+ * Wideband bank (added within revision 1.9, detected by symbol): a bank whose channels are all cut from ONE wideband I/Q capture by
+ * the wideband front end (ofdmrx_util_channelize below) on the device, as the capture arrives.
+ *   begin_wideband  n_channels (1 .. 65535) channels centred at centre_hz[c] (a HOST array) of a capture at decim x the handle's
+ *                   rate, arriving as interleaved I/Q of sample_format.  The channels are 2-channel F32 at the handle's rate.
+ *   push_wideband   n_wide more wideband sample frames (0 allowed; <= 1 << 26; a HOST pointer).  After W frames in all every channel
+ *                   has been fed ceil(W / decim) samples.  end != 0: every channel's stream is over after these samples.  The output
+ *                   arguments are those of ofdmrx_bank_push.  The block is copied once, behind the last T - 1 wideband samples, and
+ *                   one kernel launch writes every channel's new samples into its window.
+ * ofdmrx_bank_end, ofdmrx_bank_resident_samples, ofdmrx_bank_preambles and ofdmrx_bank_last_stage_ops serve a wideband bank
+ * unchanged; ofdmrx_bank_last_stage_ops stays independent of n_channels.
+ * The contract: for every channel c and ANY cutting of the capture into pushes (lengths that are no multiple of decim, and zero,
+ * included) the records of c equal what ofdmrx_decode_stream (F32, 2 channels) returns for row c of ofdmrx_util_channelize over the
+ * whole capture - every payload byte and every byte of every ofdmrx_frame_result.  (The front end's outputs do not depend on where a
+ * block boundary falls, and a bank channel equals the one-call decode of its samples.)  sc_start counts the channel's samples: the
+ * front end's group delay puts it 12 samples behind the signal.
+ * OFDMRX_E_ARG, before any device call: what ofdmrx_bank_begin and ofdmrx_bank_push refuse (an open feed or bank, NULL outputs with
+ * max_records > 0, NULL samples with n_wide > 0, samples off the sample-frame boundary, samples after the end, ...); NULL centre_hz;
+ * decim outside 2..32; a centre that is not finite or lies outside +- decim rate / 2; ofdmrx_bank_push on a wideband bank;
+ * ofdmrx_bank_push_wideband on a plain bank; ofdmrx_util_channelize while any bank is open (a wideband bank owns the taps and
+ * increments on the device).
+ */
+int ofdmrx_bank_begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int decim, int sample_format);
+int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, size_t n_wide, int end, size_t max_records, uint8_t *payload_out,
+	ofdmrx_frame_result *results, int32_t *record_channel, int64_t *record_index, size_t *n_records, size_t *n_left);
+
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);
 int ofdmrx_chunk_frames(ofdmrx_handle *h);
@@ -533,6 +561,30 @@ typedef struct {
 int ofdmrx_util_fading(ofdmrx_handle *h, const int16_t *d_in, size_t n_in,
 	int16_t *d_out, size_t n_out, size_t samples_per_frame,
 	const ofdmrx_fading *fd, uint64_t seed, uint64_t first_frame);
+
+/* Wideband front end (added within revision 1.9, detected by symbol): one wideband I/Q capture at decim x the handle's rate ->
+ * n_channels receiver channels at the handle's rate, each mixed down from its centre frequency, low-pass filtered and decimated.
+ * DESIGN.md section 4.14 is the definition, held component by component to a float64 model:
+ *   taps    K = 12 decim, T = 2 K + 1, h[k] = (0.75 / decim) sinc(0.75 (k - K) / decim) blackman(k, T), computed in double,
+ *           normalised to sum 1, rounded once to fp32.  Flat within 0.01 dB up to rate / 4, below -70 dB from rate / 2 on.
+ *   phase   inc_c = (uint32) llrint(centre_hz[c] 2^32 / (decim rate)); the phase at ABSOLUTE wideband index m is (inc_c m) mod 2^32
+ *   output  y_c[n] = sum_k h[k] x[n decim - k] e^{-2 pi i phase_c(n decim - k) / 2^32}, x zero at negative indices; fp32 I/Q, no clip
+ * Every output is a closed form of absolute indices: there is no state, and a capture cut into blocks (each block handed over with
+ * the T - 1 samples before it) gives the same bytes as one call.  W samples give ceil(W / decim) outputs per channel.  Output n is
+ * wideband time n decim - K: a signal appears 12 output samples late (ofdmrx_frame_result.sc_start lies 12 behind).
+ * ofdmrx_util_channelize_taps: host only; writes the T taps, returns T; decim outside 2..32 or NULL taps: OFDMRX_E_ARG.
+ * ofdmrx_util_channelize: DEVICE buffers, asynchronous on the handle's stream (a call with another decim or other centres than
+ * the call before waits for the stream first); centre_hz is a HOST array.  d_in holds the wideband positions in_first .. in_first +
+ * n_in - 1 as interleaved I/Q of sample_format (scaled as the decoder scales its input); output n (out_first .. out_first + n_out
+ * - 1) of channel c lands at d_out + 2 (c out_stride + n - out_first) floats.  OFDMRX_E_ARG, before any device call and with the
+ * output untouched: NULL pointers or zero counts; n_channels outside 1..65535; decim outside 2..32; a bad format; a negative in_first
+ * or out_first; out_stride < n_out; a centre that is not finite or lies outside +- decim rate / 2; a position the outputs need that
+ * is not in the buffer - in_first > 0 and out_first decim - (T - 1) < in_first, or (out_first + n_out - 1) decim > in_first + n_in -
+ * 1 (with in_first == 0 the positions below 0 are zeros); d_out overlapping d_in; d_in off the sample-frame boundary, d_out off 8
+ * bytes; positions or counts above 2^50; a handle with an open feed or bank. */
+int ofdmrx_util_channelize_taps(int decim, float *taps);
+int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
 
 /* ---- N2: the transmitter on the device (replaces Encoder<value,cmplx,rate>(pcm, inp, count=1, freq_off,
  * call_sign, oper_mode), encode.cc:271,424-436, for batches; rate = the handle's sample_rate).  d_payload:

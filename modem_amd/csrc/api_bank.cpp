@@ -9,6 +9,10 @@
 //   when its frame is complete) | ONE decode_records call over every record that is due on any channel, in channel then preamble
 //   order: the records of many channels share chunks | delivery
 //   end:  the last partial tile of every channel with n = the samples fed, every pending preamble, delivery
+// A WIDEBAND bank (ofdmrx_bank_begin_wideband) is fed one wideband capture instead: its channels are 2-channel F32 at
+// the handle's rate, and "the new samples" of a push are made on the device - the wideband block is copied once behind the last
+// T - 1 wideband samples (kept on the host and sent with it), and ONE k_channelize launch writes every channel's new samples straight
+// into its window.  Everything behind that step is the same code.
 // The windows of all channels live in one slab pair [n_channels][cap] with a common capacity; channel c's window begins at its own
 // base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch: it is handed the address position 0
 // WOULD have and n = the samples fed, so a position past the end reads as zero as in a one-call decode); positions below the base are
@@ -49,6 +53,11 @@ struct ofdmrx_bank {
 	long long ops = 0;                                        // launches + copies + synchronisations of the last call's own stages
 	bool ending = false;
 	bool as_feed = false;                                     // opened by ofdmrx_feed_begin: the ofdmrx_feed_* entries serve it, ofdmrx_bank_* refuse it
+	// a wideband bank: decimation, the format of the wideband samples, how many have been pushed, and the last min(wfed, T - 1) of them
+	bool wide = false;
+	int decim = 0, wfmt = 0;
+	long long wfed = 0;
+	std::vector<char> wtail;
 };
 
 void bank_free(ofdmrx_handle *h)
@@ -133,7 +142,8 @@ WindowBatch window_batch(const ofdmrx_bank &b, const int *src_of, bool raw = fal
 }
 
 // One call's work: every channel c takes add[c] more samples (nullable: none), those with fin[c] end behind them.
-int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t *add, const std::vector<uint8_t> &fin)
+// A wideband bank: samples are n_wide wideband sample frames, and add[c] is what they give every channel.
+int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t *add, const std::vector<uint8_t> &fin, size_t n_wide = 0)
 {
 	ofdmrx_bank &b = *h->bank;
 	hipStream_t s = h->stream;
@@ -205,9 +215,10 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 	// ---- 2. the new samples, packed so that every share lies as its place in the window does modulo 16
 	size_t packed = 0;
 	long long pl_most = 0;
+	const size_t wunit = 2 * sample_bytes(b.wfmt);                // (a wideband bank: bytes per wideband sample frame)
 	try {
-		size_t total = 0;
-		for (size_t c = 0; c < C && add; ++c)
+		size_t total = b.wide ? b.wtail.size() + n_wide * wunit : 0;
+		for (size_t c = 0; c < C && add && !b.wide; ++c)
 			total += add[c] * unit + 32;
 		b.stage_h.resize(total);
 	} catch (const std::bad_alloc &) {
@@ -222,6 +233,10 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 				return OFDMRX_E_ARG;
 			}
 			const long long dst = (long long)(uintptr_t)b.raw[o].p + ((long long)c * ncap + (k.fed - nb[c])) * (long long)unit;
+			if (b.wide) {                                             // k_channelize writes the share there
+				at(P_PL_DST, c) = dst;
+				continue;
+			}
 			const size_t src = (packed + 15) / 16 * 16 + (size_t)(dst & 15);
 			std::memcpy(b.stage_h.data() + src, samples + c * stride, n * unit);
 			at(P_PL_SRC, c) = (long long)src;                         // (the staging buffer's address joins it below)
@@ -300,6 +315,43 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 		HIP_OK(hipMemcpyAsync(b.stage.p, b.stage_h.data(), packed, hipMemcpyHostToDevice, s));
 		launch_bank_copy(s, (int)C, 1, P, pl_most, dpar + P_PL_SRC * P, dpar + P_PL_DST * P, dpar + P_PL_BYTES * P);
 		b.ops += 2;
+	}
+	if (b.wide && n_wide) {
+		// the block behind the kept tail, one copy; one launch for every channel's new outputs ceil(W_old / D) .. ceil(W_new / D) - 1.
+		// The first of them reads from ceil(W_old / D) D - (T - 1) >= W_old - (T - 1) on: inside the tail, or below position 0
+		const long long D = b.decim, T = 24 * D + 1, tail = (long long)(b.wtail.size() / wunit);
+		const long long o0 = (b.wfed + D - 1) / D, o1 = (b.wfed + (long long)n_wide + D - 1) / D;
+		std::memcpy(b.stage_h.data(), b.wtail.data(), b.wtail.size());
+		std::memcpy(b.stage_h.data() + b.wtail.size(), samples, n_wide * wunit);
+		if (o1 > o0) {
+			if ((size_t)(o1 - o0) != (add ? add[0] : 0) || (tail < T - 1 && tail != b.wfed)) {
+				g_last_error = "bank: the wideband tail does not hold what the new outputs read";
+				return OFDMRX_E_ARG;
+			}
+			r = b.stage.ensure(b.stage_h.size());
+			if (r)
+				return r;
+			HIP_OK(hipMemcpyAsync(b.stage.p, b.stage_h.data(), b.stage_h.size(), hipMemcpyHostToDevice, s));
+			ChannelizeArgs a{};
+			a.in = b.stage.p;
+			a.fmt = b.wfmt;
+			a.decim = b.decim;
+			a.in_first = b.wfed - tail;
+			a.n_in = tail + (long long)n_wide;
+			a.taps = h->chz_taps.as<float>();
+			a.inc = h->chz_inc.as<unsigned>();
+			a.n_channels = (int)C;
+			a.out_first = o0;
+			a.n_out = o1 - o0;
+			a.out = nullptr;
+			a.out_stride = 0;
+			a.dst = dpar + P_PL_DST * P;
+			launch_channelize(s, a);
+			b.ops += 2;
+		}
+		const size_t keep = std::min(b.stage_h.size(), (size_t)(T - 1) * wunit);
+		b.wtail.assign(b.stage_h.end() - (long)keep, b.stage_h.end());
+		b.wfed += (long long)n_wide;
 	}
 	HIP_OK(hipGetLastError());
 	// ---- 3. mono input: every channel's DC-blocker states and analytic signal, each composed from that channel's own positions alone
@@ -630,7 +682,7 @@ extern "C" int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t st
 	size_t *n_left)
 {
 	int r = out_args(h, max_records, payload_out, results, n_records, n_left);
-	if (r || (max_records && (!record_channel || !record_index)) || !n_samples || !live(h, false))
+	if (r || (max_records && (!record_channel || !record_index)) || !n_samples || !live(h, false) || h->bank->wide)
 		return OFDMRX_E_ARG;
 	ofdmrx_bank &b = *h->bank;
 	const size_t unit = frame_bytes(b);
@@ -651,6 +703,54 @@ extern "C" int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t st
 		for (size_t c = 0; c < b.C && ends; ++c)
 			fin[c] = ends[c] && !b.ch[c].ended;
 		r = bank_step(h, (const char *)samples, stride_bytes, n_samples, fin);
+		if (r)
+			return r;
+	}
+	deliver(h, max_records, payload_out, results, record_channel, record_index, n_records, n_left);
+	return 0;
+}
+
+// ---- a wideband bank: one wideband capture in, every channel made from it on the device
+extern "C" int ofdmrx_bank_begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int decim, int fmt)
+{
+	if (!h || !centre_hz || decim < 2 || decim > 32 || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || n_channels < 1 || n_channels > 65535)
+		return OFDMRX_E_ARG;
+	if (h->bank)
+		return OFDMRX_E_ARG;
+	for (size_t c = 0; c < n_channels; ++c)
+		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * (double)decim * (double)h->rate)
+			return OFDMRX_E_ARG;
+	int r = begin(h, n_channels, OFDMRX_FMT_F32, 2, false);
+	if (r)
+		return r;
+	if ((r = channelize_setup(h, decim, centre_hz, n_channels))) {
+		bank_free(h);
+		return r;
+	}
+	h->bank->wide = true;
+	h->bank->decim = decim;
+	h->bank->wfmt = fmt;
+	return 0;
+}
+
+extern "C" int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, size_t n_wide, int end_all, size_t max_records, uint8_t *payload_out,
+	ofdmrx_frame_result *results, int32_t *record_channel, int64_t *record_index, size_t *n_records, size_t *n_left)
+{
+	int r = out_args(h, max_records, payload_out, results, n_records, n_left);
+	if (r || (max_records && (!record_channel || !record_index)) || !live(h, false) || !h->bank->wide)
+		return OFDMRX_E_ARG;
+	ofdmrx_bank &b = *h->bank;
+	const size_t wunit = 2 * sample_bytes(b.wfmt);
+	if (n_wide > ((size_t)1 << 26) || (n_wide && (!samples || (size_t)samples % wunit || b.ending || b.ch[0].ended)))
+		return OFDMRX_E_ARG;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	b.ops = 0;
+	if (!b.ending) {
+		// every channel takes the outputs the block completes: W samples have given ceil(W / D) of them
+		const long long D = b.decim;
+		const std::vector<size_t> add(b.C, (size_t)((b.wfed + (long long)n_wide + D - 1) / D - (b.wfed + D - 1) / D));
+		const std::vector<uint8_t> fin(b.C, (uint8_t)(end_all && !b.ch[0].ended));
+		r = bank_step(h, (const char *)samples, 0, add.data(), fin, n_wide);
 		if (r)
 			return r;
 	}

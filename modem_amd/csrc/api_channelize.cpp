@@ -1,0 +1,116 @@
+// api_channelize.cpp -- the wideband front end behind include/ofdmrx.h: the taps, the phase increments,
+// ofdmrx_util_channelize.  Everything the kernel relies on is checked here, before any device call.
+#include "api_internal.h"
+
+namespace rx {
+
+int channelize_taps(int decim, float *taps)
+{
+	const int D = decim, K = 12 * D, T = 2 * K + 1;
+	const double pi = 3.14159265358979323846;
+	std::vector<double> h((size_t)T);
+	double sum = 0.0;
+	for (int k = 0; k < T; ++k) {
+		const double t = 0.75 * (double)(k - K) / (double)D;
+		const double sinc = k == K ? 1.0 : std::sin(pi * t) / (pi * t);
+		const double w = 0.42 - 0.5 * std::cos(2.0 * pi * (double)k / (double)(T - 1)) + 0.08 * std::cos(4.0 * pi * (double)k / (double)(T - 1));
+		h[(size_t)k] = 0.75 / (double)D * sinc * w;
+		sum += h[(size_t)k];
+	}
+	for (int k = 0; k < T; ++k)
+		taps[k] = (float)(h[(size_t)k] / sum);
+	return T;
+}
+
+unsigned channelize_inc(double centre_hz, double rw)
+{
+	return (unsigned)(unsigned long long)std::llrint(centre_hz * 4294967296.0 / rw);
+}
+
+}  // namespace rx
+
+// the taps of `decim` and the increments of the centres on the device.  What is there already stays (a bank's pushes, a capture cut
+// into blocks); anything else waits for the stream first, since a kernel enqueued earlier may still read the old values
+int channelize_setup(ofdmrx_handle *h, int decim, const double *centre_hz, size_t n_channels)
+{
+	const double rw = (double)decim * (double)h->rate;
+	std::vector<unsigned> inc(n_channels);
+	for (size_t c = 0; c < n_channels; ++c) {
+		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw)
+			return OFDMRX_E_ARG;
+		inc[c] = channelize_inc(centre_hz[c], rw);
+	}
+	if (decim == h->chz_decim && inc == h->chz_inc_h)
+		return 0;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	HIP_OK(hipStreamSynchronize(h->stream));
+	h->chz_decim = 0;
+	h->chz_taps_h.resize((size_t)(24 * decim + 1));
+	channelize_taps(decim, h->chz_taps_h.data());
+	h->chz_inc_h = inc;
+	int r = h->chz_taps.ensure(h->chz_taps_h.size() * sizeof(float));
+	r = r ? r : h->chz_inc.ensure(n_channels * sizeof(unsigned));
+	if (r)
+		return r;
+	HIP_OK(hipMemcpyAsync(h->chz_taps.p, h->chz_taps_h.data(), h->chz_taps_h.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+	HIP_OK(hipMemcpyAsync(h->chz_inc.p, h->chz_inc_h.data(), n_channels * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+	h->chz_decim = decim;
+	return 0;
+}
+
+extern "C" int ofdmrx_util_channelize_taps(int decim, float *taps)
+{
+	if (decim < 2 || decim > 32 || !taps)
+		return OFDMRX_E_ARG;
+	return channelize_taps(decim, taps);
+}
+
+extern "C" int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+{
+	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
+	if (!h || !d_in || !d_out || !centre_hz || !n_in || !n_out || n_channels < 1 || n_channels > 65535 || decim < 2 || decim > 32)
+		return OFDMRX_E_ARG;
+	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || out_first < 0 || out_stride < n_out)
+		return OFDMRX_E_ARG;
+	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)channelize_max_outputs() || out_stride > (size_t)FAR / 65536)
+		return OFDMRX_E_ARG;
+	const size_t unit = 2 * sample_bytes(sample_format);
+	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))
+		return OFDMRX_E_ARG;
+	const long long D = decim, T = 24 * D + 1;
+	if ((in_first > 0 && out_first * D - (T - 1) < in_first) || (out_first + (long long)n_out - 1) * D > in_first + (long long)n_in - 1)
+		return OFDMRX_E_ARG;                                      // a position the outputs need is not in the buffer
+	{
+		const char *a = (const char *)d_in, *b = (const char *)d_out;
+		const size_t out_bytes = ((n_channels - 1) * out_stride + n_out) * sizeof(float2);
+		if (a < b + out_bytes && b < a + n_in * unit)
+			return OFDMRX_E_ARG;
+	}
+	for (size_t c = 0; c < n_channels; ++c)
+		if (!std::isfinite(centre_hz[c]))
+			return OFDMRX_E_ARG;
+	if (h->busy_live())                                           // (an open wideband bank owns the taps and increments on the device)
+		return OFDMRX_E_ARG;
+	int r = channelize_setup(h, decim, centre_hz, n_channels);
+	if (r)
+		return r;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	ChannelizeArgs a{};
+	a.in = d_in;
+	a.fmt = sample_format;
+	a.decim = decim;
+	a.in_first = in_first;
+	a.n_in = (long long)n_in;
+	a.taps = h->chz_taps.as<float>();
+	a.inc = h->chz_inc.as<unsigned>();
+	a.n_channels = (int)n_channels;
+	a.out_first = out_first;
+	a.n_out = (long long)n_out;
+	a.out = d_out;
+	a.out_stride = (long long)out_stride;
+	a.dst = nullptr;
+	launch_channelize(h->stream, a);
+	HIP_OK(hipGetLastError());
+	return 0;
+}

@@ -226,6 +226,11 @@ struct ofdmrx_handle {
 	long sxs_edge_cap = 0;    // every recording's share of the edge buffer (one recording: all of it)
 	struct ofdmrx_bank *bank = nullptr;   // the open bank of live channels or - a bank of one - the open feed (api_bank.cpp): one per handle
 	bool busy_live() const { return bank != nullptr; }   // a handle with an open feed or bank decodes nothing else
+	// the wideband front end (api_channelize.cpp): the taps and phase increments on the device, and what they were made from
+	DevBuf chz_taps, chz_inc;
+	int chz_decim = 0;
+	std::vector<float> chz_taps_h;
+	std::vector<unsigned> chz_inc_h;
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -265,4 +270,5 @@ int finish_call(ofdmrx_handle *h, int r);                                       
 // channel q would lie at fb.samples + org[q] bytes and the channel has len[q] sample frames so far (kernels.h: WindowBatch)
 struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; const long long *org = nullptr; const long long *len = nullptr; };
 int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources &srcs);
+int channelize_setup(ofdmrx_handle *h, int decim, const double *centre_hz, size_t n_channels);   // api_channelize.cpp
 void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank (or feed) and its windows go

@@ -11,6 +11,9 @@
 // `decode_stream --live --batch OUTROOT A.wav B.wav ...`: the same recordings read in blocks of one second, in lock step, and pushed
 // through one bank of live channels (ofdmrx_bank_*); a file that runs out ends its channel.  Every record is written as soon as it
 // is returned: the files and lines of --batch, up to the order of the lines.
+// `decode_stream --wideband DECIM F1,F2,... OUTROOT WIDE.wav`: one wideband I/Q capture (2 channels, DECIM x a supported rate) read
+// in blocks of one wideband second and pushed through a wideband bank (ofdmrx_bank_begin_wideband): channel i, centred at Fi Hz, goes
+// to OUTROOT/<i>/<k>.dat with the `<i>:` summary lines of --live --batch.
 #include "wav_read.h"
 #include <algorithm>
 #include <cstdlib>
@@ -273,15 +276,97 @@ static int run_live_batch(const std::string &outroot, int n_inputs, char **input
 	return (r || !written) ? 1 : 0;
 }
 
+// one wideband capture block by block through a wideband bank
+static int run_wideband(int decim, const char *centre_list, const std::string &outroot, const char *input_name)
+{
+	std::vector<double> centres;
+	for (const char *p = centre_list; *p;) {
+		char *e = nullptr;
+		const double f = std::strtod(p, &e);
+		if (e == p || (*e && *e != ',')) {
+			std::fprintf(stderr, "Centre frequencies are a comma-separated list of Hz.\n");
+			return 1;
+		}
+		centres.push_back(f);
+		p = *e ? e + 1 : e;
+	}
+	if (decim < 2 || decim > 32 || centres.empty() || centres.size() > 65535) {
+		std::fprintf(stderr, "A wideband bank takes a decimation of 2 .. 32 and 1 .. 65535 centre frequencies.\n");
+		return 1;
+	}
+	WavStream w;
+	if (!wav_open(input_name, w)) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
+		return 1;
+	}
+	if (w.channels != 2) {
+		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
+		return 1;
+	}
+	if (w.rate % decim || !supported(2, w.rate / decim)) {
+		if (w.rate % decim)
+			std::fprintf(stderr, "Unsupported sample rate.\n");
+		return 1;
+	}
+	ofdmrx_handle *h = create(w.rate / decim);
+	if (!h)
+		return 1;
+	const size_t S = centres.size(), cap = 64;
+	(void)mkdir(outroot.c_str(), 0777);
+	std::vector<std::string> dirs(S), prefixes(S);
+	for (size_t i = 0; i < S; ++i) {
+		dirs[i] = outroot + "/" + std::to_string(i);
+		prefixes[i] = std::to_string(i) + ":";
+		(void)mkdir(dirs[i].c_str(), 0777);
+	}
+	int r = ofdmrx_bank_begin_wideband(h, S, centres.data(), decim, w.fmt);
+	std::vector<uint8_t> out(cap * OFDMRX_PAYLOAD_BYTES), pcm;
+	std::vector<ofdmrx_frame_result> res(cap);
+	std::vector<int32_t> chan(cap);
+	std::vector<int64_t> index(cap);
+	bool written = true;
+	auto step = [&](bool end, const void *samples, size_t n) -> int {
+		size_t n_rec = 0, n_left = 0;
+		do {
+			const int rr = end ? ofdmrx_bank_end(h, cap, out.data(), res.data(), chan.data(), index.data(), &n_rec, &n_left)
+				: ofdmrx_bank_push_wideband(h, samples, n, 0, cap, out.data(), res.data(), chan.data(), index.data(), &n_rec, &n_left);
+			if (rr)
+				return rr;
+			samples = nullptr;
+			n = 0;
+			for (size_t i = 0; i < n_rec && written; ++i)
+				written = emit_record(dirs[(size_t)chan[i]], (size_t)index[i], res[i], out.data() + i * OFDMRX_PAYLOAD_BYTES, prefixes[(size_t)chan[i]].c_str());
+		} while (n_left && written);
+		return 0;
+	};
+	for (bool last = false; !r && written && !last;) {
+		const size_t n = wav_read_block(w, (size_t)w.rate, pcm);      // one wideband second; fewer at the end of the body
+		last = n < (size_t)w.rate;
+		if (n)
+			r = step(false, pcm.data(), n);
+	}
+	if (!r && written)
+		r = step(true, nullptr, 0);
+	if (r)
+		std::fprintf(stderr, "ofdmrx_bank: %s\n", ofdmrx_strerror(r));
+	ofdmrx_destroy(h);
+	if (w.f)
+		std::fclose(w.f);
+	return (r || !written) ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc == 6 && !std::strcmp(argv[1], "--wideband"))
+		return run_wideband(std::atoi(argv[2]), argv[3], argv[4], argv[5]);
 	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
 		return run_live_batch(argv[3], argc - 4, argv + 4);
 	if (argc >= 4 && !std::strcmp(argv[1], "--batch"))
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n", argv[0], argv[0]);
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM F1,F2,... OUTROOT INPUT\n",
+			argv[0], argv[0], argv[0]);
 		return 1;
 	}
 	const std::string outdir = argv[live ? 2 : 1];

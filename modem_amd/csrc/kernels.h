@@ -335,4 +335,28 @@ long front_end_stretch();
 void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
 void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z);
 
+// ---- the wideband front end (k_channelize.hip): mix-down, FIR and decimation of one wideband capture into
+// n_channels channel rows.  in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); every position outside
+// reads as zero and is never loaded.  Output n of channel c (n = out_first .. out_first + n_out - 1) goes to
+// out + 2 (c out_stride + n - out_first) floats, or - dst != nullptr - to the address dst[c] + 8 (n - out_first) (the bank: every
+// channel's place in its window).  taps: the 24 decim + 1 fp32 taps of channelize_taps; inc: the channels' phase increments.
+struct ChannelizeArgs {
+	const void *in;
+	int fmt;                       // OFDMRX_FMT_*
+	int decim;                     // 2 .. 32
+	long long in_first, n_in;
+	const float *taps;             // device
+	const unsigned *inc;           // device, [n_channels]
+	int n_channels;
+	long long out_first, n_out;    // n_out <= channelize_max_outputs()
+	float *out;
+	long long out_stride;          // I/Q pairs per channel row
+	const long long *dst;          // device, [n_channels] addresses, nullable
+};
+void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
+long long channelize_max_outputs();
+// host: the taps of decimation D (T = 24 D + 1 of them; returns T) and the phase increment of a centre frequency at wideband rate rw
+int channelize_taps(int decim, float *taps);
+unsigned channelize_inc(double centre_hz, double rw);
+
 }  // namespace rx

@@ -31,7 +31,8 @@ EXPORTS = [
     "ofdmrx_feed_begin", "ofdmrx_feed_push", "ofdmrx_feed_end", "ofdmrx_feed_lag", "ofdmrx_feed_resident_samples",
     "ofdmrx_decode_streams", "ofdmrx_decode_streams_device", "ofdmrx_debug_streams_edges",
     "ofdmrx_bank_begin", "ofdmrx_bank_push", "ofdmrx_bank_end", "ofdmrx_bank_resident_samples", "ofdmrx_bank_preambles",
-    "ofdmrx_bank_last_stage_ops", "ofdmrx_util_fading",
+    "ofdmrx_bank_last_stage_ops", "ofdmrx_util_fading", "ofdmrx_util_channelize_taps", "ofdmrx_util_channelize",
+    "ofdmrx_bank_begin_wideband", "ofdmrx_bank_push_wideband",
 ]
 
 
@@ -87,6 +88,16 @@ def watterson(preset, sample_rate):
         raise ValueError("watterson: preset must be one of %s" % ", ".join(WATTERSON))
     g = complex(0.5 ** 0.5, 0.0)
     return [(0, g, spread), (int(round(ms * sample_rate / 1000.0)), g, spread)]
+
+
+def channelize_taps(decim):
+    """the 24 decim + 1 fp32 taps of the wideband front end's low pass for decimation decim (2 .. 32): DESIGN.md section 4.14"""
+    decim = int(decim)
+    taps = np.zeros(24 * max(decim, 0) + 1, np.float32)
+    n = load_library().ofdmrx_util_channelize_taps(decim, _ptr(taps))
+    if n != taps.size:
+        raise OfdmRxError("channelize_taps: decim must be 2 .. 32")
+    return taps
 
 
 class Timing(C.Structure):
@@ -160,6 +171,9 @@ def load_library():
                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ofdmrx_bank_end.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
                                   C.POINTER(C.c_size_t)]
+    L.ofdmrx_bank_begin_wideband.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
+    L.ofdmrx_bank_push_wideband.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     for f in (L.ofdmrx_bank_resident_samples, L.ofdmrx_bank_preambles):
         f.argtypes = [C.c_void_p, C.c_size_t]
         f.restype = C.c_longlong
@@ -192,6 +206,9 @@ def load_library():
     L.ofdmrx_util_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(Channel)]
     L.ofdmrx_util_fading.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(Fading),
                                      C.c_uint64, C.c_uint64]
+    L.ofdmrx_util_channelize_taps.argtypes = [C.c_int, C.c_void_p]
+    L.ofdmrx_util_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_tx_frame_samples.restype = C.c_long
     L.ofdmrx_tx_frame_samples.argtypes = [C.c_int]
     L.ofdmrx_frame_samples.restype = C.c_long
@@ -327,6 +344,11 @@ class Receiver:
     def bank(self, n_channels, channels, dtype=np.int16, esn0_rows=False):
         """open a bank of n_channels live channels of `channels` interleaved values of dtype: push one block per channel per call"""
         return Bank(self, n_channels, channels, dtype, esn0_rows)
+
+    def wideband_bank(self, centres_hz, decim, dtype=np.int16, esn0_rows=False):
+        """open a bank whose channels are cut from one wideband I/Q capture (decim x the handle's rate, interleaved I/Q of dtype) at
+        the centre frequencies centres_hz: push the capture block by block"""
+        return WidebandBank(self, centres_hz, decim, dtype, esn0_rows)
 
     def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
         """device pointers (ints), or pinned host outputs; -> n_preambles (the call synchronises once, after the scan)"""
@@ -545,6 +567,14 @@ class Receiver:
             fd.delays[i], fd.gains_re[i], fd.gains_im[i], fd.spread_hz[i] = int(d), float(complex(g).real), float(complex(g).imag), float(s)
         self._check(self._lib.ofdmrx_util_fading(self._h, d_in, n_in, d_out, n_out, spf, C.byref(fd), seed, first_frame))
 
+    def channelize(self, d_in, fmt, in_first, n_in, decim, centres_hz, out_first, n_out, d_out, out_stride=None):
+        """the wideband front end on device buffers (ints): d_in holds the wideband positions in_first .. in_first + n_in - 1 of an
+        interleaved I/Q capture at decim x the handle's rate; output n (out_first .. out_first + n_out - 1) of the channel centred at
+        centres_hz[c] goes to d_out + 8 (c out_stride + n - out_first) as fp32 I/Q; asynchronous on the handle's stream"""
+        f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
+        self._check(self._lib.ofdmrx_util_channelize(self._h, d_in, fmt, in_first, n_in, decim, _ptr(f), f.size, out_first, n_out, d_out,
+                                                     n_out if out_stride is None else out_stride))
+
     def tx_frame_samples(self, mode=6):
         return int(self._lib.ofdmrx_frame_samples(self.sample_rate, mode))
 
@@ -738,3 +768,27 @@ class Bank:
         while self.open:
             self.end()
         return False
+
+
+class WidebandBank(Bank):
+    """A bank fed one wideband capture (ofdmrx_bank_begin_wideband / ofdmrx_bank_push_wideband): push(block) takes the next wideband
+    sample frames [k, 2] and returns what Bank.push returns - the records that have become due on any channel.  The records of channel
+    c are what Receiver.decode_stream returns for row c of Receiver.channelize over the whole capture, however it is cut."""
+
+    def __init__(self, rx, centres_hz, decim, dtype=np.int16, esn0_rows=False):
+        self._rx, self._lib, self._h = rx, rx._lib, rx._h
+        f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
+        self.centres_hz, self.decim = f, int(decim)
+        self.n_channels, self.channels, self.dtype, self._rows = f.size, 2, np.dtype(dtype), bool(esn0_rows)
+        rx._check(self._lib.ofdmrx_bank_begin_wideband(self._h, f.size, _ptr(f), self.decim, rx._fmt(self.dtype)))
+        self.open = True
+        self.n_left = 0
+        self._ops = 0
+
+    def push(self, block, end=False, max_records=None):
+        """more wideband samples [k, 2] (k may be 0); end: every channel's stream is over after them -> (payloads, results,
+        record_channel, record_index[, esn0 rows])"""
+        pcm = np.ascontiguousarray(block, dtype=self.dtype).reshape(-1, 2)
+        n = pcm.shape[0]
+        return self._call(lambda first, cap, o, r, ch, ix, a, b: self._lib.ofdmrx_bank_push_wideband(
+            self._h, _ptr(pcm) if n and first else None, n if first else 0, 1 if end and first else 0, cap, o, r, ch, ix, a, b), max_records)

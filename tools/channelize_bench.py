@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Time the wideband front end (ofdmrx_util_channelize, k_channelize.hip) on a resident capture.
+
+For 1, 16 and 256 channels at D = 6 and D = 24, with hipEvents on the handle's stream, median of `--reps` after `--warmup`:
+  ms, input + output GB/s, complex multiply-adds per second,
+  beside k_awgn_tile on a buffer of the same bytes (the comparison DESIGN.md 4.13 used) and beside the arithmetic floor
+  N n_out T 4 FMAs at DESIGN.md section 6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs), and which of the two is nearer.
+Then one wideband-bank push of one second x 64 channels against ofdmrx_util_channelize + copy to host + ofdmrx_bank_push of the same
+data (host wall time: these calls block).
+The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+FMA_NS, SIMDS = 0.86, 1024
+
+
+def child(args):
+    import numpy as np
+    import torch
+    import modem_amd
+    import modem_amd.ofdmrx as M
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    W = args.samples
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    d_in = torch.randint(-20000, 20000, (W, 2), dtype=torch.int16, device=dev, generator=gen)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    rows = []
+    for D in (6, 24):
+        T = 24 * D + 1
+        n_out = -(-W // D)
+        for N in (1, 16, 256):
+            f = np.linspace(-0.45, 0.45, N) * D * 8000.0 + 0.123
+            d_out = torch.empty((N, n_out, 2), dtype=torch.float32, device=dev)
+            ms = timed(lambda k: rx.channelize(d_in.data_ptr(), 0, 0, W, D, f, 0, n_out, d_out.data_ptr()))
+            nbytes = W * 4 + N * n_out * 8
+            spf = 4096
+            frames = max(1, nbytes // (2 * spf * 4))
+            d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+            d_b = torch.empty_like(d_a)
+            awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+            floor = N * n_out * T * 4 / 64.0 * FMA_NS * 1e-6 / SIMDS
+            rows.append(dict(decim=D, channels=N, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1), gmac_per_s=round(N * n_out * T / ms / 1e6, 1),
+                             awgn_tile_ms=round(awgn, 4), fma_floor_ms=round(floor, 4), nearer="arithmetic" if floor > awgn else "memory",
+                             over_bound=round(ms / max(floor, awgn), 2)))
+            del d_out, d_a, d_b
+    rx.close()
+
+    # one second x 64 channels through the wideband bank, and through channelize + copy + a plain bank
+    D, N, sec = 6, 64, 48000
+    f = np.linspace(-0.45, 0.45, N) * D * 8000.0 + 0.123
+    rng = np.random.default_rng(2)
+    cap = rng.integers(-300, 300, size=((args.warmup + args.reps) * sec, 2)).astype(np.int16)
+    outs = (np.zeros((64, 5380), np.uint8), np.zeros(64, M.RESULT_DTYPE), np.zeros(64, np.int32), np.zeros(64, np.int64))
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    p = M._ptr
+    rxw = modem_amd.Receiver(device=0)
+    L, h = rxw._lib, rxw._h
+    assert L.ofdmrx_bank_begin_wideband(h, N, p(f), D, 0) == 0
+    wide = []
+    for k in range(args.warmup + args.reps):
+        blk = np.ascontiguousarray(cap[k * sec:(k + 1) * sec])
+        t = time.perf_counter()
+        assert L.ofdmrx_bank_push_wideband(h, p(blk), sec, 0, 64, p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), C.byref(a), C.byref(b)) == 0
+        wide.append((time.perf_counter() - t) * 1e3)
+    wide_ops = int(L.ofdmrx_bank_last_stage_ops(h))
+    rxw.close()
+    rxc, rxb = modem_amd.Receiver(device=0), modem_amd.Receiver(device=0)
+    d_cap = torch.from_numpy(cap).to(dev)
+    n_blk = sec // D
+    d_rows = torch.empty((N, n_blk, 2), dtype=torch.float32, device=dev)
+    host = torch.empty((N, n_blk, 2), dtype=torch.float32).pin_memory()
+    torch.cuda.synchronize()
+    assert rxb._lib.ofdmrx_bank_begin(rxb._h, N, 2, 2) == 0
+    lens = np.full(N, n_blk, np.uintp)
+    plain = []
+    for k in range(args.warmup + args.reps):
+        i0 = max(0, k * sec - 24 * D)
+        t = time.perf_counter()
+        rxc.channelize(d_cap.data_ptr() + 4 * i0, 0, i0, (k + 1) * sec - i0, D, f, k * n_blk, n_blk, d_rows.data_ptr())
+        rxc.synchronize()
+        host.copy_(d_rows)
+        assert rxb._lib.ofdmrx_bank_push(rxb._h, host.data_ptr(), n_blk * 8, p(lens), None, 64, p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]),
+                                         C.byref(a), C.byref(b)) == 0
+        plain.append((time.perf_counter() - t) * 1e3)
+    plain_ops = int(rxb._lib.ofdmrx_bank_last_stage_ops(rxb._h))
+    rxc.close()
+    rxb.close()
+    w = args.warmup
+    bank = dict(channels=N, decim=D, wideband_push_ms=round(statistics.median(wide[w:]), 3), wideband_stage_ops=wide_ops,
+                channelize_copy_push_ms=round(statistics.median(plain[w:]), 3), plain_stage_ops=plain_ops)
+    print("decim channels      ms    GB/s  GMAC/s  awgn_tile ms  FMA floor ms  nearer bound  time / bound")
+    for r in rows:
+        print("%5d %8d %7.4f %7.1f %7.1f %13.4f %13.4f  %-12s %6.2f" % (r["decim"], r["channels"], r["ms"], r["gb_per_s"], r["gmac_per_s"],
+                                                                      r["awgn_tile_ms"], r["fma_floor_ms"], r["nearer"], r["over_bound"]))
+    print("one wideband second x %d channels: wideband bank push %.3f ms (%d stage ops); channelize + copy + plain bank push %.3f ms (%d stage ops)"
+          % (N, bank["wideband_push_ms"], wide_ops, bank["channelize_copy_push_ms"], plain_ops))
+    print(json.dumps({"tool": "channelize_bench", "samples": W, "rows": rows, "bank": bank}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds the GPU step may take")
+    ap.add_argument("--child", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    try:
+        return subprocess.run(cmd, timeout=args.timeout).returncode
+    except subprocess.TimeoutExpired:
+        print("channelize_bench: the GPU step ran into its time limit of %d s" % args.timeout, file=sys.stderr)
+        return 124
+
+
+if __name__ == "__main__":
+    sys.exit(main())
