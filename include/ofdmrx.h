@@ -58,7 +58,7 @@ extern "C" {
  *      carriers round Nyquist);
  *      added within 1.9 (the minor number stays: a caller detects it by symbol): the Watterson fading channel - ofdmrx_util_fading;
  *      the wideband front end - ofdmrx_util_channelize_taps, ofdmrx_util_channelize, ofdmrx_bank_begin_wideband,
- *      ofdmrx_bank_push_wideband */
+ *      ofdmrx_bank_push_wideband; the wideband synthesizer - ofdmrx_util_synthesize */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -585,6 +585,37 @@ int ofdmrx_util_fading(ofdmrx_handle *h, const int16_t *d_in, size_t n_in,
 int ofdmrx_util_channelize_taps(int decim, float *taps);
 int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
+
+/* Wideband synthesizer (added within revision 1.9, detected by symbol), the mirror image of the wideband front end: n_channels
+ * narrowband transmissions at the handle's rate - what the device transmitter and the channel kernels leave - are each placed at a
+ * centre frequency, a start time and a gain and summed into ONE wideband I/Q capture at interp x the handle's rate.  DESIGN.md
+ * section 4.15 is the definition, held component by component to a float64 model.  With D = interp, Rw = D rate, K = 12 D, T = 24 D
+ * + 1 and h[k] the fp32 taps ofdmrx_util_channelize_taps(D, .) writes - there is no new filter:
+ *   input   x_c[j], j = 0 .. n_in - 1: sample frame c in_stride + j of d_in, interleaved I/Q of in_format (S16 or F32, scaled as the
+ *           decoder scales its input); zero outside
+ *   phase   inc_c = (uint32) llrint(centre_hz[c] 2^32 / Rw); the phase at ABSOLUTE wideband index m is (inc_c m) mod 2^32 - the
+ *           expression of the front end, so a channel synthesized and channelized at one centre has no residual frequency at all
+ *   gain    G_c = D gain[c], formed in double, rounded once to fp32 (the D restores what zero-stuffing removes)
+ *   output  w[m] = sum_c G_c e^{+2 pi i phase_c(m) / 2^32} sum_j h[m - start[c] - j D] x_c[j], over the j with 0 <= m - start[c] -
+ *           j D <= T - 1; start[c] >= 0 in wideband samples, need not be a multiple of D.  F32 output: (re, im) of w[m], no clip, a zero always +0.
+ *           S16 output: the F32 output through the channel kernels' quantiser, nearbyintf(32767 clamp(v, -1, 1)): never -32768.
+ * Every output is a closed form of absolute indices: there is no state, and a capture made window by window has the bytes of one
+ * made in one call.  Sample j of channel c sits at wideband time start[c] + j D + K; through ofdmrx_util_channelize at the same
+ * centre and D it comes out at index j + 24 + start[c] / D - exactly where D divides start[c], by a fractional delay otherwise.
+ * The filter is flat to rate / 4 and down by 75 dB from rate / 2 on: make a 2-channel transmission for it with freq_off = 0 (its
+ * band is at most +-1600 Hz at 8 kHz).  One at the default +2000 Hz reaches into the transition band and comes out attenuated; it
+ * is not refused.
+ * DEVICE buffers d_in and d_out, HOST arrays centre_hz, start and gain; asynchronous on the handle's stream.  Calls with other
+ * parameter arrays than the call before take the next of a small ring of parameter sets and wait only for the launch that used
+ * that set four changes ago.  Output m (out_first .. out_first + n_out - 1) lands m - out_first sample frames into d_out.
+ * OFDMRX_E_ARG, before any device call and with the output untouched: NULL pointers or zero counts; n_channels outside 1..65535;
+ * interp outside 2..32; an in_format or out_format other than S16 or F32; in_stride < n_in; a negative out_first or start; a centre
+ * that is not finite or lies outside +- Rw / 2; a gain that is not finite (or so large that D gain is not); positions or counts
+ * above 2^50 (n_out above 2^41 - 1024, which the launch cannot hold; in_stride above 2^34); d_out overlapping d_in; d_in or d_out
+ * off its sample-frame boundary; a handle with an open feed or bank. */
+int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
+	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out,
+	void *d_out, int out_format);
 
 /* ---- N2: the transmitter on the device (replaces Encoder<value,cmplx,rate>(pcm, inp, count=1, freq_off,
  * call_sign, oper_mode), encode.cc:271,424-436, for batches; rate = the handle's sample_rate).  d_payload:

@@ -231,6 +231,19 @@ struct ofdmrx_handle {
 	int chz_decim = 0;
 	std::vector<float> chz_taps_h;
 	std::vector<unsigned> chz_inc_h;
+	// the wideband synthesizer (api_synthesize.cpp): a small ring of parameter sets - the channels' (start, inc, gain) and the taps
+	// behind them - so that a call with other parameters never writes what a launch still in flight reads: a slot is written again
+	// only after the event of its last launch
+	struct SynSlot {
+		DevBuf dev;
+		std::vector<SynthChannel> ch;   // (the host copy the upload reads: it lives as long as the slot)
+		std::vector<float> taps;
+		int interp = 0;
+		hipEvent_t done = nullptr;
+		~SynSlot() { if (done) (void)hipEventDestroy(done); }
+	};
+	SynSlot syn[4];
+	int syn_cur = 0;
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \

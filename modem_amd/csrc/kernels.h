@@ -359,4 +359,27 @@ long long channelize_max_outputs();
 int channelize_taps(int decim, float *taps);
 unsigned channelize_inc(double centre_hz, double rw);
 
+// ---- the wideband synthesizer (k_synthesize.hip): n_channels narrowband rows -> one wideband capture.  in: sample
+// frame j (0 .. n_in - 1) of channel c at c in_stride + j sample frames (interleaved I/Q of in_fmt: S16 or F32); every index outside
+// reads as zero and is never loaded.  Output m (out_first .. out_first + n_out - 1) goes m - out_first sample frames into out, as
+// out_fmt (S16 or F32).  taps: the 24 interp + 1 fp32 taps of channelize_taps.
+struct SynthChannel {
+	long long start;               // wideband index of the channel's first input sample, >= 0
+	unsigned inc;                  // channelize_inc of its centre
+	float gain;                    // interp x the caller's gain, rounded once
+};
+struct SynthesizeArgs {
+	const void *in;
+	int in_fmt, out_fmt;           // OFDMRX_FMT_S16 or OFDMRX_FMT_F32
+	int interp;                    // 2 .. 32
+	long long in_stride, n_in;     // sample frames
+	const SynthChannel *ch;        // device, [n_channels]
+	const float *taps;             // device
+	int n_channels;
+	long long out_first, n_out;    // n_out <= synthesize_max_outputs()
+	void *out;
+};
+void launch_synthesize(hipStream_t s, const SynthesizeArgs &a);
+long long synthesize_max_outputs();
+
 }  // namespace rx

@@ -1,0 +1,147 @@
+// synthesize_main.cpp -- `synthesize OUT.wav INTERP CENTRE_HZ:START:GAIN_DB:IN.wav [...]`: mixes narrowband recordings into one
+// wideband I/Q capture (ofdmrx_util_synthesize).  Every IN.wav is an analytic signal (2 channels) of 8 or 16
+// bits at one common supported rate; it is placed at CENTRE_HZ, START wideband samples into the capture, at GAIN_DB.  OUT.wav has 2
+// channels of 16 bits at INTERP x that rate and is as long as the last channel's support: what `decode_stream --wideband INTERP
+// c1,c2,.. OUTROOT OUT.wav` reads.  Exit status 0, or 1 on argument, WAV or library errors.
+#include "wav_read.h"
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <string>
+
+static void put32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+static void put16(uint8_t *p, uint16_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
+
+int main(int argc, char **argv)
+{
+	if (argc < 4) {
+		std::fprintf(stderr, "usage: %s OUT.wav INTERP CENTRE_HZ:START:GAIN_DB:IN.wav [...]\n", argv[0]);
+		return 1;
+	}
+	const char *output_name = argv[1];
+	const int interp = std::atoi(argv[2]);
+	const size_t C = (size_t)(argc - 3);
+	if (interp < 2 || interp > 32 || C > 65535) {
+		std::fprintf(stderr, "A wideband capture takes an interpolation of 2 .. 32 and 1 .. 65535 channels.\n");
+		return 1;
+	}
+	std::vector<double> centre(C);
+	std::vector<long long> start(C);
+	std::vector<float> gain(C);
+	std::vector<Wav> wavs(C);
+	size_t longest = 0;
+	for (size_t c = 0; c < C; ++c) {
+		const char *p = argv[c + 3];
+		char *e = nullptr;
+		centre[c] = std::strtod(p, &e);
+		bool ok = e != p && *e == ':';
+		if (ok) {
+			p = e + 1;
+			start[c] = std::strtoll(p, &e, 10);
+			ok = e != p && *e == ':' && start[c] >= 0;
+		}
+		double db = 0.0;
+		if (ok) {
+			p = e + 1;
+			db = std::strtod(p, &e);
+			ok = e != p && *e == ':' && e[1] && std::isfinite(db);
+		}
+		if (!ok) {
+			std::fprintf(stderr, "A channel is CENTRE_HZ:START:GAIN_DB:IN.wav, START a count of wideband samples.\n");
+			return 1;
+		}
+		gain[c] = (float)std::pow(10.0, db / 20.0);
+		const char *input_name = e + 1;
+		Wav &w = wavs[c];
+		if (!read_wav(input_name, w) || w.frames == 0) {
+			std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
+			return 1;
+		}
+		if (w.channels != 2 || (w.bits != 8 && w.bits != 16)) {
+			std::fprintf(stderr, "A channel is an analytic signal (two channels) of 8 or 16 bits.\n");
+			return 1;
+		}
+		if (w.rate != wavs[0].rate) {
+			std::fprintf(stderr, "The channels do not share one sample rate.\n");
+			return 1;
+		}
+		longest = std::max(longest, w.frames);
+	}
+	const int rate = wavs[0].rate;
+	if (rate != 8000 && rate != 16000 && rate != 44100 && rate != 48000) {
+		std::fprintf(stderr, "Unsupported sample rate.\n");
+		return 1;
+	}
+	if (ofdmrx_abi_version() != OFDMRX_ABI_VERSION || ofdmrx_abi_minor() < 9) {
+		std::fprintf(stderr, "libofdmrx: ABI %d.%d, this program needs %d.9\n", ofdmrx_abi_version(), ofdmrx_abi_minor(), OFDMRX_ABI_VERSION);
+		return 1;
+	}
+	// every row as fp32 I/Q, scaled as the decoder scales its input; the rows share the longest length, zeros behind a shorter one
+	const long long T = 24LL * interp + 1;
+	long long n_out = 0;
+	std::vector<float> rows(C * longest * 2, 0.f);
+	for (size_t c = 0; c < C; ++c) {
+		const Wav &w = wavs[c];
+		float *d = rows.data() + c * longest * 2;
+		for (size_t i = 0; i < 2 * w.frames; ++i)
+			d[i] = w.bits == 16 ? (float)((const int16_t *)w.pcm.data())[i] / 32767.f : (float)((int)w.pcm[i] - 128) / 127.f;
+		n_out = std::max(n_out, start[c] + ((long long)w.frames - 1) * interp + T);
+		wavs[c].pcm = std::vector<uint8_t>();
+	}
+	const unsigned long long bytes = (unsigned long long)n_out * 4;
+	if (bytes > 0xffffffffull - 36) {
+		std::fprintf(stderr, "The capture does not fit a WAV file.\n");
+		return 1;
+	}
+	ofdmrx_config cfg{};
+	cfg.abi_version = OFDMRX_ABI_VERSION;
+	cfg.sample_rate = rate;
+	cfg.list_size = 8;
+	cfg.chunk_frames = 1;
+	cfg.descramble = 1;
+	ofdmrx_handle *h = nullptr;
+	int r = ofdmrx_create(&cfg, &h);
+	if (r) {
+		std::fprintf(stderr, "ofdmrx_create: %s\n", ofdmrx_strerror(r));
+		return 1;
+	}
+	std::vector<int16_t> pcm((size_t)n_out * 2);
+	void *d_in = nullptr, *d_out = nullptr;
+	hipError_t e = hipMalloc(&d_in, rows.size() * sizeof(float));
+	e = e == hipSuccess ? hipMalloc(&d_out, (size_t)bytes) : e;
+	e = e == hipSuccess ? hipMemcpy(d_in, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice) : e;
+	if (e == hipSuccess) {
+		r = ofdmrx_util_synthesize(h, d_in, OFDMRX_FMT_F32, longest, longest, interp, centre.data(), start.data(), gain.data(), C, 0, (size_t)n_out,
+			d_out, OFDMRX_FMT_S16);
+		r = r ? r : ofdmrx_synchronize(h);
+		if (r)
+			std::fprintf(stderr, "ofdmrx_util_synthesize: %s\n", ofdmrx_strerror(r));
+		else
+			e = hipMemcpy(pcm.data(), d_out, (size_t)bytes, hipMemcpyDeviceToHost);
+	}
+	if (e != hipSuccess)
+		std::fprintf(stderr, "synthesize: %s\n", hipGetErrorString(e));
+	(void)hipFree(d_in);
+	(void)hipFree(d_out);
+	ofdmrx_destroy(h);
+	if (r || e != hipSuccess)
+		return 1;
+	FILE *o = std::fopen(output_name, "wb");
+	if (!o) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for writing.\n", output_name);
+		return 1;
+	}
+	uint8_t hd[44];
+	const uint32_t wide = (uint32_t)rate * (uint32_t)interp;
+	std::memcpy(hd, "RIFF", 4); put32(hd + 4, (uint32_t)(36 + bytes)); std::memcpy(hd + 8, "WAVEfmt ", 8);
+	put32(hd + 16, 16); put16(hd + 20, 1); put16(hd + 22, 2); put32(hd + 24, wide);
+	put32(hd + 28, wide * 4); put16(hd + 32, 4); put16(hd + 34, 16);
+	std::memcpy(hd + 36, "data", 4); put32(hd + 40, (uint32_t)bytes);
+	const bool wrote = std::fwrite(hd, 1, 44, o) == 44 && std::fwrite(pcm.data(), 1, (size_t)bytes, o) == (size_t)bytes;
+	if (std::fclose(o) || !wrote) {
+		std::fprintf(stderr, "Couldn't write file \"%s\".\n", output_name);
+		return 1;
+	}
+	return 0;
+}

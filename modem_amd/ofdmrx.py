@@ -32,7 +32,7 @@ EXPORTS = [
     "ofdmrx_decode_streams", "ofdmrx_decode_streams_device", "ofdmrx_debug_streams_edges",
     "ofdmrx_bank_begin", "ofdmrx_bank_push", "ofdmrx_bank_end", "ofdmrx_bank_resident_samples", "ofdmrx_bank_preambles",
     "ofdmrx_bank_last_stage_ops", "ofdmrx_util_fading", "ofdmrx_util_channelize_taps", "ofdmrx_util_channelize",
-    "ofdmrx_bank_begin_wideband", "ofdmrx_bank_push_wideband",
+    "ofdmrx_bank_begin_wideband", "ofdmrx_bank_push_wideband", "ofdmrx_util_synthesize",
 ]
 
 
@@ -209,6 +209,8 @@ def load_library():
     L.ofdmrx_util_channelize_taps.argtypes = [C.c_int, C.c_void_p]
     L.ofdmrx_util_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.ofdmrx_util_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
     L.ofdmrx_tx_frame_samples.restype = C.c_long
     L.ofdmrx_tx_frame_samples.argtypes = [C.c_int]
     L.ofdmrx_frame_samples.restype = C.c_long
@@ -574,6 +576,19 @@ class Receiver:
         f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
         self._check(self._lib.ofdmrx_util_channelize(self._h, d_in, fmt, in_first, n_in, decim, _ptr(f), f.size, out_first, n_out, d_out,
                                                      n_out if out_stride is None else out_stride))
+
+    def synthesize(self, d_in, in_fmt, n_in, interp, centres_hz, starts, gains, out_first, n_out, d_out, out_fmt, in_stride=None):
+        """the wideband synthesizer on device buffers (ints): channel c's n_in sample frames (interleaved I/Q of in_fmt, S16 or F32) lie
+        at d_in + c in_stride sample frames; it is placed at centres_hz[c], starts[c] wideband samples in, at gains[c], and the sum's
+        positions out_first .. out_first + n_out - 1 at interp x the handle's rate go to d_out as out_fmt (S16 or F32); asynchronous on
+        the handle's stream"""
+        f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
+        s = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        if not (f.size == s.size == g.size):
+            raise OfdmRxError("synthesize: centres_hz, starts and gains must have one length")
+        self._check(self._lib.ofdmrx_util_synthesize(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, interp, _ptr(f), _ptr(s),
+                                                     _ptr(g), f.size, out_first, n_out, d_out, out_fmt))
 
     def tx_frame_samples(self, mode=6):
         return int(self._lib.ofdmrx_frame_samples(self.sample_rate, mode))

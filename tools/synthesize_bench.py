@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Time the wideband synthesizer (ofdmrx_util_synthesize, k_synthesize.hip) on resident rows.
+
+At D = 6 and D = 24, with hipEvents on the handle's stream, median of `--reps` after `--warmup`:
+  1, 16 and 256 channels that overlap fully (every channel meets every tile), each of `--samples` / D sample frames, and
+  256 channels laid end to end (the Monte-Carlo case: every tile meets one or two channels and skips the rest), each of
+  `--samples` / (16 D) sample frames;
+  ms, input + output GB/s, real multiply-adds of the tap sums per second,
+  beside k_awgn_tile on a buffer of the output's bytes and beside the arithmetic floor C_met n_out 25 x 2 FMAs at DESIGN.md section
+  6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs) - C_met the channels a tile meets - and which of the two is nearer.
+The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+FMA_NS, SIMDS = 0.86, 1024
+
+
+def child(args):
+    import numpy as np
+    import torch
+    import modem_amd
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    rows = []
+    for D in (6, 24):
+        for N, layout in ((1, "overlapping"), (16, "overlapping"), (256, "overlapping"), (256, "end to end")):
+            n_in = args.samples // D if layout == "overlapping" else args.samples // (16 * D)
+            reach = (n_in - 1) * D + 24 * D + 1
+            step = 0 if layout == "overlapping" else reach
+            starts = np.arange(N, dtype=np.int64) * step + np.arange(N) % D
+            n_out = int(starts[-1]) + reach
+            f = np.linspace(-0.45, 0.45, N) * D * 8000.0 + 0.123
+            g = np.full(N, 0.5 / (N if layout == "overlapping" else 1), np.float32)
+            d_in = torch.randint(-20000, 20000, (N, n_in, 2), dtype=torch.int16, device=dev, generator=gen)
+            d_out = torch.empty((n_out, 2), dtype=torch.int16, device=dev)
+            ms = timed(lambda k: rx.synthesize(d_in.data_ptr(), 0, n_in, D, f, starts, g, 0, n_out, d_out.data_ptr(), 0))
+            spf = 4096
+            frames = max(1, n_out // spf)
+            d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+            d_b = torch.empty_like(d_a)
+            awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+            met = N if layout == "overlapping" else 1
+            floor = met * n_out * 25 * 2 / 64.0 * FMA_NS * 1e-6 / SIMDS
+            nbytes = N * n_in * 4 + n_out * 4
+            rows.append(dict(interp=D, channels=N, layout=layout, n_out=n_out, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1),
+                             gmac_per_s=round(met * n_out * 50 / ms / 1e6, 1), awgn_tile_ms=round(awgn, 4), fma_floor_ms=round(floor, 4),
+                             nearer="arithmetic" if floor > awgn else "memory", over_bound=round(ms / max(floor, awgn), 2)))
+            del d_in, d_out, d_a, d_b
+    rx.close()
+    print("interp channels layout        n_out      ms    GB/s  GMAC/s  awgn_tile ms  FMA floor ms  nearer bound  time / bound")
+    for r in rows:
+        print("%6d %8d %-12s %8d %8.4f %7.1f %7.1f %13.4f %13.4f  %-12s %6.2f" % (
+            r["interp"], r["channels"], r["layout"], r["n_out"], r["ms"], r["gb_per_s"], r["gmac_per_s"], r["awgn_tile_ms"], r["fma_floor_ms"],
+            r["nearer"], r["over_bound"]))
+    print(json.dumps({"tool": "synthesize_bench", "samples": args.samples, "rows": rows}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=1 << 20, help="wideband samples an overlapping channel spans")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds the GPU step may take")
+    ap.add_argument("--child", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    try:
+        return subprocess.run(cmd, timeout=args.timeout).returncode
+    except subprocess.TimeoutExpired:
+        print("synthesize_bench: the GPU step ran into its time limit of %d s" % args.timeout, file=sys.stderr)
+        return 124
+
+
+if __name__ == "__main__":
+    sys.exit(main())
