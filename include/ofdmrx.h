@@ -58,7 +58,8 @@ extern "C" {
  *      carriers round Nyquist);
  *      added within 1.9 (the minor number stays: a caller detects it by symbol): the Watterson fading channel - ofdmrx_util_fading;
  *      the wideband front end - ofdmrx_util_channelize_taps, ofdmrx_util_channelize, ofdmrx_bank_begin_wideband,
- *      ofdmrx_bank_push_wideband; the wideband synthesizer - ofdmrx_util_synthesize */
+ *      ofdmrx_bank_push_wideband; the wideband synthesizer - ofdmrx_util_synthesize; the wideband survey - ofdmrx_util_survey_window,
+ *      ofdmrx_util_survey, ofdmrx_util_find_bands */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -616,6 +617,47 @@ int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format
 int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
 	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out,
 	void *d_out, int out_format);
+
+/* Wideband survey (added within revision 1.9, detected by symbol): which bands of a wideband capture are occupied - the centres to
+ * open the front end or a wideband bank on.  DESIGN.md section 4.16 is the definition, held bin by bin to a float64 model.
+ * ofdmrx_util_survey: an averaged (Welch) power spectrum, one row or a waterfall of rows.  With N = nfft (1280, 2560 or 5120),
+ * H = N / 2, S = segs_per_row (1 .. 65536) and Rw the capture's rate:
+ *   window  periodic Hann w[n] = 0.5 - 0.5 cos(2 pi n / N), computed in double, rounded once to fp32; U = sum w[n]^2 over the fp32 values
+ *   segment s >= 0 covers the wideband positions s H .. s H + N - 1;  X_s[b] = sum_n w[n] x[s H + n] e^{-2 pi i b n / N}
+ *   row r   P[r][i] = (1 / (S U)) sum_{s = r S .. r S + S - 1} |X_s[(i + N / 2) mod N]|^2,  i = 0 .. N - 1 in ASCENDING frequency:
+ *           index i is the frequency (i - N / 2) Rw / N.  White noise of power sigma^2 per complex sample reads sigma^2 in every bin.
+ * Every output is a closed form of absolute indices: there is no state, and a capture surveyed row by row, each call given only
+ * the samples its rows need, gives the same bytes as one call (the fp32 sums run over groups of 8 consecutive segments counted from
+ * the row's first, then over the groups, both ascending).
+ * ofdmrx_util_survey_window: host only; writes the N window values, returns N; another N or NULL: OFDMRX_E_ARG.
+ * ofdmrx_util_survey: DEVICE buffers, asynchronous on the handle's stream.  d_in holds the wideband positions in_first .. in_first +
+ * n_in - 1 as interleaved I/Q of sample_format (scaled as the decoder scales its input); row r (row_first .. row_first + n_rows - 1)
+ * lands at d_out + (r - row_first) N floats.  OFDMRX_E_ARG, before any device call and with the output untouched: NULL pointers or
+ * zero counts; a bad format; N outside the set; S outside 1..65536; a negative in_first or row_first; a position the rows need that
+ * is not in the buffer - there is no zero padding: row_first S H < in_first, or (row_first + n_rows) S H + H > in_first + n_in; d_in
+ * off the sample-frame boundary, d_out off 4 bytes; d_out overlapping d_in; positions or counts above 2^50; n_rows ceil(S / 8) N
+ * above 2^28 (the partial sums of one call: 1 GiB), which the launch cannot hold; a handle with an open feed or bank.
+ * ofdmrx_util_find_bands: host only, float64; the bands of ONE row psd[0 .. N - 1] of a capture at rate_wide:
+ *   floor     max(median of the N values, abs_floor); the median is the mean of the two middle values.  It is the noise floor only
+ *             while less than half the band is occupied: give abs_floor where that may not hold.
+ *   occupied  bin i with psd[i] > floor 10^(thr_db / 10) and psd[i] > 0
+ *   run       occupied bins separated by at most floor(gap_hz / (rate_wide / N)) unoccupied bins; runs do not wrap round the band edge
+ *   band      a run first .. last of width (last - first + 1) rate_wide / N >= min_width_hz (a DC spike or a carrier is dropped by
+ *             this); centre_hz = ((first + last) / 2 - N / 2) rate_wide / N; power = mean of psd over first .. last; level_db = 10
+ *             log10(power / floor)
+ * Bands come in ascending frequency; *n_bands counts all of them, only the first max_bands are written; *floor_out (nullable) gets
+ * the floor.  OFDMRX_E_ARG: NULL psd, bands or n_bands; N outside the set; rate_wide that is not finite or <= 0; thr_db, gap_hz,
+ * min_width_hz or abs_floor that is not finite or negative. */
+typedef struct ofdmrx_band {
+	double centre_hz, width_hz, power;
+	float level_db;
+	int32_t first_bin, last_bin;
+} ofdmrx_band;
+int ofdmrx_util_survey_window(int nfft, float *w);
+int ofdmrx_util_survey(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int nfft,
+	int segs_per_row, long long row_first, size_t n_rows, float *d_out);
+int ofdmrx_util_find_bands(const float *psd, int nfft, double rate_wide, double thr_db, double gap_hz, double min_width_hz,
+	double abs_floor, size_t max_bands, ofdmrx_band *bands, size_t *n_bands, double *floor_out);
 
 /* ---- N2: the transmitter on the device (replaces Encoder<value,cmplx,rate>(pcm, inp, count=1, freq_off,
  * call_sign, oper_mode), encode.cc:271,424-436, for batches; rate = the handle's sample_rate).  d_payload:

@@ -244,6 +244,16 @@ struct ofdmrx_handle {
 	};
 	SynSlot syn[4];
 	int syn_cur = 0;
+	// the wideband survey (api_survey.cpp): per transform length (1280, 2560, 5120) the window and the roots on the device, uploaded
+	// on the first call with that length and never written again; the partials of the last call (grown on demand)
+	struct SurveyPlan {
+		DevBuf win, tw;
+		std::vector<float> win_h;   // (the host copies the uploads read: they live as long as the handle)
+		std::vector<cf> tw_h;
+		double u = 0.0;             // sum of the squared fp32 window values
+	};
+	SurveyPlan survey[3];
+	DevBuf survey_part;
 };
 
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \

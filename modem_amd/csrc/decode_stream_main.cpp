@@ -14,7 +14,10 @@
 // `decode_stream --wideband DECIM F1,F2,... OUTROOT WIDE.wav`: one wideband I/Q capture (2 channels, DECIM x a supported rate) read
 // in blocks of one wideband second and pushed through a wideband bank (ofdmrx_bank_begin_wideband): channel i, centred at Fi Hz, goes
 // to OUTROOT/<i>/<k>.dat with the `<i>:` summary lines of --live --batch.
-#include "wav_read.h"
+// `decode_stream --wideband DECIM auto OUTROOT WIDE.wav`: the capture is surveyed first (ofdmrx_util_survey over the whole file, 1280
+// bins, and ofdmrx_util_find_bands with its default parameters: what `survey WIDE.wav DECIM` prints), the centres found are printed
+// on stderr, and then exactly the form above runs with that list.  The file is read twice, so `auto` does not take standard input.
+#include "survey_cli.h"
 #include <algorithm>
 #include <cstdlib>
 #include <string>
@@ -276,6 +279,50 @@ static int run_live_batch(const std::string &outroot, int n_inputs, char **input
 	return (r || !written) ? 1 : 0;
 }
 
+// the centres of the occupied bands of a capture, as the list run_wideband takes ("" with a message: none, or an error)
+static std::string survey_centres(int decim, const char *input_name)
+{
+	if (!std::strcmp(input_name, "-") || !std::strcmp(input_name, "/dev/stdin")) {
+		std::fprintf(stderr, "`auto` reads the capture twice: give a file, not standard input.\n");
+		return "";
+	}
+	Wav w;
+	if (!read_wav(input_name, w) || w.frames == 0) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
+		return "";
+	}
+	if (w.channels != 2) {
+		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
+		return "";
+	}
+	if (decim < 2 || decim > 32 || w.rate % decim || !supported(2, w.rate / decim)) {
+		if (decim < 2 || decim > 32 || w.rate % decim)
+			std::fprintf(stderr, "Unsupported sample rate.\n");
+		return "";
+	}
+	ofdmrx_handle *h = create(w.rate / decim);
+	if (!h)
+		return "";
+	std::vector<ofdmrx_band> bands;
+	double floor = 0.0;
+	const bool ok = survey_capture(h, w, 1280, bands, floor);
+	ofdmrx_destroy(h);
+	if (!ok)
+		return "";
+	if (bands.empty()) {
+		std::fprintf(stderr, "The survey found no occupied band (floor %.6g).\n", floor);
+		return "";
+	}
+	std::string list;
+	for (const ofdmrx_band &b : bands) {
+		char t[40];
+		std::snprintf(t, sizeof(t), "%s%.17g", list.empty() ? "" : ",", b.centre_hz);
+		list += t;
+	}
+	std::fprintf(stderr, "survey: floor %.6g, centres %s\n", floor, list.c_str());
+	return list;
+}
+
 // one wideband capture block by block through a wideband bank
 static int run_wideband(int decim, const char *centre_list, const std::string &outroot, const char *input_name)
 {
@@ -357,6 +404,10 @@ static int run_wideband(int decim, const char *centre_list, const std::string &o
 
 int main(int argc, char **argv)
 {
+	if (argc == 6 && !std::strcmp(argv[1], "--wideband") && !std::strcmp(argv[3], "auto")) {
+		const std::string found = survey_centres(std::atoi(argv[2]), argv[5]);
+		return found.empty() ? 1 : run_wideband(std::atoi(argv[2]), found.c_str(), argv[4], argv[5]);
+	}
 	if (argc == 6 && !std::strcmp(argv[1], "--wideband"))
 		return run_wideband(std::atoi(argv[2]), argv[3], argv[4], argv[5]);
 	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
@@ -365,7 +416,7 @@ int main(int argc, char **argv)
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM F1,F2,... OUTROOT INPUT\n",
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM F1,F2,...|auto OUTROOT INPUT\n",
 			argv[0], argv[0], argv[0]);
 		return 1;
 	}

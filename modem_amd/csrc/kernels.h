@@ -382,4 +382,29 @@ struct SynthesizeArgs {
 void launch_synthesize(hipStream_t s, const SynthesizeArgs &a);
 long long synthesize_max_outputs();
 
+// ---- the wideband survey (k_survey.hip): a Welch power spectrum of one wideband capture, n_rows rows of nfft bins.
+// in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); the caller has checked that every position the
+// rows need is there.  Row r (row_first .. row_first + n_rows - 1) averages the segs_per_row segments from r segs_per_row on, in
+// groups of SURVEY_G: k_survey leaves the partial of (row, group) at part + ((r - row_first) n_groups + group) nfft floats in
+// natural bin order, k_survey_rows sums the groups in ascending order, multiplies by scale and writes row r in ascending frequency
+// at out + (r - row_first) nfft.  win: the nfft fp32 window values; tw: the nfft roots e^{-2 pi i m / nfft}.
+constexpr int SURVEY_G = 8;            // segments per group: part of the definition's summation order
+struct SurveyArgs {
+	const void *in;
+	int fmt;                       // OFDMRX_FMT_*
+	int nfft;                      // 1280, 2560 or 5120
+	long long in_first, n_in;
+	int segs_per_row;              // 1 .. 65536
+	int n_groups;                  // ceil(segs_per_row / SURVEY_G)
+	long long row_first, n_rows;   // n_rows n_groups nfft <= survey_max_partial_floats()
+	const float *win;              // device
+	const cf *tw;                  // device
+	float *part;                   // device, n_rows n_groups nfft floats
+	float *out;
+};
+void launch_survey(hipStream_t s, const SurveyArgs &a, float scale);
+inline long long survey_max_partial_floats() { return 1LL << 28; }   // the partials of one call: 1 GiB at most
+// host: the periodic Hann window of nfft points, rounded once to fp32 (returns nfft)
+int survey_window(int nfft, float *w);
+
 }  // namespace rx

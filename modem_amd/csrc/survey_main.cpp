@@ -1,0 +1,61 @@
+// survey_main.cpp -- `survey WIDE.wav DECIM [NFFT]`: the occupied bands of one wideband I/Q capture (2 channels, DECIM x a supported
+// rate), from one averaged power spectrum of NFFT (1280, 2560 or 5120; default 1280) bins over the whole file (ofdmrx_util_survey,
+// ofdmrx_util_find_bands).  One line per band on stdout - centre Hz, width Hz, level dB over the floor - in
+// ascending frequency: the centres `decode_stream --wideband DECIM c1,c2,... OUTROOT WIDE.wav` takes.  The floor goes to stderr.
+// Exit status 0 (also when no band is found), 1 on argument, WAV or library errors.
+#include "survey_cli.h"
+#include <cmath>
+#include <cstdlib>
+
+int main(int argc, char **argv)
+{
+	if (argc != 3 && argc != 4) {
+		std::fprintf(stderr, "usage: %s WIDE.wav DECIM [NFFT]\n", argv[0]);
+		return 1;
+	}
+	const int decim = std::atoi(argv[2]), nfft = argc == 4 ? std::atoi(argv[3]) : 1280;
+	if (decim < 2 || decim > 32 || (nfft != 1280 && nfft != 2560 && nfft != 5120)) {
+		std::fprintf(stderr, "A survey takes a decimation of 2 .. 32 and 1280, 2560 or 5120 bins.\n");
+		return 1;
+	}
+	Wav w;
+	if (!read_wav(argv[1], w) || w.frames == 0) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", argv[1]);
+		return 1;
+	}
+	if (w.channels != 2) {
+		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
+		return 1;
+	}
+	const int rate = w.rate / decim;
+	if (w.rate % decim || (rate != 8000 && rate != 16000 && rate != 44100 && rate != 48000)) {
+		std::fprintf(stderr, "Unsupported sample rate.\n");
+		return 1;
+	}
+	if (ofdmrx_abi_version() != OFDMRX_ABI_VERSION || ofdmrx_abi_minor() < 9) {
+		std::fprintf(stderr, "libofdmrx: ABI %d.%d, this program needs %d.9\n", ofdmrx_abi_version(), ofdmrx_abi_minor(), OFDMRX_ABI_VERSION);
+		return 1;
+	}
+	ofdmrx_config cfg{};
+	cfg.abi_version = OFDMRX_ABI_VERSION;
+	cfg.sample_rate = rate;
+	cfg.list_size = 8;
+	cfg.chunk_frames = 1;
+	cfg.descramble = 1;
+	ofdmrx_handle *h = nullptr;
+	const int r = ofdmrx_create(&cfg, &h);
+	if (r) {
+		std::fprintf(stderr, "ofdmrx_create: %s\n", ofdmrx_strerror(r));
+		return 1;
+	}
+	std::vector<ofdmrx_band> bands;
+	double floor = 0.0;
+	const bool ok = survey_capture(h, w, nfft, bands, floor);
+	ofdmrx_destroy(h);
+	if (!ok)
+		return 1;
+	std::fprintf(stderr, "floor %.6g (%.2f dB), %zu band%s\n", floor, floor > 0.0 ? 10.0 * std::log10(floor) : -999.0, bands.size(), bands.size() == 1 ? "" : "s");
+	for (const ofdmrx_band &b : bands)
+		std::printf("%.2f %.2f %.2f\n", b.centre_hz, b.width_hz, (double)b.level_db);
+	return 0;
+}

@@ -33,6 +33,7 @@ EXPORTS = [
     "ofdmrx_bank_begin", "ofdmrx_bank_push", "ofdmrx_bank_end", "ofdmrx_bank_resident_samples", "ofdmrx_bank_preambles",
     "ofdmrx_bank_last_stage_ops", "ofdmrx_util_fading", "ofdmrx_util_channelize_taps", "ofdmrx_util_channelize",
     "ofdmrx_bank_begin_wideband", "ofdmrx_bank_push_wideband", "ofdmrx_util_synthesize",
+    "ofdmrx_util_survey_window", "ofdmrx_util_survey", "ofdmrx_util_find_bands",
 ]
 
 
@@ -98,6 +99,40 @@ def channelize_taps(decim):
     if n != taps.size:
         raise OfdmRxError("channelize_taps: decim must be 2 .. 32")
     return taps
+
+
+SURVEY_NFFT = (1280, 2560, 5120)
+
+
+class Band(C.Structure):
+    _fields_ = [("centre_hz", C.c_double), ("width_hz", C.c_double), ("power", C.c_double), ("level_db", C.c_float),
+                ("first_bin", C.c_int32), ("last_bin", C.c_int32)]
+
+
+def survey_window(nfft):
+    """the nfft fp32 values of the survey's periodic Hann window (nfft 1280, 2560 or 5120): DESIGN.md section 4.16"""
+    nfft = int(nfft)
+    w = np.zeros(max(nfft, 1), np.float32)
+    if nfft not in SURVEY_NFFT or load_library().ofdmrx_util_survey_window(nfft, _ptr(w)) != nfft:
+        raise OfdmRxError("survey_window: nfft must be 1280, 2560 or 5120")
+    return w
+
+
+def find_bands(psd_row, rate_wide, thr_db=6.0, gap_hz=200.0, min_width_hz=1000.0, abs_floor=0.0, with_floor=False):
+    """the occupied bands of ONE survey row (fp32 [nfft], ascending frequency, on the host or a device tensor) of a capture at rate_wide
+    -> a list of dicts (centre_hz, width_hz, power, level_db, first_bin, last_bin) in ascending frequency; with_floor: -> (list, floor).
+    The floor is the row's median (or abs_floor where that is larger): the noise floor only while less than half the band is occupied"""
+    if hasattr(psd_row, "detach"):
+        psd_row = psd_row.detach().cpu().numpy()
+    row = np.ascontiguousarray(psd_row, dtype=np.float32).reshape(-1)
+    L = load_library()
+    bands = (Band * row.size)()
+    n, floor = C.c_size_t(0), C.c_double(0.0)
+    r = L.ofdmrx_util_find_bands(_ptr(row), row.size, rate_wide, thr_db, gap_hz, min_width_hz, abs_floor, row.size, bands, C.byref(n), C.byref(floor))
+    if r != 0:
+        raise OfdmRxError("find_bands: %s (%d)" % (L.ofdmrx_strerror(r).decode(), r))
+    out = [{k: getattr(bands[i], k) for k, _ in Band._fields_} for i in range(n.value)]
+    return (out, floor.value) if with_floor else out
 
 
 class Timing(C.Structure):
@@ -211,6 +246,11 @@ def load_library():
                                          C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_util_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
+    L.ofdmrx_util_survey_window.argtypes = [C.c_int, C.c_void_p]
+    L.ofdmrx_util_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_longlong, C.c_size_t,
+                                     C.c_void_p]
+    L.ofdmrx_util_find_bands.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
     L.ofdmrx_tx_frame_samples.restype = C.c_long
     L.ofdmrx_tx_frame_samples.argtypes = [C.c_int]
     L.ofdmrx_frame_samples.restype = C.c_long
@@ -589,6 +629,30 @@ class Receiver:
             raise OfdmRxError("synthesize: centres_hz, starts and gains must have one length")
         self._check(self._lib.ofdmrx_util_synthesize(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, interp, _ptr(f), _ptr(s),
                                                      _ptr(g), f.size, out_first, n_out, d_out, out_fmt))
+
+    def survey(self, d_wide, sample_format, nfft=1280, segs_per_row=None, in_first=0, row_first=0, n_rows=None):
+        """the wideband survey: d_wide, a contiguous device tensor of interleaved I/Q of sample_format, holds
+        the wideband positions in_first .. of a capture -> the Welch power spectrum torch.float32 [n_rows, nfft] on the device, rows
+        row_first .. of segs_per_row half-overlapping Hann segments each, bins in ascending frequency (bin i: (i - nfft / 2) rate / nfft).
+        segs_per_row=None: one row over everything the buffer holds (its first 65536 segments if it holds more); n_rows=None: every whole row from row_first on that the buffer
+        holds.  Waits for torch's current stream before the launch and for the handle's stream after it"""
+        import torch
+        unit = {FMT_S16: 4, FMT_U8: 2, FMT_F32: 8}[sample_format]
+        n_in = d_wide.numel() * d_wide.element_size() // unit
+        hop = nfft // 2
+        last = (in_first + n_in - hop) // hop                      # segments 0 .. last - 1 end inside the buffer
+        if segs_per_row is None:
+            if in_first or row_first:
+                raise OfdmRxError("survey: segs_per_row=None surveys a buffer that starts at position 0, as row 0")
+            segs_per_row, n_rows = min(max(last, 0), 65536), 1
+        if n_rows is None:
+            n_rows = last // max(segs_per_row, 1) - row_first
+        out = torch.empty((max(n_rows, 0), nfft), dtype=torch.float32, device=d_wide.device)
+        torch.cuda.current_stream(d_wide.device).synchronize()
+        self._check(self._lib.ofdmrx_util_survey(self._h, d_wide.data_ptr(), sample_format, in_first, n_in, nfft, segs_per_row, row_first,
+                                                 max(n_rows, 0), out.data_ptr()))
+        self.synchronize()
+        return out
 
     def tx_frame_samples(self, mode=6):
         return int(self._lib.ofdmrx_frame_samples(self.sample_rate, mode))
