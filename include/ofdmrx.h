@@ -59,7 +59,8 @@ extern "C" {
  *      added within 1.9 (the minor number stays: a caller detects it by symbol): the Watterson fading channel - ofdmrx_util_fading;
  *      the wideband front end - ofdmrx_util_channelize_taps, ofdmrx_util_channelize, ofdmrx_bank_begin_wideband,
  *      ofdmrx_bank_push_wideband; the wideband synthesizer - ofdmrx_util_synthesize; the wideband survey - ofdmrx_util_survey_window,
- *      ofdmrx_util_survey, ofdmrx_util_find_bands */
+ *      ofdmrx_util_survey, ofdmrx_util_find_bands; the wideband front end at a rational decimation -
+ *      ofdmrx_util_channelize_ratio_taps, ofdmrx_util_channelize_ratio, ofdmrx_bank_begin_wideband_ratio */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -413,6 +414,13 @@ long long ofdmrx_bank_last_stage_ops(ofdmrx_handle *h);
 int ofdmrx_bank_begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int decim, int sample_format);
 int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, size_t n_wide, int end, size_t max_records, uint8_t *payload_out,
 	ofdmrx_frame_result *results, int32_t *record_channel, int64_t *record_index, size_t *n_records, size_t *n_left);
+/* ... of a capture at p / q x the handle's rate (added within revision 1.9, detected by symbol): the front end
+ * is ofdmrx_util_channelize_ratio below.  ofdmrx_bank_push_wideband, ofdmrx_bank_end and the queries serve it unchanged: after W
+ * frames every channel has been fed ceil(W q / p) samples, one copy and one launch per push, and the contract above holds with row c
+ * of ofdmrx_util_channelize_ratio.  OFDMRX_E_ARG: what ofdmrx_bank_begin_wideband refuses, with the ratio's limits in place of
+ * decim's (p or q <= 0, reduced q above 16, p / q outside 2..32) and centres outside +- rate p / q / 2.  A ratio whose reduced q is 1
+ * opens the bank ofdmrx_bank_begin_wideband opens. */
+int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int sample_format);
 
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);
@@ -585,6 +593,31 @@ int ofdmrx_util_fading(ofdmrx_handle *h, const int16_t *d_in, size_t n_in,
  * bytes; positions or counts above 2^50; a handle with an open feed or bank. */
 int ofdmrx_util_channelize_taps(int decim, float *taps);
 int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
+
+/* Wideband front end at a rational decimation (added within revision 1.9, detected by symbol): a capture at Rw = rate p / q (formed
+ * in double) for ANY ratio with 1 <= q <= 16 and 2 <= p / q <= 32 in lowest terms - the entries reduce by the gcd themselves, (50, 8)
+ * is (25, 4).  DESIGN.md section 4.17 is the definition, held component by component to a float64 model.  With D = p / q, K = 12 D
+ * (both real) and T = floor(24 p / q) + 1 taps per phase:
+ *   time    u_n = n p (64 bits), i_n = u_n div q, q_n = u_n mod q: output n stands at wideband time i_n + q_n / q - K, 12 output
+ *           samples late as above
+ *   taps    g(t) = sinc(0.75 t / D) (0.42 + 0.5 cos(pi t / K) + 0.08 cos(2 pi t / K)) for |t| <= K, 0 outside;
+ *           h_r[j] = g(j + r / q - K), j = 0 .. T - 1, r = 0 .. q - 1: in double, each phase normalised to sum 1, rounded once to
+ *           fp32.  Every phase is flat within 0.01 dB up to rate / 4 and below -70 dB from rate / 2 on; the phases of one ratio
+ *           differ from their mean by -100 dB or less in the pass band.
+ *   phase   inc_c = (uint32) llrint(centre_hz[c] 2^32 / Rw); the phase at ABSOLUTE wideband index m is (inc_c m) mod 2^32
+ *   output  y_c[n] = sum_j h_{q_n}[j] x[i_n - j] e^{-2 pi i phase_c(i_n - j) / 2^32}, x zero at negative indices; fp32 I/Q, no clip,
+ *           summed with j ascending
+ * No state: a capture cut into blocks (each handed over with the T - 1 samples before it) gives the same bytes as one call.  W
+ * samples give ceil(W q / p) outputs per channel.
+ * ofdmrx_util_channelize_ratio_taps: host only; writes [q][T] floats for the REDUCED ratio (at most 16 x 769), returns T.
+ * ofdmrx_util_channelize_ratio: arguments, memory spaces, asynchrony and refusals are those of ofdmrx_util_channelize, with the
+ * position test restated - refused if in_first > 0 and (out_first p div q) - (T - 1) < in_first, or ((out_first + n_out - 1) p div
+ * q) > in_first + n_in - 1 - and centres outside +- Rw / 2 refused.  Both: OFDMRX_E_ARG, before any device call and with the output
+ * untouched, for p or q <= 0, a reduced q above 16, p / q outside 2..32.  With reduced q = 1 both forward to the integer entries:
+ * the same bytes by construction. */
+int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps);
+int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
 
 /* Wideband synthesizer (added within revision 1.9, detected by symbol), the mirror image of the wideband front end: n_channels

@@ -12,7 +12,8 @@
 // A WIDEBAND bank (ofdmrx_bank_begin_wideband) is fed one wideband capture instead: its channels are 2-channel F32 at
 // the handle's rate, and "the new samples" of a push are made on the device - the wideband block is copied once behind the last
 // T - 1 wideband samples (kept on the host and sent with it), and ONE k_channelize launch writes every channel's new samples straight
-// into its window.  Everything behind that step is the same code.
+// into its window (a bank opened with ofdmrx_bank_begin_wideband_ratio, DESIGN.md 4.17: ONE k_rechannelize launch).  Everything behind
+// that step is the same code.
 // The windows of all channels live in one slab pair [n_channels][cap] with a common capacity; channel c's window begins at its own
 // base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch: it is handed the address position 0
 // WOULD have and n = the samples fed, so a position past the end reads as zero as in a one-call decode); positions below the base are
@@ -54,8 +55,9 @@ struct ofdmrx_bank {
 	bool ending = false;
 	bool as_feed = false;                                     // opened by ofdmrx_feed_begin: the ofdmrx_feed_* entries serve it, ofdmrx_bank_* refuse it
 	// a wideband bank: decimation, the format of the wideband samples, how many have been pushed, and the last min(wfed, T - 1) of them
+	// (decimation p / q in lowest terms: an integer decimation has q = 1 and runs k_channelize, any other k_rechannelize)
 	bool wide = false;
-	int decim = 0, wfmt = 0;
+	int p = 0, q = 1, wfmt = 0;
 	long long wfed = 0;
 	std::vector<char> wtail;
 };
@@ -319,8 +321,9 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 	if (b.wide && n_wide) {
 		// the block behind the kept tail, one copy; one launch for every channel's new outputs ceil(W_old / D) .. ceil(W_new / D) - 1.
 		// The first of them reads from ceil(W_old / D) D - (T - 1) >= W_old - (T - 1) on: inside the tail, or below position 0
-		const long long D = b.decim, T = 24 * D + 1, tail = (long long)(b.wtail.size() / wunit);
-		const long long o0 = (b.wfed + D - 1) / D, o1 = (b.wfed + (long long)n_wide + D - 1) / D;
+		// (D = p / q: output n >= ceil(W_old q / p) reads from n p div q - (T - 1) >= W_old - (T - 1) on)
+		const long long num = b.p, den = b.q, T = 24 * num / den + 1, tail = (long long)(b.wtail.size() / wunit);
+		const long long o0 = (b.wfed * den + num - 1) / num, o1 = ((b.wfed + (long long)n_wide) * den + num - 1) / num;
 		std::memcpy(b.stage_h.data(), b.wtail.data(), b.wtail.size());
 		std::memcpy(b.stage_h.data() + b.wtail.size(), samples, n_wide * wunit);
 		if (o1 > o0) {
@@ -332,21 +335,38 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 			if (r)
 				return r;
 			HIP_OK(hipMemcpyAsync(b.stage.p, b.stage_h.data(), b.stage_h.size(), hipMemcpyHostToDevice, s));
-			ChannelizeArgs a{};
-			a.in = b.stage.p;
-			a.fmt = b.wfmt;
-			a.decim = b.decim;
-			a.in_first = b.wfed - tail;
-			a.n_in = tail + (long long)n_wide;
-			a.taps = h->chz_taps.as<float>();
-			a.inc = h->chz_inc.as<unsigned>();
-			a.n_channels = (int)C;
-			a.out_first = o0;
-			a.n_out = o1 - o0;
-			a.out = nullptr;
-			a.out_stride = 0;
-			a.dst = dpar + P_PL_DST * P;
-			launch_channelize(s, a);
+			if (b.q > 1) {
+				RechannelizeArgs a{};
+				a.in = b.stage.p;
+				a.fmt = b.wfmt;
+				a.p = b.p;
+				a.q = b.q;
+				a.in_first = b.wfed - tail;
+				a.n_in = tail + (long long)n_wide;
+				a.taps = h->rcz_taps.as<float>();
+				a.inc = h->rcz_inc.as<unsigned>();
+				a.n_channels = (int)C;
+				a.out_first = o0;
+				a.n_out = o1 - o0;
+				a.dst = dpar + P_PL_DST * P;
+				launch_rechannelize(s, a);
+			} else {
+				ChannelizeArgs a{};
+				a.in = b.stage.p;
+				a.fmt = b.wfmt;
+				a.decim = b.p;
+				a.in_first = b.wfed - tail;
+				a.n_in = tail + (long long)n_wide;
+				a.taps = h->chz_taps.as<float>();
+				a.inc = h->chz_inc.as<unsigned>();
+				a.n_channels = (int)C;
+				a.out_first = o0;
+				a.n_out = o1 - o0;
+				a.out = nullptr;
+				a.out_stride = 0;
+				a.dst = dpar + P_PL_DST * P;
+				launch_channelize(s, a);
+			}
 			b.ops += 2;
 		}
 		const size_t keep = std::min(b.stage_h.size(), (size_t)(T - 1) * wunit);
@@ -728,7 +748,36 @@ extern "C" int ofdmrx_bank_begin_wideband(ofdmrx_handle *h, size_t n_channels, c
 		return r;
 	}
 	h->bank->wide = true;
-	h->bank->decim = decim;
+	h->bank->p = decim;
+	h->bank->q = 1;
+	h->bank->wfmt = fmt;
+	return 0;
+}
+
+// ... at a rational decimation p / q: push, end and the queries serve it as they serve the integer one
+extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt)
+{
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	if (q == 1)
+		return ofdmrx_bank_begin_wideband(h, n_channels, centre_hz, p, fmt);
+	if (!h || !centre_hz || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || n_channels < 1 || n_channels > 65535)
+		return OFDMRX_E_ARG;
+	if (h->bank)
+		return OFDMRX_E_ARG;
+	for (size_t c = 0; c < n_channels; ++c)
+		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * ((double)h->rate * (double)p / (double)q))
+			return OFDMRX_E_ARG;
+	int r = begin(h, n_channels, OFDMRX_FMT_F32, 2, false);
+	if (r)
+		return r;
+	if ((r = rechannelize_setup(h, p, q, centre_hz, n_channels))) {
+		bank_free(h);
+		return r;
+	}
+	h->bank->wide = true;
+	h->bank->p = p;
+	h->bank->q = q;
 	h->bank->wfmt = fmt;
 	return 0;
 }
@@ -746,9 +795,9 @@ extern "C" int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, 
 	HIP_OK(hipSetDevice(h->cfg.device));
 	b.ops = 0;
 	if (!b.ending) {
-		// every channel takes the outputs the block completes: W samples have given ceil(W / D) of them
-		const long long D = b.decim;
-		const std::vector<size_t> add(b.C, (size_t)((b.wfed + (long long)n_wide + D - 1) / D - (b.wfed + D - 1) / D));
+		// every channel takes the outputs the block completes: W samples have given ceil(W q / p) of them
+		const long long P = b.p, Q = b.q;
+		const std::vector<size_t> add(b.C, (size_t)(((b.wfed + (long long)n_wide) * Q + P - 1) / P - (b.wfed * Q + P - 1) / P));
 		const std::vector<uint8_t> fin(b.C, (uint8_t)(end_all && !b.ch[0].ended));
 		r = bank_step(h, (const char *)samples, 0, add.data(), fin, n_wide);
 		if (r)

@@ -17,6 +17,8 @@
 // `decode_stream --wideband DECIM auto OUTROOT WIDE.wav`: the capture is surveyed first (ofdmrx_util_survey over the whole file, 1280
 // bins, and ofdmrx_util_find_bands with its default parameters: what `survey WIDE.wav DECIM` prints), the centres found are printed
 // on stderr, and then exactly the form above runs with that list.  The file is read twice, so `auto` does not take standard input.
+// DECIM may be a ratio P/Q in both forms - it is one when it holds a '/' (Q <= 16, 2 <= P / Q <= 32): the
+// capture's rate x Q / P must be a supported rate, and the bank is opened with ofdmrx_bank_begin_wideband_ratio.
 #include "survey_cli.h"
 #include <algorithm>
 #include <cstdlib>
@@ -280,7 +282,7 @@ static int run_live_batch(const std::string &outroot, int n_inputs, char **input
 }
 
 // the centres of the occupied bands of a capture, as the list run_wideband takes ("" with a message: none, or an error)
-static std::string survey_centres(int decim, const char *input_name)
+static std::string survey_centres(const Decimation &decim, const char *input_name)
 {
 	if (!std::strcmp(input_name, "-") || !std::strcmp(input_name, "/dev/stdin")) {
 		std::fprintf(stderr, "`auto` reads the capture twice: give a file, not standard input.\n");
@@ -295,12 +297,12 @@ static std::string survey_centres(int decim, const char *input_name)
 		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
 		return "";
 	}
-	if (decim < 2 || decim > 32 || w.rate % decim || !supported(2, w.rate / decim)) {
-		if (decim < 2 || decim > 32 || w.rate % decim)
+	if (!decim.valid() || !decim.rate_of(w.rate) || !supported(2, decim.rate_of(w.rate))) {
+		if (!decim.valid() || !decim.rate_of(w.rate))
 			std::fprintf(stderr, "Unsupported sample rate.\n");
 		return "";
 	}
-	ofdmrx_handle *h = create(w.rate / decim);
+	ofdmrx_handle *h = create(decim.rate_of(w.rate));
 	if (!h)
 		return "";
 	std::vector<ofdmrx_band> bands;
@@ -324,7 +326,7 @@ static std::string survey_centres(int decim, const char *input_name)
 }
 
 // one wideband capture block by block through a wideband bank
-static int run_wideband(int decim, const char *centre_list, const std::string &outroot, const char *input_name)
+static int run_wideband(const Decimation &decim, const char *centre_list, const std::string &outroot, const char *input_name)
 {
 	std::vector<double> centres;
 	for (const char *p = centre_list; *p;) {
@@ -337,8 +339,8 @@ static int run_wideband(int decim, const char *centre_list, const std::string &o
 		centres.push_back(f);
 		p = *e ? e + 1 : e;
 	}
-	if (decim < 2 || decim > 32 || centres.empty() || centres.size() > 65535) {
-		std::fprintf(stderr, "A wideband bank takes a decimation of 2 .. 32 and 1 .. 65535 centre frequencies.\n");
+	if (!decim.valid() || centres.empty() || centres.size() > 65535) {
+		std::fprintf(stderr, "A wideband bank takes a decimation of 2 .. 32 (a ratio P/Q: Q <= 16) and 1 .. 65535 centre frequencies.\n");
 		return 1;
 	}
 	WavStream w;
@@ -350,12 +352,12 @@ static int run_wideband(int decim, const char *centre_list, const std::string &o
 		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
 		return 1;
 	}
-	if (w.rate % decim || !supported(2, w.rate / decim)) {
-		if (w.rate % decim)
+	if (!decim.rate_of(w.rate) || !supported(2, decim.rate_of(w.rate))) {
+		if (!decim.rate_of(w.rate))
 			std::fprintf(stderr, "Unsupported sample rate.\n");
 		return 1;
 	}
-	ofdmrx_handle *h = create(w.rate / decim);
+	ofdmrx_handle *h = create(decim.rate_of(w.rate));
 	if (!h)
 		return 1;
 	const size_t S = centres.size(), cap = 64;
@@ -366,7 +368,8 @@ static int run_wideband(int decim, const char *centre_list, const std::string &o
 		prefixes[i] = std::to_string(i) + ":";
 		(void)mkdir(dirs[i].c_str(), 0777);
 	}
-	int r = ofdmrx_bank_begin_wideband(h, S, centres.data(), decim, w.fmt);
+	int r = decim.ratio ? ofdmrx_bank_begin_wideband_ratio(h, S, centres.data(), decim.p, decim.q, w.fmt)
+		: ofdmrx_bank_begin_wideband(h, S, centres.data(), decim.p, w.fmt);
 	std::vector<uint8_t> out(cap * OFDMRX_PAYLOAD_BYTES), pcm;
 	std::vector<ofdmrx_frame_result> res(cap);
 	std::vector<int32_t> chan(cap);
@@ -405,18 +408,18 @@ static int run_wideband(int decim, const char *centre_list, const std::string &o
 int main(int argc, char **argv)
 {
 	if (argc == 6 && !std::strcmp(argv[1], "--wideband") && !std::strcmp(argv[3], "auto")) {
-		const std::string found = survey_centres(std::atoi(argv[2]), argv[5]);
-		return found.empty() ? 1 : run_wideband(std::atoi(argv[2]), found.c_str(), argv[4], argv[5]);
+		const std::string found = survey_centres(Decimation(argv[2]), argv[5]);
+		return found.empty() ? 1 : run_wideband(Decimation(argv[2]), found.c_str(), argv[4], argv[5]);
 	}
 	if (argc == 6 && !std::strcmp(argv[1], "--wideband"))
-		return run_wideband(std::atoi(argv[2]), argv[3], argv[4], argv[5]);
+		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5]);
 	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
 		return run_live_batch(argv[3], argc - 4, argv + 4);
 	if (argc >= 4 && !std::strcmp(argv[1], "--batch"))
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM F1,F2,...|auto OUTROOT INPUT\n",
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n",
 			argv[0], argv[0], argv[0]);
 		return 1;
 	}

@@ -359,6 +359,32 @@ long long channelize_max_outputs();
 int channelize_taps(int decim, float *taps);
 unsigned channelize_inc(double centre_hz, double rw);
 
+// ---- the wideband front end at a rational decimation p / q in lowest terms (k_rechannelize.hip): 1 <= q <= 16,
+// 2 <= p / q <= 32.  in, out, dst, inc: as ChannelizeArgs.  Output n reads the wideband positions n p div q - (T - 1) .. n p div q,
+// T = 24 p div q + 1.  taps: device, [T][q] - tap j of phase r at j q + r (the transpose of what rechannelize_taps writes).
+struct RechannelizeArgs {
+	const void *in;
+	int fmt;                       // OFDMRX_FMT_*
+	int p, q;
+	long long in_first, n_in;
+	const float *taps;             // device, [T][q]
+	const unsigned *inc;           // device, [n_channels]
+	int n_channels;
+	long long out_first, n_out;    // n_out <= rechannelize_max_outputs()
+	float *out;
+	long long out_stride;          // I/Q pairs per channel row
+	const long long *dst;          // device, [n_channels] addresses, nullable
+	int n_taps, m, hist, rows;     // (the launch fills them in from rechannelize_shape)
+};
+// what a workgroup's tile looks like: T, the outputs per residue M (a tile is q M outputs), the rows of history, the rows of a
+// plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
+struct RechannelizeShape { int n_taps, m, hist, rows, passes; size_t lds; };
+RechannelizeShape rechannelize_shape(int p, int q);
+void launch_rechannelize(hipStream_t s, const RechannelizeArgs &a);
+long long rechannelize_max_outputs();
+// host: the taps of the reduced ratio p / q as [q][T] (returns T); q = 1: channelize_taps(p, .)
+int rechannelize_taps(int p, int q, float *taps);
+
 // ---- the wideband synthesizer (k_synthesize.hip): n_channels narrowband rows -> one wideband capture.  in: sample
 // frame j (0 .. n_in - 1) of channel c at c in_stride + j sample frames (interleaved I/Q of in_fmt: S16 or F32); every index outside
 // reads as zero and is never loaded.  Output m (out_first .. out_first + n_out - 1) goes m - out_first sample frames into out, as

@@ -1,11 +1,48 @@
-// survey_cli.h -- what `survey` and `decode_stream --wideband DECIM auto` share: the occupied bands of a whole wideband capture
+// survey_cli.h -- what `survey` and `decode_stream --wideband DECIM|P/Q auto` share: the decimation argument, and the occupied bands
+// of a whole wideband capture
 // (ofdmrx_util_survey + ofdmrx_util_find_bands) with the finder's default parameters.
 #pragma once
 #include "wav_read.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstdlib>
+#include <cstring>
 
 constexpr double SURVEY_THR_DB = 6.0, SURVEY_GAP_HZ = 200.0, SURVEY_MIN_WIDTH_HZ = 1000.0;
+
+// The decimation argument of both programs: DECIM, an integer 2 .. 32, or - when it holds a '/' - a ratio P/Q (DESIGN.md section
+// 4.17: lowest terms Q <= 16, 2 <= P / Q <= 32).  valid(): in range.  rate_of(): the handle rate wide_rate Q / P, 0 if that is no integer.
+struct Decimation {
+	int p = 0, q = 1;
+	bool ratio = false;
+	explicit Decimation(const char *arg)
+	{
+		const char *slash = std::strchr(arg, '/');
+		p = std::atoi(arg);
+		ratio = slash != nullptr;
+		if (ratio)
+			q = std::atoi(slash + 1);
+	}
+	bool valid() const
+	{
+		if (!ratio)
+			return p >= 2 && p <= 32;
+		if (p <= 0 || q <= 0)
+			return false;
+		int a = p, b = q;
+		while (b) {
+			const int t = a % b;
+			a = b;
+			b = t;
+		}
+		return q / a <= 16 && p >= 2 * q && p <= 32 * q;
+	}
+	int rate_of(int wide_rate) const
+	{
+		const long long num = (long long)wide_rate * q;
+		return (p > 0 && num % p == 0) ? (int)(num / p) : 0;
+	}
+};
 
 // w: a 2-channel capture read by read_wav.  One spectrum over the whole file: rows of at most 65536 segments, averaged here in double
 // when there are several.  Returns false with a message on stderr; bands may come back empty.

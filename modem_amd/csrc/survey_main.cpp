@@ -1,5 +1,5 @@
-// survey_main.cpp -- `survey WIDE.wav DECIM [NFFT]`: the occupied bands of one wideband I/Q capture (2 channels, DECIM x a supported
-// rate), from one averaged power spectrum of NFFT (1280, 2560 or 5120; default 1280) bins over the whole file (ofdmrx_util_survey,
+// survey_main.cpp -- `survey WIDE.wav DECIM|P/Q [NFFT]`: the occupied bands of one wideband I/Q capture (2 channels, DECIM or P/Q x a
+// supported rate), from one averaged power spectrum of NFFT (1280, 2560 or 5120; default 1280) bins over the whole file (ofdmrx_util_survey,
 // ofdmrx_util_find_bands).  One line per band on stdout - centre Hz, width Hz, level dB over the floor - in
 // ascending frequency: the centres `decode_stream --wideband DECIM c1,c2,... OUTROOT WIDE.wav` takes.  The floor goes to stderr.
 // Exit status 0 (also when no band is found), 1 on argument, WAV or library errors.
@@ -10,12 +10,13 @@
 int main(int argc, char **argv)
 {
 	if (argc != 3 && argc != 4) {
-		std::fprintf(stderr, "usage: %s WIDE.wav DECIM [NFFT]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s WIDE.wav DECIM|P/Q [NFFT]\n", argv[0]);
 		return 1;
 	}
-	const int decim = std::atoi(argv[2]), nfft = argc == 4 ? std::atoi(argv[3]) : 1280;
-	if (decim < 2 || decim > 32 || (nfft != 1280 && nfft != 2560 && nfft != 5120)) {
-		std::fprintf(stderr, "A survey takes a decimation of 2 .. 32 and 1280, 2560 or 5120 bins.\n");
+	const Decimation decim(argv[2]);
+	const int nfft = argc == 4 ? std::atoi(argv[3]) : 1280;
+	if (!decim.valid() || (nfft != 1280 && nfft != 2560 && nfft != 5120)) {
+		std::fprintf(stderr, "A survey takes a decimation of 2 .. 32 (a ratio P/Q: Q <= 16) and 1280, 2560 or 5120 bins.\n");
 		return 1;
 	}
 	Wav w;
@@ -27,8 +28,8 @@ int main(int argc, char **argv)
 		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
 		return 1;
 	}
-	const int rate = w.rate / decim;
-	if (w.rate % decim || (rate != 8000 && rate != 16000 && rate != 44100 && rate != 48000)) {
+	const int rate = decim.rate_of(w.rate);
+	if (!rate || (rate != 8000 && rate != 16000 && rate != 44100 && rate != 48000)) {
 		std::fprintf(stderr, "Unsupported sample rate.\n");
 		return 1;
 	}

@@ -1,5 +1,7 @@
 """ctypes mirror of include/ofdmrx.h (the drop-in boundary for decode.cc's Decoder seam)."""
 import ctypes as C
+import fractions
+import math
 import os
 import subprocess
 
@@ -34,6 +36,7 @@ EXPORTS = [
     "ofdmrx_bank_last_stage_ops", "ofdmrx_util_fading", "ofdmrx_util_channelize_taps", "ofdmrx_util_channelize",
     "ofdmrx_bank_begin_wideband", "ofdmrx_bank_push_wideband", "ofdmrx_util_synthesize",
     "ofdmrx_util_survey_window", "ofdmrx_util_survey", "ofdmrx_util_find_bands",
+    "ofdmrx_util_channelize_ratio_taps", "ofdmrx_util_channelize_ratio", "ofdmrx_bank_begin_wideband_ratio",
 ]
 
 
@@ -98,6 +101,32 @@ def channelize_taps(decim):
     n = load_library().ofdmrx_util_channelize_taps(decim, _ptr(taps))
     if n != taps.size:
         raise OfdmRxError("channelize_taps: decim must be 2 .. 32")
+    return taps
+
+
+def _ratio(decim):
+    """decim as the front end takes it: an int -> (decim, None), the integer entries; a pair (p, q) or a fractions.Fraction ->
+    (p, q), the ratio entries"""
+    if isinstance(decim, fractions.Fraction):
+        return int(decim.numerator), int(decim.denominator)
+    if isinstance(decim, (tuple, list)):
+        p, q = decim
+        return int(p), int(q)
+    return int(decim), None
+
+
+def channelize_ratio_taps(p, q):
+    """the fp32 taps [q', T] of the wideband front end at the decimation p / q, reduced to lowest terms p' / q' (q' <= 16, 2 <= p / q
+    <= 32), T = 24 p' // q' + 1: DESIGN.md section 4.17"""
+    p, q = int(p), int(q)
+    if p <= 0 or q <= 0:
+        raise OfdmRxError("channelize_ratio_taps: p and q must be positive")
+    g = math.gcd(p, q)
+    p, q = p // g, q // g
+    T = 24 * p // q + 1
+    taps = np.zeros((min(q, 16), T), np.float32)
+    if q > 16 or load_library().ofdmrx_util_channelize_ratio_taps(p, q, _ptr(taps)) != T:
+        raise OfdmRxError("channelize_ratio_taps: the reduced q must be 1 .. 16 and p / q 2 .. 32")
     return taps
 
 
@@ -242,6 +271,10 @@ def load_library():
     L.ofdmrx_util_fading.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(Fading),
                                      C.c_uint64, C.c_uint64]
     L.ofdmrx_util_channelize_taps.argtypes = [C.c_int, C.c_void_p]
+    L.ofdmrx_util_channelize_ratio_taps.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.ofdmrx_util_channelize_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.ofdmrx_bank_begin_wideband_ratio.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.ofdmrx_util_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_util_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -389,7 +422,8 @@ class Receiver:
 
     def wideband_bank(self, centres_hz, decim, dtype=np.int16, esn0_rows=False):
         """open a bank whose channels are cut from one wideband I/Q capture (decim x the handle's rate, interleaved I/Q of dtype) at
-        the centre frequencies centres_hz: push the capture block by block"""
+        the centre frequencies centres_hz: push the capture block by block.  decim: an int, or a ratio - a pair (p, q) or a
+        fractions.Fraction"""
         return WidebandBank(self, centres_hz, decim, dtype, esn0_rows)
 
     def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
@@ -612,8 +646,14 @@ class Receiver:
     def channelize(self, d_in, fmt, in_first, n_in, decim, centres_hz, out_first, n_out, d_out, out_stride=None):
         """the wideband front end on device buffers (ints): d_in holds the wideband positions in_first .. in_first + n_in - 1 of an
         interleaved I/Q capture at decim x the handle's rate; output n (out_first .. out_first + n_out - 1) of the channel centred at
-        centres_hz[c] goes to d_out + 8 (c out_stride + n - out_first) as fp32 I/Q; asynchronous on the handle's stream"""
+        centres_hz[c] goes to d_out + 8 (c out_stride + n - out_first) as fp32 I/Q; asynchronous on the handle's stream.  decim: an
+        int, or a ratio - a pair (p, q) or a fractions.Fraction"""
         f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
+        decim, q = _ratio(decim)
+        if q is not None:
+            self._check(self._lib.ofdmrx_util_channelize_ratio(self._h, d_in, fmt, in_first, n_in, decim, q, _ptr(f), f.size, out_first, n_out,
+                                                               d_out, n_out if out_stride is None else out_stride))
+            return
         self._check(self._lib.ofdmrx_util_channelize(self._h, d_in, fmt, in_first, n_in, decim, _ptr(f), f.size, out_first, n_out, d_out,
                                                      n_out if out_stride is None else out_stride))
 
@@ -857,9 +897,13 @@ class WidebandBank(Bank):
     def __init__(self, rx, centres_hz, decim, dtype=np.int16, esn0_rows=False):
         self._rx, self._lib, self._h = rx, rx._lib, rx._h
         f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
-        self.centres_hz, self.decim = f, int(decim)
+        p, q = _ratio(decim)
+        self.centres_hz, self.decim = f, p if q is None else (p, q)
         self.n_channels, self.channels, self.dtype, self._rows = f.size, 2, np.dtype(dtype), bool(esn0_rows)
-        rx._check(self._lib.ofdmrx_bank_begin_wideband(self._h, f.size, _ptr(f), self.decim, rx._fmt(self.dtype)))
+        if q is None:
+            rx._check(self._lib.ofdmrx_bank_begin_wideband(self._h, f.size, _ptr(f), p, rx._fmt(self.dtype)))
+        else:
+            rx._check(self._lib.ofdmrx_bank_begin_wideband_ratio(self._h, f.size, _ptr(f), p, q, rx._fmt(self.dtype)))
         self.open = True
         self.n_left = 0
         self._ops = 0

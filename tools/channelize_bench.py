@@ -7,6 +7,10 @@ For 1, 16 and 256 channels at D = 6 and D = 24, with hipEvents on the handle's s
   N n_out T 4 FMAs at DESIGN.md section 6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs), and which of the two is nearer.
 Then one wideband-bank push of one second x 64 channels against ofdmrx_util_channelize + copy to host + ofdmrx_bank_push of the same
 data (host wall time: these calls block).
+--ratio P/Q (repeatable) times the front end at a rational decimation instead (ofdmrx_util_channelize_ratio, k_rechannelize.hip;
+DESIGN.md section 4.17): for 1, 16 and 256 channels, beside k_channelize at the neighbouring integer D on the same bytes, beside
+k_awgn_tile and the arithmetic floor N n_out T 4 FMAs, with the time per FMA relative to k_channelize's; then one wideband second x
+64 channels through the ratio bank.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import ctypes as C
@@ -122,8 +126,100 @@ def child(args):
     print(json.dumps({"tool": "channelize_bench", "samples": W, "rows": rows, "bank": bank}), flush=True)
 
 
+def child_ratio(args):
+    import numpy as np
+    import torch
+    import modem_amd
+    import modem_amd.ofdmrx as M
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    W = args.samples
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    d_in = torch.randint(-20000, 20000, (W, 2), dtype=torch.int16, device=dev, generator=gen)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    ratios = [tuple(int(t) for t in r.split("/")) for r in args.ratio]
+    rows = []
+    for P, Q in ratios:
+        T = 24 * P // Q + 1
+        n_out = -(-W * Q // P)
+        D = min(32, max(2, int(round(P / Q))))                        # the neighbouring integer decimation, on the same bytes
+        Ti, ni = 24 * D + 1, -(-W // D)
+        for N in (1, 16, 256):
+            f = np.linspace(-0.45, 0.45, N) * 8000.0 * P / Q + 0.123
+            d_out = torch.empty((N, max(n_out, ni), 2), dtype=torch.float32, device=dev)
+            ms = timed(lambda k: rx.channelize(d_in.data_ptr(), 0, 0, W, (P, Q), f, 0, n_out, d_out.data_ptr()))
+            fi = np.linspace(-0.45, 0.45, N) * 8000.0 * D + 0.123
+            msi = timed(lambda k: rx.channelize(d_in.data_ptr(), 0, 0, W, D, fi, 0, ni, d_out.data_ptr()))
+            nbytes = W * 4 + N * n_out * 8
+            spf = 4096
+            frames = max(1, nbytes // (2 * spf * 4))
+            d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+            d_b = torch.empty_like(d_a)
+            awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+            floor = N * n_out * T * 4 / 64.0 * FMA_NS * 1e-6 / SIMDS
+            per_fma = (ms / (N * n_out * T)) / (msi / (N * ni * Ti))
+            rows.append(dict(ratio="%d/%d" % (P, Q), taps=T, channels=N, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1),
+                             gmac_per_s=round(N * n_out * T / ms / 1e6, 1), integer_decim=D, k_channelize_ms=round(msi, 4),
+                             time_per_fma_vs_k_channelize=round(per_fma, 2), awgn_tile_ms=round(awgn, 4), fma_floor_ms=round(floor, 4),
+                             nearer="arithmetic" if floor > awgn else "memory", over_bound=round(ms / max(floor, awgn), 2)))
+            del d_out, d_a, d_b
+    rx.close()
+
+    # one wideband second x 64 channels through the ratio bank
+    N = 64
+    outs = (np.zeros((64, 5380), np.uint8), np.zeros(64, M.RESULT_DTYPE), np.zeros(64, np.int32), np.zeros(64, np.int64))
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    p = M._ptr
+    banks = []
+    for P, Q in ratios:
+        if 8000 * P % Q:
+            continue
+        sec = 8000 * P // Q
+        f = np.linspace(-0.45, 0.45, N) * sec + 0.123
+        rng = np.random.default_rng(2)
+        cap = rng.integers(-300, 300, size=((args.warmup + args.reps) * sec, 2)).astype(np.int16)
+        rxw = modem_amd.Receiver(device=0)
+        L, h = rxw._lib, rxw._h
+        assert L.ofdmrx_bank_begin_wideband_ratio(h, N, p(f), P, Q, 0) == 0
+        wide = []
+        for k in range(args.warmup + args.reps):
+            blk = np.ascontiguousarray(cap[k * sec:(k + 1) * sec])
+            t = time.perf_counter()
+            assert L.ofdmrx_bank_push_wideband(h, p(blk), sec, 0, 64, p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), C.byref(a), C.byref(b)) == 0
+            wide.append((time.perf_counter() - t) * 1e3)
+        ops = int(L.ofdmrx_bank_last_stage_ops(h))
+        rxw.close()
+        banks.append(dict(ratio="%d/%d" % (P, Q), channels=N, wideband_samples=sec, push_ms=round(statistics.median(wide[args.warmup:]), 3), stage_ops=ops))
+    print("ratio     T channels      ms    GB/s  GMAC/s  k_channelize D ms  t/FMA vs it  awgn_tile ms  FMA floor ms  nearer bound  time / bound")
+    for r in rows:
+        print("%-7s %3d %8d %7.4f %7.1f %7.1f %9d %9.4f %10.2f %13.4f %13.4f  %-12s %6.2f"
+              % (r["ratio"], r["taps"], r["channels"], r["ms"], r["gb_per_s"], r["gmac_per_s"], r["integer_decim"], r["k_channelize_ms"],
+                 r["time_per_fma_vs_k_channelize"], r["awgn_tile_ms"], r["fma_floor_ms"], r["nearer"], r["over_bound"]))
+    for k in banks:
+        print("one wideband second (%d samples at %s) x %d channels through the ratio bank: push %.3f ms (%d stage ops)"
+              % (k["wideband_samples"], k["ratio"], k["channels"], k["push_ms"], k["stage_ops"]))
+    print(json.dumps({"tool": "channelize_bench", "samples": W, "ratio_rows": rows, "ratio_banks": banks}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ratio", action="append", default=[], metavar="P/Q", help="time the front end at this rational decimation (repeatable)")
     ap.add_argument("--samples", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
@@ -131,8 +227,10 @@ def main():
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
-        return child(args)
+        return child_ratio(args) if args.ratio else child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    for r in args.ratio:
+        cmd += ["--ratio", r]
     try:
         return subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
