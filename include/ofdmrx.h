@@ -60,7 +60,8 @@ extern "C" {
  *      the wideband front end - ofdmrx_util_channelize_taps, ofdmrx_util_channelize, ofdmrx_bank_begin_wideband,
  *      ofdmrx_bank_push_wideband; the wideband synthesizer - ofdmrx_util_synthesize; the wideband survey - ofdmrx_util_survey_window,
  *      ofdmrx_util_survey, ofdmrx_util_find_bands; the wideband front end at a rational decimation -
- *      ofdmrx_util_channelize_ratio_taps, ofdmrx_util_channelize_ratio, ofdmrx_bank_begin_wideband_ratio */
+ *      ofdmrx_util_channelize_ratio_taps, ofdmrx_util_channelize_ratio, ofdmrx_bank_begin_wideband_ratio; the wideband synthesizer
+ *      at a rational interpolation - ofdmrx_util_synthesize_ratio */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -648,6 +649,30 @@ int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_
  * above 2^50 (n_out above 2^41 - 1024, which the launch cannot hold; in_stride above 2^34); d_out overlapping d_in; d_in or d_out
  * off its sample-frame boundary; a handle with an open feed or bank. */
 int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
+	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out,
+	void *d_out, int out_format);
+
+/* Wideband synthesizer at a rational interpolation (added within revision 1.9, detected by symbol), the mirror image of the front end
+ * at a rational decimation: a capture at Rw = rate p / q (formed in double) for ANY ratio with 1 <= q <= 16 and 2 <= p / q <= 32 in
+ * lowest terms - the entry reduces by the gcd itself, (50, 8) is (25, 4).  DESIGN.md section 4.18 is the definition, held component
+ * by component to a float64 model.  With D = p / q and K = 12 D (both real) and H[r][j] the fp32 table [q][T], T = floor(24 p / q) +
+ * 1, that ofdmrx_util_channelize_ratio_taps(p, q, .) writes - there is no new filter - read as one sequence on the grid of 1 / q
+ * wideband samples, G[tn] = H[tn mod q][tn div q], tn = 0 .. 24 p:
+ *   input, phase: as ofdmrx_util_synthesize, with this Rw
+ *   gain    G_c = D gain[c], D = (double)p / (double)q, formed in double, rounded once to fp32
+ *   output  at ABSOLUTE wideband index m, r = m - start[c] (nothing where r < 0), nu = r q (64 bits), q0 = nu div p, b = nu mod p:
+ *           w[m] = sum_c G_c e^{+2 pi i phase_c(m) / 2^32} sum_a G[b + a p] x_c[q0 - a], a = 0 .. 23, and a = 24 where b = 0.  F32 and
+ *           S16 output as ofdmrx_util_synthesize writes them: a zero always +0, never -32768.
+ * A channel's support is start[c] .. start[c] + ((n_in - 1 + 24) p) div q.  No state: a capture made window by window has the bytes
+ * of one made in one call.  Sample j of channel c sits at wideband time start[c] + j D + K; through ofdmrx_util_channelize_ratio at
+ * the same centre and ratio it comes out at index j + 24 + start[c] q / p - exactly where p divides start[c], by a fractional delay
+ * otherwise.
+ * Arguments, memory spaces, asynchrony, the ring of parameter sets (a set belongs to its ratio: 25/4 after 6, or after 25/3, never
+ * reuses one) and every refusal are those of ofdmrx_util_synthesize, with the ratio's limits in place of interp's: OFDMRX_E_ARG,
+ * before any device call and with the output untouched, for p or q <= 0, a reduced q above 16, p / q outside 2..32; a centre outside
+ * +- Rw / 2; a gain for which D gain is not finite; n_out above 2^41 - 1024, which the launch cannot hold.  With reduced q = 1 it
+ * forwards to ofdmrx_util_synthesize: the same bytes by construction. */
+int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
 	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out,
 	void *d_out, int out_format);
 

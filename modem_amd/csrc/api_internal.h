@@ -243,7 +243,7 @@ struct ofdmrx_handle {
 		DevBuf dev;
 		std::vector<SynthChannel> ch;   // (the host copy the upload reads: it lives as long as the slot)
 		std::vector<float> taps;
-		int interp = 0;
+		int p = 0, q = 0;               // the reduced ratio the set was made for (q = 1: the integer synthesizer's interp); 0: none
 		hipEvent_t done = nullptr;
 		~SynSlot() { if (done) (void)hipEventDestroy(done); }
 	};

@@ -1,14 +1,28 @@
-// api_synthesize.cpp -- the wideband synthesizer behind include/ofdmrx.h: ofdmrx_util_synthesize.
-// Everything the kernel relies on is checked here, before any device call.
+// api_synthesize.cpp -- the wideband synthesizer behind include/ofdmrx.h: ofdmrx_util_synthesize; behind it
+// the same at a rational interpolation p / q (section 4.18): ofdmrx_util_synthesize_ratio.
+// Everything the kernels rely on is checked here, before any device call.
 #include "api_internal.h"
+
+// G[tn] = H[tn mod q][tn div q], tn = 0 .. 24 p, of rechannelize_taps' [q][T] -> rows b = 0 .. p - 1 of G[b + a p], a = 0 .. 24
+static void resynthesize_taps(int p, int q, std::vector<float> &rows)
+{
+	const size_t T = (size_t)(24 * p / q + 1);
+	std::vector<float> H((size_t)q * T);
+	rechannelize_taps(p, q, H.data());
+	rows.assign((size_t)p * RSY_ROW, 0.f);
+	for (int tn = 0; tn <= 24 * p; ++tn)
+		rows[(size_t)(tn % p) * RSY_ROW + (size_t)(tn / p)] = H[(size_t)(tn % q) * T + (size_t)(tn / q)];
+}
 
 // the parameters of a call on the device: the slot of the call before if nothing differs, else the next slot of the ring, once the
 // last launch that read it is over (the upload reads the slot's own host copy, which nothing touches before then either)
-static int synthesize_setup(ofdmrx_handle *h, int interp, const std::vector<SynthChannel> &ch, const ofdmrx_handle::SynSlot **out)
+// q = 1: the 24 p + 1 taps of the integer synthesizer at interp p; q > 1: the ratio's taps transposed, [p][RSY_ROW].  The taps lie
+// behind the channels (16 bytes each), so they begin on a 16-byte boundary
+static int synthesize_setup(ofdmrx_handle *h, int p, int q, const std::vector<SynthChannel> &ch, const ofdmrx_handle::SynSlot **out)
 {
 	constexpr int RING = (int)(sizeof(h->syn) / sizeof(h->syn[0]));
 	ofdmrx_handle::SynSlot *s = &h->syn[h->syn_cur];
-	if (s->interp == interp && s->ch.size() == ch.size() && !std::memcmp(s->ch.data(), ch.data(), ch.size() * sizeof(SynthChannel))) {
+	if (s->p == p && s->q == q && s->ch.size() == ch.size() && !std::memcmp(s->ch.data(), ch.data(), ch.size() * sizeof(SynthChannel))) {
 		*out = s;
 		return 0;
 	}
@@ -19,10 +33,14 @@ static int synthesize_setup(ofdmrx_handle *h, int interp, const std::vector<Synt
 		HIP_OK(hipEventSynchronize(s->done));
 	else
 		HIP_OK(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
-	s->interp = 0;
+	s->p = s->q = 0;
 	s->ch = ch;
-	s->taps.resize((size_t)(24 * interp + 1));
-	channelize_taps(interp, s->taps.data());
+	if (q == 1) {
+		s->taps.resize((size_t)(24 * p + 1));
+		channelize_taps(p, s->taps.data());
+	} else {
+		resynthesize_taps(p, q, s->taps);
+	}
 	const size_t ch_bytes = ch.size() * sizeof(SynthChannel), tap_bytes = s->taps.size() * sizeof(float);
 	const int r = s->dev.ensure(ch_bytes + tap_bytes);
 	if (r)
@@ -30,7 +48,8 @@ static int synthesize_setup(ofdmrx_handle *h, int interp, const std::vector<Synt
 	HIP_OK(hipMemcpyAsync(s->dev.p, s->ch.data(), ch_bytes, hipMemcpyHostToDevice, h->stream));
 	HIP_OK(hipMemcpyAsync((char *)s->dev.p + ch_bytes, s->taps.data(), tap_bytes, hipMemcpyHostToDevice, h->stream));
 	HIP_OK(hipEventRecord(s->done, h->stream));                   // (a failed launch below still leaves the slot waitable)
-	s->interp = interp;
+	s->p = p;
+	s->q = q;
 	*out = s;
 	return 0;
 }
@@ -70,7 +89,7 @@ extern "C" int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in
 	if (h->busy_live())
 		return OFDMRX_E_ARG;
 	const ofdmrx_handle::SynSlot *slot = nullptr;
-	int r = synthesize_setup(h, interp, ch, &slot);
+	int r = synthesize_setup(h, interp, 1, ch, &slot);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -88,6 +107,70 @@ extern "C" int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in
 	a.n_out = (long long)n_out;
 	a.out = d_out;
 	launch_synthesize(h->stream, a);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipEventRecord(slot->done, h->stream));
+	return 0;
+}
+
+// ---- the synthesizer at a rational interpolation p / q (k_resynthesize.hip)
+extern "C" int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
+	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out, void *d_out,
+	int out_format)
+{
+	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	if (q == 1)                                                   // the integer synthesizer: the same bytes by construction
+		return ofdmrx_util_synthesize(h, d_in, in_format, in_stride, n_in, p, centre_hz, start, gain, n_channels, out_first, n_out, d_out, out_format);
+	if (!h || !d_in || !d_out || !centre_hz || !start || !gain || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
+		return OFDMRX_E_ARG;
+	if ((in_format != OFDMRX_FMT_S16 && in_format != OFDMRX_FMT_F32) || (out_format != OFDMRX_FMT_S16 && out_format != OFDMRX_FMT_F32) ||
+		in_stride < n_in || out_first < 0)
+		return OFDMRX_E_ARG;
+	if (out_first > FAR || in_stride > (size_t)FAR / 65536 || n_out > (size_t)resynthesize_max_outputs())   // (n_in <= in_stride; the launch holds 2^41 - 1024 outputs)
+		return OFDMRX_E_ARG;
+	const size_t in_unit = 2 * sample_bytes(in_format), out_unit = 2 * sample_bytes(out_format);
+	if ((size_t)d_in % in_unit || (size_t)d_out % out_unit)
+		return OFDMRX_E_ARG;
+	{
+		const char *a = (const char *)d_in, *b = (const char *)d_out;
+		const size_t in_bytes = ((n_channels - 1) * in_stride + n_in) * in_unit;
+		if (a < b + n_out * out_unit && b < a + in_bytes)
+			return OFDMRX_E_ARG;
+	}
+	const double d = (double)p / (double)q, rw = (double)h->rate * (double)p / (double)q;
+	std::vector<SynthChannel> ch(n_channels);
+	for (size_t c = 0; c < n_channels; ++c) {
+		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw || !std::isfinite(gain[c]) || start[c] < 0 || start[c] > FAR)
+			return OFDMRX_E_ARG;
+		ch[c].start = start[c];
+		ch[c].inc = channelize_inc(centre_hz[c], rw);
+		ch[c].gain = (float)(d * (double)gain[c]);
+		if (!std::isfinite(ch[c].gain))                              // (p / q x gain beyond fp32: times a zero it would not be +0)
+			return OFDMRX_E_ARG;
+	}
+	if (h->busy_live())
+		return OFDMRX_E_ARG;
+	const ofdmrx_handle::SynSlot *slot = nullptr;
+	int r = synthesize_setup(h, p, q, ch, &slot);
+	if (r)
+		return r;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	ResynthesizeArgs a{};
+	a.in = d_in;
+	a.in_fmt = in_format;
+	a.out_fmt = out_format;
+	a.p = p;
+	a.q = q;
+	a.in_stride = (long long)in_stride;
+	a.n_in = (long long)n_in;
+	a.ch = slot->dev.as<SynthChannel>();
+	a.taps = (const float *)((const char *)slot->dev.p + n_channels * sizeof(SynthChannel));
+	a.n_channels = (int)n_channels;
+	a.out_first = out_first;
+	a.n_out = (long long)n_out;
+	a.out = d_out;
+	launch_resynthesize(h->stream, a);
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(slot->done, h->stream));
 	return 0;

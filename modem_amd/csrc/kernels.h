@@ -408,6 +408,25 @@ struct SynthesizeArgs {
 void launch_synthesize(hipStream_t s, const SynthesizeArgs &a);
 long long synthesize_max_outputs();
 
+// ---- the wideband synthesizer at a rational interpolation p / q in lowest terms (k_resynthesize.hip): 2 <= q <= 16,
+// 2 <= p / q <= 32.  in, ch, out: as SynthesizeArgs (a channel's gain is p / q x the caller's).  taps: device, 16-byte aligned,
+// [p][RSY_ROW] - row b holds G[b + a p], a = 0 .. 24, of the sequence G[tn] = H[tn mod q][tn div q], tn = 0 .. 24 p, that
+// rechannelize_taps' table [q][T] spells, zeros behind it (resynthesize_taps writes it).
+constexpr int RSY_ROW = 28;
+struct ResynthesizeArgs {
+	const void *in;
+	int in_fmt, out_fmt;           // OFDMRX_FMT_S16 or OFDMRX_FMT_F32
+	int p, q;
+	long long in_stride, n_in;     // sample frames
+	const SynthChannel *ch;        // device, [n_channels]
+	const float *taps;             // device, [p][RSY_ROW]
+	int n_channels;
+	long long out_first, n_out;    // n_out <= resynthesize_max_outputs()
+	void *out;
+};
+void launch_resynthesize(hipStream_t s, const ResynthesizeArgs &a);
+long long resynthesize_max_outputs();
+
 // ---- the wideband survey (k_survey.hip): a Welch power spectrum of one wideband capture, n_rows rows of nfft bins.
 // in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); the caller has checked that every position the
 // rows need is there.  Row r (row_first .. row_first + n_rows - 1) averages the segs_per_row segments from r segs_per_row on, in

@@ -2,8 +2,10 @@
 // wideband I/Q capture (ofdmrx_util_synthesize).  Every IN.wav is an analytic signal (2 channels) of 8 or 16
 // bits at one common supported rate; it is placed at CENTRE_HZ, START wideband samples into the capture, at GAIN_DB.  OUT.wav has 2
 // channels of 16 bits at INTERP x that rate and is as long as the last channel's support: what `decode_stream --wideband INTERP
-// c1,c2,.. OUTROOT OUT.wav` reads.  Exit status 0, or 1 on argument, WAV or library errors.
-#include "wav_read.h"
+// c1,c2,.. OUTROOT OUT.wav` reads.  INTERP may be a ratio P/Q - it is one when it holds a '/' (Q <= 16,
+// 2 <= P / Q <= 32; ofdmrx_util_synthesize_ratio): OUT.wav is then at that rate x P / Q, which must be an integer.
+// Exit status 0, or 1 on argument, WAV or library errors.
+#include "survey_cli.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -20,10 +22,10 @@ int main(int argc, char **argv)
 		return 1;
 	}
 	const char *output_name = argv[1];
-	const int interp = std::atoi(argv[2]);
+	const Decimation interp(argv[2]);
 	const size_t C = (size_t)(argc - 3);
-	if (interp < 2 || interp > 32 || C > 65535) {
-		std::fprintf(stderr, "A wideband capture takes an interpolation of 2 .. 32 and 1 .. 65535 channels.\n");
+	if (!interp.valid() || C > 65535) {
+		std::fprintf(stderr, "A wideband capture takes an interpolation of 2 .. 32 (a ratio P/Q: Q <= 16) and 1 .. 65535 channels.\n");
 		return 1;
 	}
 	std::vector<double> centre(C);
@@ -73,12 +75,16 @@ int main(int argc, char **argv)
 		std::fprintf(stderr, "Unsupported sample rate.\n");
 		return 1;
 	}
+	const long long wide_num = (long long)rate * interp.p;
+	if (wide_num % interp.q) {
+		std::fprintf(stderr, "The capture's rate %d x %d / %d is not an integer.\n", rate, interp.p, interp.q);
+		return 1;
+	}
 	if (ofdmrx_abi_version() != OFDMRX_ABI_VERSION || ofdmrx_abi_minor() < 9) {
 		std::fprintf(stderr, "libofdmrx: ABI %d.%d, this program needs %d.9\n", ofdmrx_abi_version(), ofdmrx_abi_minor(), OFDMRX_ABI_VERSION);
 		return 1;
 	}
 	// every row as fp32 I/Q, scaled as the decoder scales its input; the rows share the longest length, zeros behind a shorter one
-	const long long T = 24LL * interp + 1;
 	long long n_out = 0;
 	std::vector<float> rows(C * longest * 2, 0.f);
 	for (size_t c = 0; c < C; ++c) {
@@ -86,7 +92,7 @@ int main(int argc, char **argv)
 		float *d = rows.data() + c * longest * 2;
 		for (size_t i = 0; i < 2 * w.frames; ++i)
 			d[i] = w.bits == 16 ? (float)((const int16_t *)w.pcm.data())[i] / 32767.f : (float)((int)w.pcm[i] - 128) / 127.f;
-		n_out = std::max(n_out, start[c] + ((long long)w.frames - 1) * interp + T);
+		n_out = std::max(n_out, start[c] + (((long long)w.frames - 1 + 24) * interp.p) / interp.q + 1);
 		wavs[c].pcm = std::vector<uint8_t>();
 	}
 	const unsigned long long bytes = (unsigned long long)n_out * 4;
@@ -112,7 +118,9 @@ int main(int argc, char **argv)
 	e = e == hipSuccess ? hipMalloc(&d_out, (size_t)bytes) : e;
 	e = e == hipSuccess ? hipMemcpy(d_in, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice) : e;
 	if (e == hipSuccess) {
-		r = ofdmrx_util_synthesize(h, d_in, OFDMRX_FMT_F32, longest, longest, interp, centre.data(), start.data(), gain.data(), C, 0, (size_t)n_out,
+		r = interp.ratio ? ofdmrx_util_synthesize_ratio(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, interp.q, centre.data(), start.data(),
+			gain.data(), C, 0, (size_t)n_out, d_out, OFDMRX_FMT_S16)
+			: ofdmrx_util_synthesize(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, centre.data(), start.data(), gain.data(), C, 0, (size_t)n_out,
 			d_out, OFDMRX_FMT_S16);
 		r = r ? r : ofdmrx_synchronize(h);
 		if (r)
@@ -133,7 +141,7 @@ int main(int argc, char **argv)
 		return 1;
 	}
 	uint8_t hd[44];
-	const uint32_t wide = (uint32_t)rate * (uint32_t)interp;
+	const uint32_t wide = (uint32_t)(wide_num / interp.q);
 	std::memcpy(hd, "RIFF", 4); put32(hd + 4, (uint32_t)(36 + bytes)); std::memcpy(hd + 8, "WAVEfmt ", 8);
 	put32(hd + 16, 16); put16(hd + 20, 1); put16(hd + 22, 2); put32(hd + 24, wide);
 	put32(hd + 28, wide * 4); put16(hd + 32, 4); put16(hd + 34, 16);

@@ -37,6 +37,7 @@ EXPORTS = [
     "ofdmrx_bank_begin_wideband", "ofdmrx_bank_push_wideband", "ofdmrx_util_synthesize",
     "ofdmrx_util_survey_window", "ofdmrx_util_survey", "ofdmrx_util_find_bands",
     "ofdmrx_util_channelize_ratio_taps", "ofdmrx_util_channelize_ratio", "ofdmrx_bank_begin_wideband_ratio",
+    "ofdmrx_util_synthesize_ratio",
 ]
 
 
@@ -128,6 +129,17 @@ def channelize_ratio_taps(p, q):
     if q > 16 or load_library().ofdmrx_util_channelize_ratio_taps(p, q, _ptr(taps)) != T:
         raise OfdmRxError("channelize_ratio_taps: the reduced q must be 1 .. 16 and p / q 2 .. 32")
     return taps
+
+
+def synthesize_support(n_in, interp):
+    """the length of a channel's support in the wideband synthesizer's capture, counted from its start: ((n_in - 1 + 24) p) // q + 1
+    for interp p / q - an int, a pair (p, q) or a fractions.Fraction (DESIGN.md sections 4.15 and 4.18)"""
+    p, q = _ratio(interp)
+    q = 1 if q is None else q
+    if p <= 0 or q <= 0 or int(n_in) < 1:
+        raise OfdmRxError("synthesize_support: n_in, p and q must be positive")
+    g = math.gcd(p, q)
+    return ((int(n_in) - 1 + 24) * (p // g)) // (q // g) + 1
 
 
 SURVEY_NFFT = (1280, 2560, 5120)
@@ -279,6 +291,8 @@ def load_library():
                                          C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_util_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
+    L.ofdmrx_util_synthesize_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
     L.ofdmrx_util_survey_window.argtypes = [C.c_int, C.c_void_p]
     L.ofdmrx_util_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_longlong, C.c_size_t,
                                      C.c_void_p]
@@ -661,12 +675,17 @@ class Receiver:
         """the wideband synthesizer on device buffers (ints): channel c's n_in sample frames (interleaved I/Q of in_fmt, S16 or F32) lie
         at d_in + c in_stride sample frames; it is placed at centres_hz[c], starts[c] wideband samples in, at gains[c], and the sum's
         positions out_first .. out_first + n_out - 1 at interp x the handle's rate go to d_out as out_fmt (S16 or F32); asynchronous on
-        the handle's stream"""
+        the handle's stream.  interp: an int, or a ratio - a pair (p, q) or a fractions.Fraction (section 4.18)"""
         f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
         s = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
         g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
         if not (f.size == s.size == g.size):
             raise OfdmRxError("synthesize: centres_hz, starts and gains must have one length")
+        interp, q = _ratio(interp)
+        if q is not None:
+            self._check(self._lib.ofdmrx_util_synthesize_ratio(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, interp, q,
+                                                               _ptr(f), _ptr(s), _ptr(g), f.size, out_first, n_out, d_out, out_fmt))
+            return
         self._check(self._lib.ofdmrx_util_synthesize(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, interp, _ptr(f), _ptr(s),
                                                      _ptr(g), f.size, out_first, n_out, d_out, out_fmt))
 

@@ -5,7 +5,8 @@ with one neighbour `spacing` Hz below it and one above, both `level` dB above th
   started 7 and 13 wideband samples late) -> awgn_tile on the capture -> channelize at the victim's centre -> decode_streams_device.
 A victim frame counts as received when a record of status 0 carries its payload.  For every spacing and level it prints one JSON line
   {"spacing_hz", "level_db", "frames", "fer", "ber", "records"}   (ber: over the frames that gave a record where they were sent)
-and at the end one line with all of them.  The victim's gain is chosen so that the three signals together stay inside int16.
+and at the end one line with all of them.  --ratio P/Q runs the same loop at a rational capture rate (section 4.18: synthesize and
+channelize take the ratio, the capture is at rate x P / Q); without it nothing changes.  The victim's gain is chosen so that the three signals together stay inside int16.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU."""
 import argparse
 import json
@@ -19,7 +20,8 @@ sys.path.insert(0, ROOT)
 
 def point(rx, torch, np, M, args, spacing, level, seed):
     dev = torch.device("cuda", 0)
-    D, N, rate = args.interp, args.frames, rx.sample_rate
+    N = args.frames
+    D = args.interp if args.ratio is None else args.ratio               # an int, or the pair (p, q)
     spf = rx.tx_frame_samples(args.mode)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -29,12 +31,12 @@ def point(rx, torch, np, M, args, spacing, level, seed):
     ratio = 10.0 ** (level / 20.0)
     g_v = 0.9 / (1.0 + 2.0 * ratio)
     starts = np.array([0, 7, 13], np.int64)
-    W = int(starts.max()) + (N * spf - 1) * D + 24 * D + 1
+    W = int(starts.max()) + M.synthesize_support(N * spf, D)
     d_cap = torch.empty((W, 2), dtype=torch.int16, device=dev)
     rx.synthesize(d_pcm.data_ptr(), M.FMT_S16, N * spf, D, [0.0, -spacing, spacing], starts, [g_v, g_v * ratio, g_v * ratio], 0, W,
                   d_cap.data_ptr(), M.FMT_S16)
     rx.awgn_tile(d_cap.data_ptr(), 1, d_cap.data_ptr(), 1, W, args.noise_db, seed, 0)
-    n_rows = -(-W // D)
+    n_rows = -(-W // D) if args.ratio is None else -(-W * D[1] // D[0])
     d_row = torch.empty((1, n_rows, 2), dtype=torch.float32, device=dev)
     rx.channelize(d_cap.data_ptr(), M.FMT_S16, 0, W, D, [0.0], 0, n_rows, d_row.data_ptr())
     cap = 4 * N + 8
@@ -49,7 +51,7 @@ def point(rx, torch, np, M, args, spacing, level, seed):
     good = [bool(((out == pay[i]).all(axis=1) & (res["status"] == 0)).any()) for i in range(N)]
     bits = errs = 0
     for i in range(N):                                                # the record nearest to where frame i was sent, if one is near
-        at = i * spf + 24
+        at = i * spf + 24                                              # (the victim starts at 0: its delay is 24 at any ratio)
         near = [j for j in range(k) if 0 <= int(res["sc_start"][j]) - at < spf and res["status"][j] in (0, 6)]
         if near:
             j = near[0]
@@ -74,13 +76,14 @@ def child(args):
                 rows.append(r)
     finally:
         rx.close()
-    print(json.dumps({"tool": "adjacent_channel", "interp": args.interp, "rate": args.rate, "mode": args.mode, "noise_db": args.noise_db, "rows": rows}),
+    print(json.dumps({"tool": "adjacent_channel", "interp": args.interp if args.ratio is None else "%d/%d" % args.ratio, "rate": args.rate, "mode": args.mode, "noise_db": args.noise_db, "rows": rows}),
           flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--interp", type=int, default=6)
+    ap.add_argument("--ratio", default=None, help="P/Q: a rational capture rate in place of --interp (Q <= 16, 2 <= P / Q <= 32)")
     ap.add_argument("--rate", type=int, default=8000)
     ap.add_argument("--mode", type=int, default=6)
     ap.add_argument("--frames", type=int, default=16, help="victim frames per point")
@@ -90,11 +93,18 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds the GPU step may take")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
+    ratio = args.ratio
+    if ratio is not None:
+        try:
+            p, q = (int(v) for v in ratio.split("/"))
+        except ValueError:
+            ap.error("--ratio takes P/Q")
+        args.ratio = (p, q)
     if args.child:
         return child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--interp", str(args.interp), "--rate", str(args.rate), "--mode", str(args.mode),
            "--frames", str(args.frames), "--noise-db", str(args.noise_db), "--spacings"] + [str(s) for s in args.spacings] + ["--levels"] + [
-               str(v) for v in args.levels]
+               str(v) for v in args.levels] + ([] if ratio is None else ["--ratio", ratio])
     try:
         return subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:

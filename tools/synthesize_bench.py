@@ -8,6 +8,8 @@ At D = 6 and D = 24, with hipEvents on the handle's stream, median of `--reps` a
   ms, input + output GB/s, real multiply-adds of the tap sums per second,
   beside k_awgn_tile on a buffer of the output's bytes and beside the arithmetic floor C_met n_out 25 x 2 FMAs at DESIGN.md section
   6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs) - C_met the channels a tile meets - and which of the two is nearer.
+--ratio P/Q times the ratio synthesizer (ofdmrx_util_synthesize_ratio, k_resynthesize.hip; section 4.18) in place of those two, and
+beside it k_synthesize at the neighbouring integer D = round(P / Q) on the same input bytes, against the same yardsticks.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import json
@@ -46,14 +48,21 @@ def child(args):
         return statistics.median(ms)
 
     rows = []
-    for D in (6, 24):
+    interps = (6, 24)
+    if args.ratio is not None:
+        p, q = (int(v) for v in args.ratio.split("/"))
+        interps = ((p, q), min(32, max(2, int(round(p / q)))))
+    size_by = interps[0][0] / interps[0][1] if args.ratio is not None else None   # both take the ratio's input rows
+    for D in interps:
         for N, layout in ((1, "overlapping"), (16, "overlapping"), (256, "overlapping"), (256, "end to end")):
-            n_in = args.samples // D if layout == "overlapping" else args.samples // (16 * D)
-            reach = (n_in - 1) * D + 24 * D + 1
+            Dr = D[0] / D[1] if isinstance(D, tuple) else float(D)
+            Ds = Dr if size_by is None else size_by
+            n_in = int(args.samples / Ds) if layout == "overlapping" else int(args.samples / (16 * Ds))
+            reach = modem_amd.synthesize_support(n_in, D)
             step = 0 if layout == "overlapping" else reach
-            starts = np.arange(N, dtype=np.int64) * step + np.arange(N) % D
+            starts = np.arange(N, dtype=np.int64) * step + np.arange(N) % (D[0] if isinstance(D, tuple) else D)
             n_out = int(starts[-1]) + reach
-            f = np.linspace(-0.45, 0.45, N) * D * 8000.0 + 0.123
+            f = np.linspace(-0.45, 0.45, N) * Dr * 8000.0 + 0.123
             g = np.full(N, 0.5 / (N if layout == "overlapping" else 1), np.float32)
             d_in = torch.randint(-20000, 20000, (N, n_in, 2), dtype=torch.int16, device=dev, generator=gen)
             d_out = torch.empty((n_out, 2), dtype=torch.int16, device=dev)
@@ -66,14 +75,14 @@ def child(args):
             met = N if layout == "overlapping" else 1
             floor = met * n_out * 25 * 2 / 64.0 * FMA_NS * 1e-6 / SIMDS
             nbytes = N * n_in * 4 + n_out * 4
-            rows.append(dict(interp=D, channels=N, layout=layout, n_out=n_out, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1),
+            rows.append(dict(interp="%d/%d" % D if isinstance(D, tuple) else D, channels=N, layout=layout, n_out=n_out, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1),
                              gmac_per_s=round(met * n_out * 50 / ms / 1e6, 1), awgn_tile_ms=round(awgn, 4), fma_floor_ms=round(floor, 4),
                              nearer="arithmetic" if floor > awgn else "memory", over_bound=round(ms / max(floor, awgn), 2)))
             del d_in, d_out, d_a, d_b
     rx.close()
     print("interp channels layout        n_out      ms    GB/s  GMAC/s  awgn_tile ms  FMA floor ms  nearer bound  time / bound")
     for r in rows:
-        print("%6d %8d %-12s %8d %8.4f %7.1f %7.1f %13.4f %13.4f  %-12s %6.2f" % (
+        print("%6s %8d %-12s %8d %8.4f %7.1f %7.1f %13.4f %13.4f  %-12s %6.2f" % (
             r["interp"], r["channels"], r["layout"], r["n_out"], r["ms"], r["gb_per_s"], r["gmac_per_s"], r["awgn_tile_ms"], r["fma_floor_ms"],
             r["nearer"], r["over_bound"]))
     print(json.dumps({"tool": "synthesize_bench", "samples": args.samples, "rows": rows}), flush=True)
@@ -82,6 +91,7 @@ def child(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=1 << 20, help="wideband samples an overlapping channel spans")
+    ap.add_argument("--ratio", default=None, help="P/Q: the ratio synthesizer beside k_synthesize at round(P / Q)")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=240, help="seconds the GPU step may take")
@@ -90,6 +100,8 @@ def main():
     if args.child:
         return child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    if args.ratio is not None:
+        cmd += ["--ratio", args.ratio]
     try:
         return subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
