@@ -335,38 +335,20 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 			if (r)
 				return r;
 			HIP_OK(hipMemcpyAsync(b.stage.p, b.stage_h.data(), b.stage_h.size(), hipMemcpyHostToDevice, s));
-			if (b.q > 1) {
-				RechannelizeArgs a{};
-				a.in = b.stage.p;
-				a.fmt = b.wfmt;
-				a.p = b.p;
-				a.q = b.q;
-				a.in_first = b.wfed - tail;
-				a.n_in = tail + (long long)n_wide;
-				a.taps = h->rcz_taps.as<float>();
-				a.inc = h->rcz_inc.as<unsigned>();
-				a.n_channels = (int)C;
-				a.out_first = o0;
-				a.n_out = o1 - o0;
-				a.dst = dpar + P_PL_DST * P;
-				launch_rechannelize(s, a);
-			} else {
-				ChannelizeArgs a{};
-				a.in = b.stage.p;
-				a.fmt = b.wfmt;
-				a.decim = b.p;
-				a.in_first = b.wfed - tail;
-				a.n_in = tail + (long long)n_wide;
-				a.taps = h->chz_taps.as<float>();
-				a.inc = h->chz_inc.as<unsigned>();
-				a.n_channels = (int)C;
-				a.out_first = o0;
-				a.n_out = o1 - o0;
-				a.out = nullptr;
-				a.out_stride = 0;
-				a.dst = dpar + P_PL_DST * P;
-				launch_channelize(s, a);
-			}
+			ChannelizeArgs a{};
+			a.in = b.stage.p;
+			a.fmt = b.wfmt;
+			a.p = b.p;
+			a.q = b.q;
+			a.in_first = b.wfed - tail;
+			a.n_in = tail + (long long)n_wide;
+			a.taps = h->chz_taps.as<float>();
+			a.inc = h->chz_inc.as<unsigned>();
+			a.n_channels = (int)C;
+			a.out_first = o0;
+			a.n_out = o1 - o0;
+			a.dst = dpar + P_PL_DST * P;
+			launch_channelize(s, a);
 			b.ops += 2;
 		}
 		const size_t keep = std::min(b.stage_h.size(), (size_t)(T - 1) * wunit);
@@ -730,37 +712,10 @@ extern "C" int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t st
 	return 0;
 }
 
-// ---- a wideband bank: one wideband capture in, every channel made from it on the device
-extern "C" int ofdmrx_bank_begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int decim, int fmt)
+// ---- a wideband bank: one wideband capture in, every channel made from it on the device at the reduced
+// decimation p / q (q = 1: the integer decimation p); push, end and the queries serve every ratio alike
+static int begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt)
 {
-	if (!h || !centre_hz || decim < 2 || decim > 32 || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || n_channels < 1 || n_channels > 65535)
-		return OFDMRX_E_ARG;
-	if (h->bank)
-		return OFDMRX_E_ARG;
-	for (size_t c = 0; c < n_channels; ++c)
-		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * (double)decim * (double)h->rate)
-			return OFDMRX_E_ARG;
-	int r = begin(h, n_channels, OFDMRX_FMT_F32, 2, false);
-	if (r)
-		return r;
-	if ((r = channelize_setup(h, decim, centre_hz, n_channels))) {
-		bank_free(h);
-		return r;
-	}
-	h->bank->wide = true;
-	h->bank->p = decim;
-	h->bank->q = 1;
-	h->bank->wfmt = fmt;
-	return 0;
-}
-
-// ... at a rational decimation p / q: push, end and the queries serve it as they serve the integer one
-extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt)
-{
-	if (rechannelize_ratio(p, q))
-		return OFDMRX_E_ARG;
-	if (q == 1)
-		return ofdmrx_bank_begin_wideband(h, n_channels, centre_hz, p, fmt);
 	if (!h || !centre_hz || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || n_channels < 1 || n_channels > 65535)
 		return OFDMRX_E_ARG;
 	if (h->bank)
@@ -771,7 +726,7 @@ extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_chann
 	int r = begin(h, n_channels, OFDMRX_FMT_F32, 2, false);
 	if (r)
 		return r;
-	if ((r = rechannelize_setup(h, p, q, centre_hz, n_channels))) {
+	if ((r = channelize_setup(h, p, q, centre_hz, n_channels))) {
 		bank_free(h);
 		return r;
 	}
@@ -780,6 +735,20 @@ extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_chann
 	h->bank->q = q;
 	h->bank->wfmt = fmt;
 	return 0;
+}
+
+extern "C" int ofdmrx_bank_begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int decim, int fmt)
+{
+	if (decim < 2 || decim > 32)
+		return OFDMRX_E_ARG;
+	return begin_wideband(h, n_channels, centre_hz, decim, 1, fmt);
+}
+
+extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt)
+{
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	return begin_wideband(h, n_channels, centre_hz, p, q, fmt);
 }
 
 extern "C" int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, size_t n_wide, int end_all, size_t max_records, uint8_t *payload_out,

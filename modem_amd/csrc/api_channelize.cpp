@@ -1,6 +1,7 @@
-// api_channelize.cpp -- the wideband front end behind include/ofdmrx.h: the taps, the phase increments,
-// ofdmrx_util_channelize; behind them the same at a rational decimation p / q (section 4.17): ofdmrx_util_channelize_ratio_taps,
-// ofdmrx_util_channelize_ratio.  Everything the kernels rely on is checked here, before any device call.
+// api_channelize.cpp -- the wideband front end behind include/ofdmrx.h (DESIGN.md sections 4.14 and 4.17): the taps, the phase
+// increments, and one host path for every decimation p / q - ofdmrx_util_channelize is p = decim, q = 1 of what
+// ofdmrx_util_channelize_ratio does, and launch_channelize picks the kernel by q.  Everything the kernels rely on is checked here,
+// before any device call.
 #include "api_internal.h"
 
 namespace rx {
@@ -28,97 +29,7 @@ unsigned channelize_inc(double centre_hz, double rw)
 	return (unsigned)(unsigned long long)std::llrint(centre_hz * 4294967296.0 / rw);
 }
 
-}  // namespace rx
-
-// the taps of `decim` and the increments of the centres on the device.  What is there already stays (a bank's pushes, a capture cut
-// into blocks); anything else waits for the stream first, since a kernel enqueued earlier may still read the old values
-int channelize_setup(ofdmrx_handle *h, int decim, const double *centre_hz, size_t n_channels)
-{
-	const double rw = (double)decim * (double)h->rate;
-	std::vector<unsigned> inc(n_channels);
-	for (size_t c = 0; c < n_channels; ++c) {
-		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw)
-			return OFDMRX_E_ARG;
-		inc[c] = channelize_inc(centre_hz[c], rw);
-	}
-	if (decim == h->chz_decim && inc == h->chz_inc_h)
-		return 0;
-	HIP_OK(hipSetDevice(h->cfg.device));
-	HIP_OK(hipStreamSynchronize(h->stream));
-	h->chz_decim = 0;
-	h->chz_taps_h.resize((size_t)(24 * decim + 1));
-	channelize_taps(decim, h->chz_taps_h.data());
-	h->chz_inc_h = inc;
-	int r = h->chz_taps.ensure(h->chz_taps_h.size() * sizeof(float));
-	r = r ? r : h->chz_inc.ensure(n_channels * sizeof(unsigned));
-	if (r)
-		return r;
-	HIP_OK(hipMemcpyAsync(h->chz_taps.p, h->chz_taps_h.data(), h->chz_taps_h.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-	HIP_OK(hipMemcpyAsync(h->chz_inc.p, h->chz_inc_h.data(), n_channels * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-	h->chz_decim = decim;
-	return 0;
-}
-
-extern "C" int ofdmrx_util_channelize_taps(int decim, float *taps)
-{
-	if (decim < 2 || decim > 32 || !taps)
-		return OFDMRX_E_ARG;
-	return channelize_taps(decim, taps);
-}
-
-extern "C" int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
-	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
-{
-	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
-	if (!h || !d_in || !d_out || !centre_hz || !n_in || !n_out || n_channels < 1 || n_channels > 65535 || decim < 2 || decim > 32)
-		return OFDMRX_E_ARG;
-	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || out_first < 0 || out_stride < n_out)
-		return OFDMRX_E_ARG;
-	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)channelize_max_outputs() || out_stride > (size_t)FAR / 65536)
-		return OFDMRX_E_ARG;
-	const size_t unit = 2 * sample_bytes(sample_format);
-	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))
-		return OFDMRX_E_ARG;
-	const long long D = decim, T = 24 * D + 1;
-	if ((in_first > 0 && out_first * D - (T - 1) < in_first) || (out_first + (long long)n_out - 1) * D > in_first + (long long)n_in - 1)
-		return OFDMRX_E_ARG;                                      // a position the outputs need is not in the buffer
-	{
-		const char *a = (const char *)d_in, *b = (const char *)d_out;
-		const size_t out_bytes = ((n_channels - 1) * out_stride + n_out) * sizeof(float2);
-		if (a < b + out_bytes && b < a + n_in * unit)
-			return OFDMRX_E_ARG;
-	}
-	for (size_t c = 0; c < n_channels; ++c)
-		if (!std::isfinite(centre_hz[c]))
-			return OFDMRX_E_ARG;
-	if (h->busy_live())                                           // (an open wideband bank owns the taps and increments on the device)
-		return OFDMRX_E_ARG;
-	int r = channelize_setup(h, decim, centre_hz, n_channels);
-	if (r)
-		return r;
-	HIP_OK(hipSetDevice(h->cfg.device));
-	ChannelizeArgs a{};
-	a.in = d_in;
-	a.fmt = sample_format;
-	a.decim = decim;
-	a.in_first = in_first;
-	a.n_in = (long long)n_in;
-	a.taps = h->chz_taps.as<float>();
-	a.inc = h->chz_inc.as<unsigned>();
-	a.n_channels = (int)n_channels;
-	a.out_first = out_first;
-	a.n_out = (long long)n_out;
-	a.out = d_out;
-	a.out_stride = (long long)out_stride;
-	a.dst = nullptr;
-	launch_channelize(h->stream, a);
-	HIP_OK(hipGetLastError());
-	return 0;
-}
-
-// ---- the front end at a rational decimation p / q (k_rechannelize.hip)
-namespace rx {
-
+// the same at a rational decimation p / q, one row of T = 24 p div q + 1 taps per phase r = 0 .. q - 1:
 // h_r[j] = g(j + r / q - K), K = 12 p / q, g(t) = sinc(0.75 t / D) (0.42 + 0.5 cos(pi t / K) + 0.08 cos(2 pi t / K)) inside |t| <= K:
 // with the integer tn = j q + r - 12 p the time is t = tn / q, t / D = tn / p and t / K = tn / (12 p)
 int rechannelize_taps(int p, int q, float *taps)
@@ -166,9 +77,11 @@ int rechannelize_ratio(int &p, int &q)
 	return 0;
 }
 
-// as channelize_setup: what is on the device already stays, anything else waits for the stream first.  The device holds the taps
-// transposed, [T][q], as the kernel reads them
-int rechannelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels)
+// the taps of the reduced ratio p / q and the increments of the centres on the device.  What is there already stays (a bank's pushes,
+// a capture cut into blocks); anything else - other centres, another ratio, an integer decimation after a ratio - waits for the
+// stream first, since a kernel enqueued earlier may still read the old values.  The device holds the taps transposed, [T][q], as
+// k_rechannelize reads them; at q = 1 that is channelize_taps' own order, which k_channelize reads
+int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels)
 {
 	const double rw = (double)h->rate * (double)p / (double)q;
 	std::vector<unsigned> inc(n_channels);
@@ -177,28 +90,35 @@ int rechannelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, 
 			return OFDMRX_E_ARG;
 		inc[c] = channelize_inc(centre_hz[c], rw);
 	}
-	if (p == h->rcz_p && q == h->rcz_q && inc == h->rcz_inc_h)
+	if (p == h->chz_p && q == h->chz_q && inc == h->chz_inc_h)
 		return 0;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	HIP_OK(hipStreamSynchronize(h->stream));
-	h->rcz_p = h->rcz_q = 0;
+	h->chz_p = h->chz_q = 0;
 	const size_t T = (size_t)(24 * p / q + 1);
 	std::vector<float> rows((size_t)q * T);
 	rechannelize_taps(p, q, rows.data());
-	h->rcz_taps_h.resize(rows.size());
+	h->chz_taps_h.resize(rows.size());
 	for (size_t r = 0; r < (size_t)q; ++r)
 		for (size_t j = 0; j < T; ++j)
-			h->rcz_taps_h[j * (size_t)q + r] = rows[r * T + j];
-	h->rcz_inc_h = inc;
-	int r = h->rcz_taps.ensure(h->rcz_taps_h.size() * sizeof(float));
-	r = r ? r : h->rcz_inc.ensure(n_channels * sizeof(unsigned));
+			h->chz_taps_h[j * (size_t)q + r] = rows[r * T + j];
+	h->chz_inc_h = inc;
+	int r = h->chz_taps.ensure(h->chz_taps_h.size() * sizeof(float));
+	r = r ? r : h->chz_inc.ensure(n_channels * sizeof(unsigned));
 	if (r)
 		return r;
-	HIP_OK(hipMemcpyAsync(h->rcz_taps.p, h->rcz_taps_h.data(), h->rcz_taps_h.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-	HIP_OK(hipMemcpyAsync(h->rcz_inc.p, h->rcz_inc_h.data(), n_channels * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-	h->rcz_p = p;
-	h->rcz_q = q;
+	HIP_OK(hipMemcpyAsync(h->chz_taps.p, h->chz_taps_h.data(), h->chz_taps_h.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+	HIP_OK(hipMemcpyAsync(h->chz_inc.p, h->chz_inc_h.data(), n_channels * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+	h->chz_p = p;
+	h->chz_q = q;
 	return 0;
+}
+
+extern "C" int ofdmrx_util_channelize_taps(int decim, float *taps)
+{
+	if (decim < 2 || decim > 32 || !taps)
+		return OFDMRX_E_ARG;
+	return channelize_taps(decim, taps);
 }
 
 extern "C" int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps)
@@ -208,19 +128,16 @@ extern "C" int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps)
 	return rechannelize_taps(p, q, taps);
 }
 
-extern "C" int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+// one call at the reduced ratio p / q (q = 1: the integer decimation p)
+static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
 {
 	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
-	if (rechannelize_ratio(p, q))
-		return OFDMRX_E_ARG;
-	if (q == 1)                                                   // the integer front end: the same bytes by construction
-		return ofdmrx_util_channelize(h, d_in, sample_format, in_first, n_in, p, centre_hz, n_channels, out_first, n_out, d_out, out_stride);
 	if (!h || !d_in || !d_out || !centre_hz || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
 		return OFDMRX_E_ARG;
 	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || out_first < 0 || out_stride < n_out)
 		return OFDMRX_E_ARG;
-	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)rechannelize_max_outputs() || out_stride > (size_t)FAR / 65536)
+	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)channelize_max_outputs(q) || out_stride > (size_t)FAR / 65536)
 		return OFDMRX_E_ARG;
 	const size_t unit = 2 * sample_bytes(sample_format);
 	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))
@@ -239,26 +156,42 @@ extern "C" int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, 
 			return OFDMRX_E_ARG;
 	if (h->busy_live())                                           // (an open wideband bank owns the taps and increments on the device)
 		return OFDMRX_E_ARG;
-	int r = rechannelize_setup(h, p, q, centre_hz, n_channels);
+	int r = channelize_setup(h, p, q, centre_hz, n_channels);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
-	RechannelizeArgs a{};
+	ChannelizeArgs a{};
 	a.in = d_in;
 	a.fmt = sample_format;
 	a.p = p;
 	a.q = q;
 	a.in_first = in_first;
 	a.n_in = (long long)n_in;
-	a.taps = h->rcz_taps.as<float>();
-	a.inc = h->rcz_inc.as<unsigned>();
+	a.taps = h->chz_taps.as<float>();
+	a.inc = h->chz_inc.as<unsigned>();
 	a.n_channels = (int)n_channels;
 	a.out_first = out_first;
 	a.n_out = (long long)n_out;
 	a.out = d_out;
 	a.out_stride = (long long)out_stride;
 	a.dst = nullptr;
-	launch_rechannelize(h->stream, a);
+	launch_channelize(h->stream, a);
 	HIP_OK(hipGetLastError());
 	return 0;
+}
+
+extern "C" int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+{
+	if (decim < 2 || decim > 32)
+		return OFDMRX_E_ARG;
+	return channelize_call(h, d_in, sample_format, in_first, n_in, decim, 1, centre_hz, n_channels, out_first, n_out, d_out, out_stride);
+}
+
+extern "C" int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+{
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	return channelize_call(h, d_in, sample_format, in_first, n_in, p, q, centre_hz, n_channels, out_first, n_out, d_out, out_stride);
 }

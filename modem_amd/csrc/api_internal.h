@@ -226,16 +226,12 @@ struct ofdmrx_handle {
 	long sxs_edge_cap = 0;    // every recording's share of the edge buffer (one recording: all of it)
 	struct ofdmrx_bank *bank = nullptr;   // the open bank of live channels or - a bank of one - the open feed (api_bank.cpp): one per handle
 	bool busy_live() const { return bank != nullptr; }   // a handle with an open feed or bank decodes nothing else
-	// the wideband front end (api_channelize.cpp): the taps and phase increments on the device, and what they were made from
+	// the wideband front end (api_channelize.cpp): the taps [T][q] and the phase increments on the device, and what they were made
+	// from - the reduced ratio chz_p / chz_q (an integer decimation D is D / 1; 0 / 0: none) and the host copies the uploads read
 	DevBuf chz_taps, chz_inc;
-	int chz_decim = 0;
+	int chz_p = 0, chz_q = 0;
 	std::vector<float> chz_taps_h;
 	std::vector<unsigned> chz_inc_h;
-	// ... at a rational decimation: the taps [T][q] and the increments of the reduced ratio rcz_p / rcz_q
-	DevBuf rcz_taps, rcz_inc;
-	int rcz_p = 0, rcz_q = 0;
-	std::vector<float> rcz_taps_h;
-	std::vector<unsigned> rcz_inc_h;
 	// the wideband synthesizer (api_synthesize.cpp): a small ring of parameter sets - the channels' (start, inc, gain) and the taps
 	// behind them - so that a call with other parameters never writes what a launch still in flight reads: a slot is written again
 	// only after the event of its last launch
@@ -298,8 +294,7 @@ int finish_call(ofdmrx_handle *h, int r);                                       
 // channel q would lie at fb.samples + org[q] bytes and the channel has len[q] sample frames so far (kernels.h: WindowBatch)
 struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; const long long *org = nullptr; const long long *len = nullptr; };
 int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources &srcs);
-int channelize_setup(ofdmrx_handle *h, int decim, const double *centre_hz, size_t n_channels);   // api_channelize.cpp
 // p / q -> lowest terms; OFDMRX_E_ARG unless p, q > 0, the reduced q <= 16 and 2 <= p / q <= 32
-int rechannelize_ratio(int &p, int &q);
-int rechannelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels);   // (p / q reduced, q > 1)
+int rechannelize_ratio(int &p, int &q);                                                     // api_channelize.cpp
+int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels);   // (p / q reduced; q = 1: decimation p)
 void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank (or feed) and its windows go

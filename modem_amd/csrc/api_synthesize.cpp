@@ -1,6 +1,6 @@
-// api_synthesize.cpp -- the wideband synthesizer behind include/ofdmrx.h: ofdmrx_util_synthesize; behind it
-// the same at a rational interpolation p / q (section 4.18): ofdmrx_util_synthesize_ratio.
-// Everything the kernels rely on is checked here, before any device call.
+// api_synthesize.cpp -- the wideband synthesizer behind include/ofdmrx.h (DESIGN.md sections 4.15 and 4.18): one host path for every
+// interpolation p / q - ofdmrx_util_synthesize is p = interp, q = 1 of what ofdmrx_util_synthesize_ratio does, and
+// launch_synthesize picks the kernel by q.  Everything the kernels rely on is checked here, before any device call.
 #include "api_internal.h"
 
 // G[tn] = H[tn mod q][tn div q], tn = 0 .. 24 p, of rechannelize_taps' [q][T] -> rows b = 0 .. p - 1 of G[b + a p], a = 0 .. 24
@@ -54,80 +54,18 @@ static int synthesize_setup(ofdmrx_handle *h, int p, int q, const std::vector<Sy
 	return 0;
 }
 
-extern "C" int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
+// one call at the reduced ratio p / q (q = 1: the integer interpolation p)
+static int synthesize_call(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
 	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out, void *d_out,
 	int out_format)
 {
 	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
-	if (!h || !d_in || !d_out || !centre_hz || !start || !gain || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
-		return OFDMRX_E_ARG;
-	if (interp < 2 || interp > 32 || (in_format != OFDMRX_FMT_S16 && in_format != OFDMRX_FMT_F32) ||
-		(out_format != OFDMRX_FMT_S16 && out_format != OFDMRX_FMT_F32) || in_stride < n_in || out_first < 0)
-		return OFDMRX_E_ARG;
-	if (out_first > FAR || in_stride > (size_t)FAR / 65536 || n_out > (size_t)synthesize_max_outputs())   // (n_in <= in_stride; the launch holds 2^41 - 1024 outputs)
-		return OFDMRX_E_ARG;
-	const size_t in_unit = 2 * sample_bytes(in_format), out_unit = 2 * sample_bytes(out_format);
-	if ((size_t)d_in % in_unit || (size_t)d_out % out_unit)
-		return OFDMRX_E_ARG;
-	{
-		const char *a = (const char *)d_in, *b = (const char *)d_out;
-		const size_t in_bytes = ((n_channels - 1) * in_stride + n_in) * in_unit;
-		if (a < b + n_out * out_unit && b < a + in_bytes)
-			return OFDMRX_E_ARG;
-	}
-	const double rw = (double)interp * (double)h->rate;
-	std::vector<SynthChannel> ch(n_channels);
-	for (size_t c = 0; c < n_channels; ++c) {
-		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw || !std::isfinite(gain[c]) || start[c] < 0 || start[c] > FAR)
-			return OFDMRX_E_ARG;
-		ch[c].start = start[c];
-		ch[c].inc = channelize_inc(centre_hz[c], rw);
-		ch[c].gain = (float)((double)interp * (double)gain[c]);
-		if (!std::isfinite(ch[c].gain))                              // (interp x gain beyond fp32: times a zero it would not be +0)
-			return OFDMRX_E_ARG;
-	}
-	if (h->busy_live())
-		return OFDMRX_E_ARG;
-	const ofdmrx_handle::SynSlot *slot = nullptr;
-	int r = synthesize_setup(h, interp, 1, ch, &slot);
-	if (r)
-		return r;
-	HIP_OK(hipSetDevice(h->cfg.device));
-	SynthesizeArgs a{};
-	a.in = d_in;
-	a.in_fmt = in_format;
-	a.out_fmt = out_format;
-	a.interp = interp;
-	a.in_stride = (long long)in_stride;
-	a.n_in = (long long)n_in;
-	a.ch = slot->dev.as<SynthChannel>();
-	a.taps = (const float *)((const char *)slot->dev.p + n_channels * sizeof(SynthChannel));
-	a.n_channels = (int)n_channels;
-	a.out_first = out_first;
-	a.n_out = (long long)n_out;
-	a.out = d_out;
-	launch_synthesize(h->stream, a);
-	HIP_OK(hipGetLastError());
-	HIP_OK(hipEventRecord(slot->done, h->stream));
-	return 0;
-}
-
-// ---- the synthesizer at a rational interpolation p / q (k_resynthesize.hip)
-extern "C" int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
-	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out, void *d_out,
-	int out_format)
-{
-	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
-	if (rechannelize_ratio(p, q))
-		return OFDMRX_E_ARG;
-	if (q == 1)                                                   // the integer synthesizer: the same bytes by construction
-		return ofdmrx_util_synthesize(h, d_in, in_format, in_stride, n_in, p, centre_hz, start, gain, n_channels, out_first, n_out, d_out, out_format);
 	if (!h || !d_in || !d_out || !centre_hz || !start || !gain || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
 		return OFDMRX_E_ARG;
 	if ((in_format != OFDMRX_FMT_S16 && in_format != OFDMRX_FMT_F32) || (out_format != OFDMRX_FMT_S16 && out_format != OFDMRX_FMT_F32) ||
 		in_stride < n_in || out_first < 0)
 		return OFDMRX_E_ARG;
-	if (out_first > FAR || in_stride > (size_t)FAR / 65536 || n_out > (size_t)resynthesize_max_outputs())   // (n_in <= in_stride; the launch holds 2^41 - 1024 outputs)
+	if (out_first > FAR || in_stride > (size_t)FAR / 65536 || n_out > (size_t)synthesize_max_outputs(q))   // (n_in <= in_stride; the launch holds 2^41 - 1024 outputs)
 		return OFDMRX_E_ARG;
 	const size_t in_unit = 2 * sample_bytes(in_format), out_unit = 2 * sample_bytes(out_format);
 	if ((size_t)d_in % in_unit || (size_t)d_out % out_unit)
@@ -156,7 +94,7 @@ extern "C" int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, 
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
-	ResynthesizeArgs a{};
+	SynthesizeArgs a{};
 	a.in = d_in;
 	a.in_fmt = in_format;
 	a.out_fmt = out_format;
@@ -170,8 +108,26 @@ extern "C" int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, 
 	a.out_first = out_first;
 	a.n_out = (long long)n_out;
 	a.out = d_out;
-	launch_resynthesize(h->stream, a);
+	launch_synthesize(h->stream, a);
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipEventRecord(slot->done, h->stream));
 	return 0;
+}
+
+extern "C" int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
+	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out, void *d_out,
+	int out_format)
+{
+	if (interp < 2 || interp > 32)
+		return OFDMRX_E_ARG;
+	return synthesize_call(h, d_in, in_format, in_stride, n_in, interp, 1, centre_hz, start, gain, n_channels, out_first, n_out, d_out, out_format);
+}
+
+extern "C" int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
+	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out, void *d_out,
+	int out_format)
+{
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	return synthesize_call(h, d_in, in_format, in_stride, n_in, p, q, centre_hz, start, gain, n_channels, out_first, n_out, d_out, out_format);
 }

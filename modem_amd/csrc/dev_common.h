@@ -152,6 +152,48 @@ __device__ __forceinline__ float div_127(float x)
 	return __builtin_fmaf(__builtin_fmaf(-127.f, q0, x), c, q0);
 }
 
+// ---- what the wideband kernels share (k_channelize, k_rechannelize, k_synthesize, k_resynthesize, k_survey; k_fading the phasor)
+// interleaved I/Q pair i of `in` as fp32; FMT: 0 S16, 1 U8, 2 F32 (OFDMRX_FMT_*).  The caller has checked the bounds
+template <int FMT> __device__ __forceinline__ float2 iq_sample(const void *in, size_t i)
+{
+	if (FMT == 0) {
+		const short2 v = ((const short2 *)in)[i];
+		return make_float2(div_32767((float)v.x), div_32767((float)v.y));
+	}
+	if (FMT == 1) {
+		const unsigned v = ((const uint16_t *)in)[i];
+		return make_float2(div_127((float)((int)(v & 255u) - 128)), div_127((float)((int)(v >> 8) - 128)));
+	}
+	return ((const float2 *)in)[i];
+}
+
+// e^{2 pi i phase / 2^32}: the phase as a signed fraction of a turn, |x| <= 1/2 (the conversion is off by at most 2^-26 turns)
+__device__ __forceinline__ void phase_phasor(unsigned phase, float &cs, float &sn)
+{
+	const float x = (float)(int)phase * (1.f / 4294967296.f);
+	sincospif(2.f * x, &sn, &cs);
+}
+
+// floor(a / d) for d > 0, in 64 bits (the synthesizers' place of a wideband index in a channel's grid, which may lie before its start)
+__device__ __forceinline__ long long floor_div(long long a, int d)
+{
+	const long long q = a / d;
+	return q * d > a ? q - 1 : q;
+}
+
+// the synthesizers' output sample frame t0 + t of `out` (the tile's place, the output's place in the tile: the sum is formed here,
+// behind the conversion, as the kernels formed it); OFMT: 0 S16 (clamped to +-1, rounded to nearest even), 2 F32.  Both pass
+// through v + 0.f first: a zero is always written as +0 (k_synthesize.hip's header)
+template <int OFMT> __device__ __forceinline__ void iq_store(void *out, long long t0, int t, float wr, float wi)
+{
+	if (OFMT == 0) {
+		const float re = fminf(fmaxf(wr + 0.f, -1.f), 1.f), im = fminf(fmaxf(wi + 0.f, -1.f), 1.f);
+		((short2 *)out)[t0 + t] = make_short2((short)nearbyintf(32767.f * re), (short)nearbyintf(32767.f * im));
+	} else {
+		((float2 *)out)[t0 + t] = make_float2(wr + 0.f, wi + 0.f);
+	}
+}
+
 template <int V> struct IntC { static constexpr int value = V; };
 struct SampleSrc {
 	const void *base;      // first sample of this frame

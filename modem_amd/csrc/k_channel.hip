@@ -177,10 +177,8 @@ __global__ __launch_bounds__(256) void k_fading(const short2 *__restrict__ in, s
 		const int i = min(base + tid, items - 1);
 		const int k = i & 15, tj = i >> 4, t = tj / nk, j = tj - t * nk;
 		const unsigned phase = s_ph0[t * FADING_SINES + k] + s_inc[t * FADING_SINES + k] * ((unsigned)m0 + (unsigned)(FADING_KNOT * j));
-		// the phase as a signed fraction of a turn, |x| <= 1/2: the conversion is off by at most 2^-26 turns
-		const float x = (float)(int)phase * (1.f / 4294967296.f);
 		float sn, cs;
-		sincospif(2.f * x, &sn, &cs);
+		phase_phasor(phase, cs, sn);
 		#pragma unroll
 		for (int m = 1; m < FADING_SINES; m <<= 1) {
 			cs += __shfl_xor(cs, m);

@@ -17,33 +17,13 @@ namespace rx {
 constexpr int CHZ_WAVES = 4;                                      // channels per workgroup
 constexpr int CHZ_HIST = 24;                                      // (T - 1) / D: rows of history in front of a tile
 
-template <int FMT> __device__ __forceinline__ float2 chz_sample(const void *in, size_t i)
-{
-	if (FMT == 0) {
-		const short2 v = ((const short2 *)in)[i];
-		return make_float2(div_32767((float)v.x), div_32767((float)v.y));
-	}
-	if (FMT == 1) {
-		const unsigned v = ((const uint16_t *)in)[i];
-		return make_float2(div_127((float)((int)(v & 255u) - 128)), div_127((float)((int)(v >> 8) - 128)));
-	}
-	return ((const float2 *)in)[i];
-}
-
-// the phase as a signed fraction of a turn, |x| <= 1/2 (k_fading's conversion: off by at most 2^-26 turns)
-__device__ __forceinline__ void chz_phasor(unsigned phase, float &cs, float &sn)
-{
-	const float x = (float)(int)phase * (1.f / 4294967296.f);
-	sincospif(2.f * x, &sn, &cs);
-}
-
 // R: outputs per lane; the tile is 64 R outputs, its rows in LDS 64 R + CHZ_HIST, padded to an odd count
 template <int FMT, int R>
 __global__ __launch_bounds__(64 * CHZ_WAVES) void k_channelize(ChannelizeArgs a)
 {
 	constexpr int TILE = 64 * R, ROWS = TILE + CHZ_HIST + 1;
 	extern __shared__ float2 chz_lds[];
-	const int D = a.decim, T = 2 * 12 * D + 1;
+	const int D = a.p, T = 2 * 12 * D + 1;
 	float2 *xs = chz_lds;                                         // [D][ROWS]
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 	float2 *g = chz_lds + D * ROWS + w * T;                       // [CHZ_WAVES][T]
@@ -54,7 +34,7 @@ __global__ __launch_bounds__(64 * CHZ_WAVES) void k_channelize(ChannelizeArgs a)
 		const long long m = m_lo + s;
 		float2 v = make_float2(0.f, 0.f);
 		if (m >= a.in_first && m - a.in_first < a.n_in)
-			v = chz_sample<FMT>(a.in, (size_t)(m - a.in_first));
+			v = iq_sample<FMT>(a.in, (size_t)(m - a.in_first));
 		const int q = s / D, p = s - q * D;
 		xs[p * ROWS + q] = v;
 	}
@@ -63,7 +43,7 @@ __global__ __launch_bounds__(64 * CHZ_WAVES) void k_channelize(ChannelizeArgs a)
 	const unsigned inc = live ? a.inc[c] : 0u;
 	for (int k = lane; k < T; k += 64) {
 		float cs, sn;
-		chz_phasor(inc * (unsigned)k, cs, sn);
+		phase_phasor(inc * (unsigned)k, cs, sn);
 		const float h = a.taps[k];
 		g[k] = make_float2(h * cs, h * sn);
 	}
@@ -98,7 +78,7 @@ __global__ __launch_bounds__(64 * CHZ_WAVES) void k_channelize(ChannelizeArgs a)
 		if (j >= a.n_out)
 			continue;
 		float cs, sn;
-		chz_phasor(inc * (unsigned)(unsigned long long)((a.out_first + j) * D), cs, sn);
+		phase_phasor(inc * (unsigned)(unsigned long long)((a.out_first + j) * D), cs, sn);
 		const float yr = __builtin_fmaf(re[r], cs, im[r] * sn), yi = __builtin_fmaf(im[r], cs, -(re[r] * sn));
 		dst[j] = make_float2(yr, yi);
 	}
@@ -106,7 +86,7 @@ __global__ __launch_bounds__(64 * CHZ_WAVES) void k_channelize(ChannelizeArgs a)
 
 template <int FMT> static void chz_launch(hipStream_t s, const ChannelizeArgs &a)
 {
-	const int D = a.decim, T = 24 * D + 1;
+	const int D = a.p, T = 24 * D + 1;
 	const unsigned groups = (unsigned)((a.n_channels + CHZ_WAVES - 1) / CHZ_WAVES);
 	// (64 KiB of LDS hold a tile of 256 outputs up to D = 16, one of 128 above: 48288 bytes at D = 16, 63776 at D = 32)
 	if (D <= 16) {
@@ -120,11 +100,14 @@ template <int FMT> static void chz_launch(hipStream_t s, const ChannelizeArgs &a
 	}
 }
 
-long long channelize_max_outputs() { return 128LL * 0x7fffffffLL; }
+// (k_channelize's shortest tile is 128 outputs, k_rechannelize's 32: the grid's x stays below 2^31)
+long long channelize_max_outputs(int q) { return (q == 1 ? 128LL : 32LL) * 0x7fffffffLL; }
 
 void launch_channelize(hipStream_t s, const ChannelizeArgs &a)
 {
-	if (a.fmt == 0)
+	if (a.q != 1)
+		launch_channelize_ratio(s, a);
+	else if (a.fmt == 0)
 		chz_launch<0>(s, a);
 	else if (a.fmt == 1)
 		chz_launch<1>(s, a);

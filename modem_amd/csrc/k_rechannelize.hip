@@ -23,31 +23,14 @@ constexpr int RCZ_WAVES = 4;                                      // channels pe
 constexpr int RCZ_R = 4;                                          // slots per lane at most: a tile has at most 256
 constexpr size_t RCZ_LDS = 65536;                                 // the span and the phasors stay inside it: two workgroups per CU
 
-template <int FMT> __device__ __forceinline__ float2 rcz_sample(const void *in, size_t i)
-{
-	if (FMT == 0) {
-		const short2 v = ((const short2 *)in)[i];
-		return make_float2(div_32767((float)v.x), div_32767((float)v.y));
-	}
-	if (FMT == 1) {
-		const unsigned v = ((const uint16_t *)in)[i];
-		return make_float2(div_127((float)((int)(v & 255u) - 128)), div_127((float)((int)(v >> 8) - 128)));
-	}
-	return ((const float2 *)in)[i];
-}
-
-// the phase as a signed fraction of a turn, |x| <= 1/2 (k_channelize's chz_phasor)
-__device__ __forceinline__ void rcz_phasor(unsigned phase, float &cs, float &sn)
-{
-	const float x = (float)(int)phase * (1.f / 4294967296.f);
-	sincospif(2.f * x, &sn, &cs);
-}
+// the tile's shape, from rechannelize_shape: T, M, the rows of history, the rows of a plane in LDS
+struct RczTile { int n_taps, m, hist, rows; };
 
 template <int FMT, int NP>
-__global__ __launch_bounds__(64 * RCZ_WAVES) void k_rechannelize(RechannelizeArgs a)
+__global__ __launch_bounds__(64 * RCZ_WAVES) void k_rechannelize(ChannelizeArgs a, RczTile g)
 {
 	extern __shared__ float2 rcz_lds[];
-	const int P = a.p, Q = a.q, T = a.n_taps, M = a.m, H = a.hist, ROWS = a.rows;
+	const int P = a.p, Q = a.q, T = g.n_taps, M = g.m, H = g.hist, ROWS = g.rows;
 	float2 *xs = rcz_lds;                                         // [P][ROWS]
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 	float2 *ph = rcz_lds + P * ROWS + w * T;                      // [RCZ_WAVES][T]
@@ -59,7 +42,7 @@ __global__ __launch_bounds__(64 * RCZ_WAVES) void k_rechannelize(RechannelizeArg
 		const long long m = m_lo + s;
 		float2 v = make_float2(0.f, 0.f);
 		if (m >= a.in_first && m - a.in_first < a.n_in)
-			v = rcz_sample<FMT>(a.in, (size_t)(m - a.in_first));
+			v = iq_sample<FMT>(a.in, (size_t)(m - a.in_first));
 		const int row = s / P, pl = s - row * P;
 		xs[pl * ROWS + row] = v;
 	}
@@ -68,7 +51,7 @@ __global__ __launch_bounds__(64 * RCZ_WAVES) void k_rechannelize(RechannelizeArg
 	const unsigned inc = live ? a.inc[c] : 0u;
 	for (int j = lane; j < T; j += 64) {
 		float cs, sn;
-		rcz_phasor(inc * (unsigned)j, cs, sn);
+		phase_phasor(inc * (unsigned)j, cs, sn);
 		ph[j] = make_float2(cs, sn);
 	}
 	__syncthreads();
@@ -117,7 +100,7 @@ __global__ __launch_bounds__(64 * RCZ_WAVES) void k_rechannelize(RechannelizeArg
 			continue;
 		const unsigned long long i_n = (unsigned long long)(n_of[r] * P) / (unsigned)Q;
 		float cs, sn;
-		rcz_phasor(inc * (unsigned)i_n, cs, sn);
+		phase_phasor(inc * (unsigned)i_n, cs, sn);
 		const float yr = __builtin_fmaf(re[r], cs, im[r] * sn), yi = __builtin_fmaf(im[r], cs, -(re[r] * sn));
 		dst[j] = make_float2(yr, yi);
 	}
@@ -145,18 +128,18 @@ RechannelizeShape rechannelize_shape(int p, int q)
 	return g;
 }
 
-long long rechannelize_max_outputs() { return 32LL * 0x7fffffffLL; }   // (no tile is shorter than 32 outputs: the grid's x stays below 2^31)
-
-template <int FMT, int NP> static void rcz_launch_np(hipStream_t s, const RechannelizeArgs &a, const RechannelizeShape &g)
+template <int FMT, int NP> static void rcz_launch_np(hipStream_t s, const ChannelizeArgs &a, const RechannelizeShape &g)
 {
 	const long long tile = (long long)a.q * g.m;
 	const long long tiles = (a.out_first + a.n_out - 1) / tile - a.out_first / tile + 1;
 	const unsigned groups = (unsigned)((a.n_channels + RCZ_WAVES - 1) / RCZ_WAVES);
-	hipLaunchKernelGGL((k_rechannelize<FMT, NP>), dim3((unsigned)tiles, groups), dim3(64 * RCZ_WAVES), g.lds, s, a);
+	const RczTile t{ g.n_taps, g.m, g.hist, g.rows };
+	hipLaunchKernelGGL((k_rechannelize<FMT, NP>), dim3((unsigned)tiles, groups), dim3(64 * RCZ_WAVES), g.lds, s, a, t);
 }
 
-template <int FMT> static void rcz_launch(hipStream_t s, const RechannelizeArgs &a, const RechannelizeShape &g)
+template <int FMT> static void rcz_launch_fmt(hipStream_t s, const ChannelizeArgs &a)
 {
+	const RechannelizeShape g = rechannelize_shape(a.p, a.q);
 	if (g.passes == 4)
 		rcz_launch_np<FMT, 4>(s, a, g);
 	else if (g.passes == 3)
@@ -167,20 +150,14 @@ template <int FMT> static void rcz_launch(hipStream_t s, const RechannelizeArgs 
 		rcz_launch_np<FMT, 1>(s, a, g);
 }
 
-void launch_rechannelize(hipStream_t s, const RechannelizeArgs &args)
+void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a)
 {
-	RechannelizeArgs a = args;
-	const RechannelizeShape g = rechannelize_shape(a.p, a.q);
-	a.n_taps = g.n_taps;
-	a.m = g.m;
-	a.hist = g.hist;
-	a.rows = g.rows;
 	if (a.fmt == 0)
-		rcz_launch<0>(s, a, g);
+		rcz_launch_fmt<0>(s, a);
 	else if (a.fmt == 1)
-		rcz_launch<1>(s, a, g);
+		rcz_launch_fmt<1>(s, a);
 	else
-		rcz_launch<2>(s, a, g);
+		rcz_launch_fmt<2>(s, a);
 }
 
 }  // namespace rx

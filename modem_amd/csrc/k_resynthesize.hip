@@ -38,32 +38,10 @@ constexpr int RSY_HIST = 24;
 constexpr int RSY_SPAN = RSY_HIST + (RSY_TILE - 1) / 2 + 1 + 1;
 constexpr int RSY_PRE = (RSY_SPAN + RSY_THREADS - 1) / RSY_THREADS;
 
-template <int FMT> __device__ __forceinline__ float2 rsy_sample(const void *in, size_t i)
-{
-	if (FMT == 0) {
-		const short2 v = ((const short2 *)in)[i];
-		return make_float2(div_32767((float)v.x), div_32767((float)v.y));
-	}
-	return ((const float2 *)in)[i];
-}
-
-// the phase as a signed fraction of a turn, |x| <= 1/2 (k_synthesize's syn_phasor)
-__device__ __forceinline__ void rsy_phasor(unsigned phase, float &cs, float &sn)
-{
-	const float x = (float)(int)phase * (1.f / 4294967296.f);
-	sincospif(2.f * x, &sn, &cs);
-}
-
-__device__ __forceinline__ long long rsy_floor_div(long long a, int d)
-{
-	const long long q = a / d;
-	return q * d > a ? q - 1 : q;
-}
-
 // IFMT: 0 S16, 2 F32 input; OFMT: 0 S16, 2 F32 output.  The second launch bound holds the kernel to 128 VGPRs, four waves per SIMD
 // (it takes 130 - 132 and three without it, and the end-to-end case is 17 % slower: profiles/resynthesize.txt)
 template <int IFMT, int OFMT>
-__global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(ResynthesizeArgs a)
+__global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(SynthesizeArgs a)
 {
 	__shared__ float2 xs[2][RSY_SPAN];
 	const int P = a.p, Q = a.q;
@@ -92,7 +70,7 @@ __global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(ResynthesizeArg
 	// input sample frame j_lo + s of channel c for s = tid, tid + 256, ..: zeros outside 0 .. n_in - 1, which are never loaded
 	float2 pre[RSY_PRE];
 	auto fetch = [&](int c) {
-		const long long j_lo = rsy_floor_div((m0 - a.ch[c].start) * Q, P) - RSY_HIST;
+		const long long j_lo = floor_div((m0 - a.ch[c].start) * Q, P) - RSY_HIST;
 		const size_t row = (size_t)c * (size_t)a.in_stride;
 		#pragma unroll
 		for (int p = 0; p < RSY_PRE; ++p) {
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(ResynthesizeArg
 			const long long j = j_lo + s;
 			pre[p] = make_float2(0.f, 0.f);
 			if (s < span && j >= 0 && j < a.n_in)
-				pre[p] = rsy_sample<IFMT>(a.in, row + (size_t)j);
+				pre[p] = iq_sample<IFMT>(a.in, row + (size_t)j);
 		}
 	};
 	auto stash = [&](int buf) {
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(ResynthesizeArg
 			fetch(cn);
 		const SynthChannel ch = a.ch[c];
 		const long long nu0 = (m0 - ch.start) * Q;
-		const int bb = (int)(nu0 - rsy_floor_div(nu0, P) * P);        // 0 .. P - 1: output t of the tile has nu = (j_lo + 24) P + bb + t Q
+		const int bb = (int)(nu0 - floor_div(nu0, P) * P);            // 0 .. P - 1: output t of the tile has nu = (j_lo + 24) P + bb + t Q
 		const unsigned tq = (unsigned)(bb + tid * Q);                 // < 512 + 255 x 16
 		int s = (int)(tq / (unsigned)P), b = (int)tq - s * P;         // output i: b, and q0 - j_lo = 24 + s
 		#pragma unroll
@@ -153,7 +131,7 @@ __global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(ResynthesizeArg
 				ui = __builtin_fmaf(h[RSY_HIST], v.y, ui);
 			}
 			float cs, sn;
-			rsy_phasor(ch.inc * (unsigned)(unsigned long long)(m0 + tid + RSY_THREADS * i), cs, sn);
+			phase_phasor(ch.inc * (unsigned)(unsigned long long)(m0 + tid + RSY_THREADS * i), cs, sn);
 			const float gr = ch.gain * cs, gi = ch.gain * sn;
 			wr[i] = __builtin_fmaf(gr, ur, wr[i]);
 			wr[i] = __builtin_fmaf(-gi, ui, wr[i]);
@@ -177,18 +155,13 @@ __global__ __launch_bounds__(RSY_THREADS, 4) void k_resynthesize(ResynthesizeArg
 		const int t = tid + RSY_THREADS * i;
 		if (t >= n_tile)
 			continue;
-		if (OFMT == 0) {
-			const float re = fminf(fmaxf(wr[i] + 0.f, -1.f), 1.f), im = fminf(fmaxf(wi[i] + 0.f, -1.f), 1.f);
-			((short2 *)a.out)[t0 + t] = make_short2((short)nearbyintf(32767.f * re), (short)nearbyintf(32767.f * im));
-		} else {
-			((float2 *)a.out)[t0 + t] = make_float2(wr[i] + 0.f, wi[i] + 0.f);   // (-0 -> +0: see the header)
-		}
+		iq_store<OFMT>(a.out, t0, t, wr[i], wi[i]);                       // (-0 -> +0: see the header)
 	}
 }
 
-long long resynthesize_max_outputs() { return (long long)RSY_TILE * 0x7fffffffLL; }   // (the grid's x stays below 2^31)
+static_assert(RSY_TILE == 1024, "synthesize_max_outputs (k_synthesize.hip) counts on tiles of 1024 outputs");
 
-void launch_resynthesize(hipStream_t s, const ResynthesizeArgs &a)
+void launch_synthesize_ratio(hipStream_t s, const SynthesizeArgs &a)
 {
 	const dim3 grid((unsigned)((a.n_out + RSY_TILE - 1) / RSY_TILE)), block(RSY_THREADS);
 	if (a.in_fmt == 0 && a.out_fmt == 0)

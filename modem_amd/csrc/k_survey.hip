@@ -30,15 +30,7 @@ template <int FMT> __device__ __forceinline__ cf survey_sample(const SurveyArgs 
 	const long long i = m - a.in_first;
 	if (i < 0 || i >= a.n_in)                                     // (the host refuses such a call: never taken)
 		return mk(0.f, 0.f);
-	if (FMT == 0) {
-		const short2 v = ((const short2 *)a.in)[i];
-		return mk(div_32767((float)v.x), div_32767((float)v.y));
-	}
-	if (FMT == 1) {
-		const unsigned v = ((const uint16_t *)a.in)[i];
-		return mk(div_127((float)((int)(v & 255u) - 128)), div_127((float)((int)(v >> 8) - 128)));
-	}
-	const float2 v = ((const float2 *)a.in)[i];
+	const float2 v = iq_sample<FMT>(a.in, (size_t)i);
 	return mk(v.x, v.y);
 }
 

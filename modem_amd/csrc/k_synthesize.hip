@@ -16,7 +16,7 @@
 // neighbouring taps and broadcast their inputs; lanes of neighbouring g read inputs SYN_R float2 apart, and SYN_R is odd, so that
 // the 32 lanes of a half wave fall on different bank pairs (a carry of one sample between the lanes of a g can cost a 2-way conflict).
 // The order is part of the definition's contract and a function of (c, m) alone: u_c is one chain of fused multiply-adds per
-// component with a ascending from +0; (cs, sn) = sincospif of the phase as a signed fraction of a turn (k_channelize's conversion);
+// component with a ascending from +0; (cs, sn) = sincospif of the phase as a signed fraction of a turn (phase_phasor, dev_common.h);
 // gr = G_c cs, gi = G_c sn; then re: + gr u.re, - gi u.im; im: + gr u.im, + gi u.re, one chain per component over c ascending from
 // +0.  A term whose input lies outside 0 .. n_in - 1 multiplies +0 and a channel that misses the tile adds +0 four times: neither
 // changes a value.  It can change the sign of a zero - a product that underflows to -0 stays -0 only until a +0 is added - so every
@@ -36,35 +36,13 @@ constexpr int SYN_TAPS = 24 * 32 + 1;
 
 __host__ __device__ inline int syn_tile(int D) { return (SYN_THREADS / D) * D * SYN_R; }
 
-template <int FMT> __device__ __forceinline__ float2 syn_sample(const void *in, size_t i)
-{
-	if (FMT == 0) {
-		const short2 v = ((const short2 *)in)[i];
-		return make_float2(div_32767((float)v.x), div_32767((float)v.y));
-	}
-	return ((const float2 *)in)[i];
-}
-
-// the phase as a signed fraction of a turn, |x| <= 1/2 (k_channelize's conversion: off by at most 2^-26 turns)
-__device__ __forceinline__ void syn_phasor(unsigned phase, float &cs, float &sn)
-{
-	const float x = (float)(int)phase * (1.f / 4294967296.f);
-	sincospif(2.f * x, &sn, &cs);
-}
-
-__device__ __forceinline__ long long syn_floor_div(long long a, int d)
-{
-	const long long q = a / d;
-	return q * d > a ? q - 1 : q;
-}
-
 // IFMT: 0 S16, 2 F32 input; OFMT: 0 S16, 2 F32 output
 template <int IFMT, int OFMT>
 __global__ __launch_bounds__(SYN_THREADS) void k_synthesize(SynthesizeArgs a)
 {
 	__shared__ float hs[SYN_TAPS];
 	__shared__ float2 xs[2][SYN_SPAN];
-	const int D = a.interp, T = 2 * 12 * D + 1;
+	const int D = a.p, T = 2 * 12 * D + 1;
 	const int G = SYN_THREADS / D, TILE = G * D * SYN_R;
 	const int tid = threadIdx.x;
 	const int g = tid / D, tp = tid - g * D;
@@ -94,7 +72,7 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synthesize(SynthesizeArgs a)
 	// input sample frame j_lo + s of channel c for s = tid, tid + 256, ..: zeros outside 0 .. n_in - 1, which are never loaded
 	float2 pre[SYN_PRE];
 	auto fetch = [&](int c) {
-		const long long j_lo = syn_floor_div(m0 - a.ch[c].start - (T - 1), D);
+		const long long j_lo = floor_div(m0 - a.ch[c].start - (T - 1), D);
 		const size_t row = (size_t)c * (size_t)a.in_stride;
 		#pragma unroll
 		for (int p = 0; p < SYN_PRE; ++p) {
@@ -102,7 +80,7 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synthesize(SynthesizeArgs a)
 			const long long j = j_lo + s;
 			pre[p] = make_float2(0.f, 0.f);
 			if (s < span && j >= 0 && j < a.n_in)
-				pre[p] = syn_sample<IFMT>(a.in, row + (size_t)j);
+				pre[p] = iq_sample<IFMT>(a.in, row + (size_t)j);
 		}
 	};
 	auto stash = [&](int buf) {
@@ -126,7 +104,7 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synthesize(SynthesizeArgs a)
 		if (active) {
 			const SynthChannel ch = a.ch[c];
 			const long long r_lo = m0 - ch.start - (T - 1);
-			const int e = (int)(r_lo - syn_floor_div(r_lo, D) * D);   // 0 .. D - 1: output t of the tile has r = (24 + j_lo) D + e + t
+			const int e = (int)(r_lo - floor_div(r_lo, D) * D);       // 0 .. D - 1: output t of the tile has r = (24 + j_lo) D + e + t
 			int b = tp + e, s0 = g * SYN_R;                            // output i: b, and q - j_lo = 24 + s0 + i
 			if (b >= D) {
 				b -= D;
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synthesize(SynthesizeArgs a)
 					ui = __builtin_fmaf(h24, xw[i].y, ui);
 				}
 				float cs, sn;
-				syn_phasor(ch.inc * (unsigned)(unsigned long long)(m0 + (g * SYN_R + i) * D + tp), cs, sn);
+				phase_phasor(ch.inc * (unsigned)(unsigned long long)(m0 + (g * SYN_R + i) * D + tp), cs, sn);
 				const float gr = ch.gain * cs, gi = ch.gain * sn;
 				wr[i] = __builtin_fmaf(gr, ur, wr[i]);
 				wr[i] = __builtin_fmaf(-gi, ui, wr[i]);
@@ -176,21 +154,18 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synthesize(SynthesizeArgs a)
 		const int t = (g * SYN_R + i) * D + tp;
 		if (t >= n_tile)
 			continue;
-		if (OFMT == 0) {
-			const float re = fminf(fmaxf(wr[i] + 0.f, -1.f), 1.f), im = fminf(fmaxf(wi[i] + 0.f, -1.f), 1.f);
-			((short2 *)a.out)[t0 + t] = make_short2((short)nearbyintf(32767.f * re), (short)nearbyintf(32767.f * im));
-		} else {
-			((float2 *)a.out)[t0 + t] = make_float2(wr[i] + 0.f, wi[i] + 0.f);   // (-0 -> +0: see the header)
-		}
+		iq_store<OFMT>(a.out, t0, t, wr[i], wi[i]);                       // (-0 -> +0: see the header)
 	}
 }
 
-// (the smallest tile is 1160 outputs, at D = 29)
-long long synthesize_max_outputs() { return 1024LL * 0x7fffffffLL; }
+// (k_synthesize's smallest tile is 1160 outputs, at D = 29; k_resynthesize's is 1024: the grid's x stays below 2^31)
+long long synthesize_max_outputs(int) { return 1024LL * 0x7fffffffLL; }
 
 void launch_synthesize(hipStream_t s, const SynthesizeArgs &a)
 {
-	const int tile = syn_tile(a.interp);
+	if (a.q != 1)
+		return launch_synthesize_ratio(s, a);
+	const int tile = syn_tile(a.p);
 	const dim3 grid((unsigned)((a.n_out + tile - 1) / tile)), block(SYN_THREADS);
 	if (a.in_fmt == 0 && a.out_fmt == 0)
 		hipLaunchKernelGGL((k_synthesize<0, 0>), grid, block, 0, s, a);

@@ -335,34 +335,15 @@ long front_end_stretch();
 void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
 void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z);
 
-// ---- the wideband front end (k_channelize.hip): mix-down, FIR and decimation of one wideband capture into
-// n_channels channel rows.  in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); every position outside
-// reads as zero and is never loaded.  Output n of channel c (n = out_first .. out_first + n_out - 1) goes to
-// out + 2 (c out_stride + n - out_first) floats, or - dst != nullptr - to the address dst[c] + 8 (n - out_first) (the bank: every
-// channel's place in its window).  taps: the 24 decim + 1 fp32 taps of channelize_taps; inc: the channels' phase increments.
+// ---- the wideband front end (k_channelize.hip, k_rechannelize.hip): mix-down, FIR and decimation by p / q
+// (in lowest terms, 1 <= q <= 16, 2 <= p / q <= 32; q = 1: the integer decimation D = p) of one wideband capture into n_channels
+// channel rows.  in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); every position outside reads as
+// zero and is never loaded.  Output n of channel c (n = out_first .. out_first + n_out - 1) reads the wideband positions
+// n p div q - (T - 1) .. n p div q, T = 24 p div q + 1, and goes to out + 2 (c out_stride + n - out_first) floats, or
+// - dst != nullptr - to the address dst[c] + 8 (n - out_first) (the bank: every channel's place in its window).  taps: device,
+// [T][q] - tap j of phase r at j q + r, the transpose of what rechannelize_taps writes (q = 1: the T taps of channelize_taps as
+// they are); inc: the channels' phase increments.
 struct ChannelizeArgs {
-	const void *in;
-	int fmt;                       // OFDMRX_FMT_*
-	int decim;                     // 2 .. 32
-	long long in_first, n_in;
-	const float *taps;             // device
-	const unsigned *inc;           // device, [n_channels]
-	int n_channels;
-	long long out_first, n_out;    // n_out <= channelize_max_outputs()
-	float *out;
-	long long out_stride;          // I/Q pairs per channel row
-	const long long *dst;          // device, [n_channels] addresses, nullable
-};
-void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
-long long channelize_max_outputs();
-// host: the taps of decimation D (T = 24 D + 1 of them; returns T) and the phase increment of a centre frequency at wideband rate rw
-int channelize_taps(int decim, float *taps);
-unsigned channelize_inc(double centre_hz, double rw);
-
-// ---- the wideband front end at a rational decimation p / q in lowest terms (k_rechannelize.hip): 1 <= q <= 16,
-// 2 <= p / q <= 32.  in, out, dst, inc: as ChannelizeArgs.  Output n reads the wideband positions n p div q - (T - 1) .. n p div q,
-// T = 24 p div q + 1.  taps: device, [T][q] - tap j of phase r at j q + r (the transpose of what rechannelize_taps writes).
-struct RechannelizeArgs {
 	const void *in;
 	int fmt;                       // OFDMRX_FMT_*
 	int p, q;
@@ -370,62 +351,53 @@ struct RechannelizeArgs {
 	const float *taps;             // device, [T][q]
 	const unsigned *inc;           // device, [n_channels]
 	int n_channels;
-	long long out_first, n_out;    // n_out <= rechannelize_max_outputs()
+	long long out_first, n_out;    // n_out <= channelize_max_outputs(q)
 	float *out;
 	long long out_stride;          // I/Q pairs per channel row
 	const long long *dst;          // device, [n_channels] addresses, nullable
-	int n_taps, m, hist, rows;     // (the launch fills them in from rechannelize_shape)
 };
-// what a workgroup's tile looks like: T, the outputs per residue M (a tile is q M outputs), the rows of history, the rows of a
-// plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
+// k_channelize where a.q == 1, k_rechannelize (launch_channelize_ratio) otherwise: each keeps its own summation order (see the files)
+void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
+void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a);   // k_rechannelize.hip: launch_channelize's q > 1
+long long channelize_max_outputs(int q);
+// what a workgroup's tile of k_rechannelize looks like: T, the outputs per residue M (a tile is q M outputs), the rows of history,
+// the rows of a plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
 struct RechannelizeShape { int n_taps, m, hist, rows, passes; size_t lds; };
 RechannelizeShape rechannelize_shape(int p, int q);
-void launch_rechannelize(hipStream_t s, const RechannelizeArgs &a);
-long long rechannelize_max_outputs();
+// host: the taps of decimation D (T = 24 D + 1 of them; returns T) and the phase increment of a centre frequency at wideband rate rw
+int channelize_taps(int decim, float *taps);
+unsigned channelize_inc(double centre_hz, double rw);
 // host: the taps of the reduced ratio p / q as [q][T] (returns T); q = 1: channelize_taps(p, .)
 int rechannelize_taps(int p, int q, float *taps);
 
-// ---- the wideband synthesizer (k_synthesize.hip): n_channels narrowband rows -> one wideband capture.  in: sample
-// frame j (0 .. n_in - 1) of channel c at c in_stride + j sample frames (interleaved I/Q of in_fmt: S16 or F32); every index outside
-// reads as zero and is never loaded.  Output m (out_first .. out_first + n_out - 1) goes m - out_first sample frames into out, as
-// out_fmt (S16 or F32).  taps: the 24 interp + 1 fp32 taps of channelize_taps.
-struct SynthChannel {
-	long long start;               // wideband index of the channel's first input sample, >= 0
-	unsigned inc;                  // channelize_inc of its centre
-	float gain;                    // interp x the caller's gain, rounded once
-};
-struct SynthesizeArgs {
-	const void *in;
-	int in_fmt, out_fmt;           // OFDMRX_FMT_S16 or OFDMRX_FMT_F32
-	int interp;                    // 2 .. 32
-	long long in_stride, n_in;     // sample frames
-	const SynthChannel *ch;        // device, [n_channels]
-	const float *taps;             // device
-	int n_channels;
-	long long out_first, n_out;    // n_out <= synthesize_max_outputs()
-	void *out;
-};
-void launch_synthesize(hipStream_t s, const SynthesizeArgs &a);
-long long synthesize_max_outputs();
-
-// ---- the wideband synthesizer at a rational interpolation p / q in lowest terms (k_resynthesize.hip): 2 <= q <= 16,
-// 2 <= p / q <= 32.  in, ch, out: as SynthesizeArgs (a channel's gain is p / q x the caller's).  taps: device, 16-byte aligned,
+// ---- the wideband synthesizer (k_synthesize.hip, k_resynthesize.hip): n_channels narrowband rows -> one
+// wideband capture at p / q times their rate (lowest terms, 1 <= q <= 16, 2 <= p / q <= 32; q = 1: the integer interpolation p).
+// in: sample frame j (0 .. n_in - 1) of channel c at c in_stride + j sample frames (interleaved I/Q of in_fmt: S16 or F32); every
+// index outside reads as zero and is never loaded.  Output m (out_first .. out_first + n_out - 1) goes m - out_first sample frames
+// into out, as out_fmt (S16 or F32).  taps: device; q = 1: the 24 p + 1 fp32 taps of channelize_taps; q > 1: 16-byte aligned,
 // [p][RSY_ROW] - row b holds G[b + a p], a = 0 .. 24, of the sequence G[tn] = H[tn mod q][tn div q], tn = 0 .. 24 p, that
 // rechannelize_taps' table [q][T] spells, zeros behind it (resynthesize_taps writes it).
 constexpr int RSY_ROW = 28;
-struct ResynthesizeArgs {
+struct SynthChannel {
+	long long start;               // wideband index of the channel's first input sample, >= 0
+	unsigned inc;                  // channelize_inc of its centre
+	float gain;                    // p / q x the caller's gain, rounded once
+};
+struct SynthesizeArgs {
 	const void *in;
 	int in_fmt, out_fmt;           // OFDMRX_FMT_S16 or OFDMRX_FMT_F32
 	int p, q;
 	long long in_stride, n_in;     // sample frames
 	const SynthChannel *ch;        // device, [n_channels]
-	const float *taps;             // device, [p][RSY_ROW]
+	const float *taps;             // device
 	int n_channels;
-	long long out_first, n_out;    // n_out <= resynthesize_max_outputs()
+	long long out_first, n_out;    // n_out <= synthesize_max_outputs(q)
 	void *out;
 };
-void launch_resynthesize(hipStream_t s, const ResynthesizeArgs &a);
-long long resynthesize_max_outputs();
+// k_synthesize where a.q == 1, k_resynthesize (launch_synthesize_ratio) otherwise: they tile differently (profiles/resynthesize.txt)
+void launch_synthesize(hipStream_t s, const SynthesizeArgs &a);
+void launch_synthesize_ratio(hipStream_t s, const SynthesizeArgs &a);   // k_resynthesize.hip: launch_synthesize's q > 1
+long long synthesize_max_outputs(int q);
 
 // ---- the wideband survey (k_survey.hip): a Welch power spectrum of one wideband capture, n_rows rows of nfft bins.
 // in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); the caller has checked that every position the

@@ -275,3 +275,41 @@ def test_refusals_leave_the_output_untouched(rx):
     v, tol, _ = RM.channelize(pcm, P, Q, f)
     assert RM.worst(got[:, :n_out], v, tol) <= 1.0
     assert (got[:, n_out:].view(np.uint8) == 77).all() and (buf[4 * W + 2 * (n_out + 1) * 8:] == 77).all()
+
+
+def test_one_handle_serves_integer_and_ratio_calls_in_turn(rx):
+    """the handle keeps ONE set of front-end parameters, keyed by the reduced (p, q) and the increments: D = 5 and 5/2 share p, and
+    10/4 must meet 5/2's.  Integer and ratio calls alternate on one handle, with the same centres, other centres and fewer of them;
+    every output equals, byte for byte, the same call on a second handle on which a call at 64/3 precedes it - so that handle uploads
+    its parameters anew every time.  4096 samples give 820 outputs at D = 5, 1639 at 5/2 and 656 at 25/4: more than one tile each;
+    three channels leave a workgroup partly filled"""
+    import modem_amd
+    import torch
+    W = 4096
+    pcm = RM.random_pcm(W, np.int16, seed=11)
+    d_in = _dev(pcm)
+    f = np.array([1234.5, -9000.0, 10000.0])                         # inside +-10 kHz, half the wideband rate of 5/2
+    g = np.array([-3333.25, 0.0, 7000.125])
+    calls = ((5, f), ((5, 2), f), (5, f), ((5, 2), f), ((5, 2), g), ((5, 2), g[:2]), ((25, 4), f), ((10, 4), f))
+    assert [RM.n_outputs(W, 5, 1), RM.n_outputs(W, 5, 2), RM.n_outputs(W, 25, 4)] == [820, 1639, 656]
+    assert tile_of(5, 2) < 1639 and tile_of(25, 4) < 656 and 256 < 820
+
+    def run(r, decim, centres):
+        P, Q = decim if isinstance(decim, tuple) else (decim, 1)
+        n_out = RM.n_outputs(W, P, Q)
+        out = torch.full((len(centres), n_out, 2), SENTINEL, dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        r.channelize(d_in.data_ptr(), 0, 0, W, decim, centres, 0, n_out, out.data_ptr())
+        r.synchronize()
+        return out.cpu().numpy()
+
+    ref = modem_amd.Receiver(device=0, chunk_frames=1)
+    try:
+        for k, (decim, centres) in enumerate(calls):
+            run(ref, (64, 3), f)
+            want = run(ref, decim, centres)
+            got = run(rx, decim, centres)
+            assert not (want == SENTINEL).any(), (k, decim)
+            assert got.tobytes() == want.tobytes(), (k, decim)
+    finally:
+        ref.close()
