@@ -61,7 +61,8 @@ extern "C" {
  *      ofdmrx_bank_push_wideband; the wideband synthesizer - ofdmrx_util_synthesize; the wideband survey - ofdmrx_util_survey_window,
  *      ofdmrx_util_survey, ofdmrx_util_find_bands; the wideband front end at a rational decimation -
  *      ofdmrx_util_channelize_ratio_taps, ofdmrx_util_channelize_ratio, ofdmrx_bank_begin_wideband_ratio; the wideband synthesizer
- *      at a rational interpolation - ofdmrx_util_synthesize_ratio */
+ *      at a rational interpolation - ofdmrx_util_synthesize_ratio; the wideband front end on a channel grid (a polyphase filter bank) -
+ *      ofdmrx_util_channelize_grid_taps, ofdmrx_util_channelize_grid, ofdmrx_bank_begin_wideband_grid */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -422,6 +423,15 @@ int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, size_t n_wi
  * decim's (p or q <= 0, reduced q above 16, p / q outside 2..32) and centres outside +- rate p / q / 2.  A ratio whose reduced q is 1
  * opens the bank ofdmrx_bank_begin_wideband opens. */
 int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int sample_format);
+/* ... of a capture at decim x the handle's rate whose channels lie on the raster rate / 2 (added within revision 1.9, detected by
+ * symbol): the front end is ofdmrx_util_channelize_grid below, decim a power of two 2 .. 512, channel j the
+ * slot slots[j] (slots NULL with n_slots = 2 decim: every slot in ascending order).  ofdmrx_bank_push_wideband, ofdmrx_bank_end and
+ * the queries serve it unchanged: one copy behind the kept tail (up to 24 decim = 12288 wideband samples) and one launch per push,
+ * whatever the number of slots, and the contract above holds with row j of ofdmrx_util_channelize_grid.  OFDMRX_E_ARG: what
+ * ofdmrx_bank_begin_wideband refuses, with a decim that is no power of two in 2..512, a slot outside -decim .. decim - 1 and n_slots
+ * outside 1..65535 in the place of its limits.  While it is open ofdmrx_util_channelize* (the grid entry too) and ofdmrx_bank_push
+ * are refused. */
+int ofdmrx_bank_begin_wideband_grid(ofdmrx_handle *h, size_t n_slots, const int32_t *slots, int decim, int sample_format);
 
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);
@@ -620,6 +630,33 @@ int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format
 int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps);
 int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
+
+/* Wideband front end on a channel grid (added within revision 1.9, detected by symbol): a polyphase filter bank for channels on a
+ * raster.  DESIGN.md section 4.19 is the definition, held component by component to a float64 model.  With `rate` the handle's rate:
+ *   D = decim, one of 2, 4, 8 .. 512; Rw = D rate; M = 2 D slots k = -M/2 .. M/2 - 1, slot k's centre at k rate / 2 (the slots lie
+ *   half a channel rate apart: the bank is oversampled by 2); K = 12 D, T = 24 D + 1 = 12 M + 1
+ *   taps    h[t]: the formula of ofdmrx_util_channelize_taps unchanged - in double, normalised to sum 1, rounded once to fp32; for
+ *           D <= 32 the bytes that entry writes, for larger D the same filter scaled (flat within 0.01 dB up to rate / 4, -70 dB or
+ *           below from rate / 2 on)
+ *   output  y_k[n] = sum_{t = 0 .. T - 1} h[t] x[n D - t] e^{-2 pi i k (n D - t) / M}, x zero at negative indices; fp32 I/Q, no
+ *           clip.  2^32 / M is an integer, so this is ofdmrx_util_channelize's output for the centre k rate / 2 with the increment
+ *           k 2^32 / M and no rounding of it.  Group delay (12 output samples), sc_start + 12 and ceil(W / D) outputs per channel as
+ *           there
+ *   form    u_n[r] = sum_a h[r + M a] x[n D - r - M a], r = 0 .. M - 1, a = 0 .. 11 and a = 12 for r = 0: one fp32 fused
+ *           multiply-add chain per component, a ascending, positions outside the buffer entering as +0;
+ *           y_k[n] = (-1)^{k n} sum_r u_n[r] e^{+2 pi i k r / M}: an unnormalised inverse DFT of length M, whose order of
+ *           operations is fixed by M alone.  No NCO
+ * No state: a capture cut into blocks (each handed over with the T - 1 samples before it) gives the same bytes as one call.  The
+ * outputs agree with ofdmrx_util_channelize at the same centres within the two tolerances, not byte for byte.
+ * ofdmrx_util_channelize_grid_taps: host only; writes T floats (at most 12289), returns T; OFDMRX_E_ARG for a decim that is no power
+ * of two in 2..512 or a NULL pointer.
+ * ofdmrx_util_channelize_grid: row j of the output is slot slots[j] (a host array; NULL with n_slots = M: every slot in ascending k);
+ * the other arguments, memory spaces, asynchrony and refusals are those of ofdmrx_util_channelize.  OFDMRX_E_ARG besides, before
+ * any device call and with the output untouched: a decim that is no power of two in 2..512, a slot outside -M/2 .. M/2 - 1, n_slots
+ * outside 1..65535, NULL slots with n_slots != M. */
+int ofdmrx_util_channelize_grid_taps(int decim, float *taps);
+int ofdmrx_util_channelize_grid(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	const int32_t *slots, size_t n_slots, long long out_first, size_t n_out, float *d_out, size_t out_stride);
 
 /* Wideband synthesizer (added within revision 1.9, detected by symbol), the mirror image of the wideband front end: n_channels
  * narrowband transmissions at the handle's rate - what the device transmitter and the channel kernels leave - are each placed at a

@@ -12,7 +12,8 @@
 // A WIDEBAND bank (ofdmrx_bank_begin_wideband) is fed one wideband capture instead: its channels are 2-channel F32 at
 // the handle's rate, and "the new samples" of a push are made on the device - the wideband block is copied once behind the last
 // T - 1 wideband samples (kept on the host and sent with it), and ONE k_channelize launch writes every channel's new samples straight
-// into its window (a bank opened with ofdmrx_bank_begin_wideband_ratio, DESIGN.md 4.17: ONE k_rechannelize launch).  Everything behind
+// into its window (a bank opened with ofdmrx_bank_begin_wideband_ratio, DESIGN.md 4.17: ONE k_rechannelize launch; with
+// ofdmrx_bank_begin_wideband_grid, DESIGN.md 4.19: ONE k_channelize_grid launch, the tail up to 24 x 512 samples).  Everything behind
 // that step is the same code.
 // The windows of all channels live in one slab pair [n_channels][cap] with a common capacity; channel c's window begins at its own
 // base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch: it is handed the address position 0
@@ -55,7 +56,8 @@ struct ofdmrx_bank {
 	bool ending = false;
 	bool as_feed = false;                                     // opened by ofdmrx_feed_begin: the ofdmrx_feed_* entries serve it, ofdmrx_bank_* refuse it
 	// a wideband bank: decimation, the format of the wideband samples, how many have been pushed, and the last min(wfed, T - 1) of them
-	// (decimation p / q in lowest terms: an integer decimation has q = 1 and runs k_channelize, any other k_rechannelize)
+	// (decimation p / q in lowest terms: an integer decimation has q = 1 and runs k_channelize, any other k_rechannelize, DESIGN.md 4.17;
+	// a grid bank, DESIGN.md 4.19, has q = 1 and runs k_channelize_grid: the handle's table says so, which the open bank owns)
 	bool wide = false;
 	int p = 0, q = 1, wfmt = 0;
 	long long wfed = 0;
@@ -342,13 +344,15 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 			a.q = b.q;
 			a.in_first = b.wfed - tail;
 			a.n_in = tail + (long long)n_wide;
-			a.taps = h->chz_taps.as<float>();
-			a.inc = h->chz_inc.as<unsigned>();
+			channelize_tables(h, a);
 			a.n_channels = (int)C;
 			a.out_first = o0;
 			a.n_out = o1 - o0;
 			a.dst = dpar + P_PL_DST * P;
-			launch_channelize(s, a);
+			if (a.grid)
+				launch_channelize_grid(s, a);
+			else
+				launch_channelize(s, a);
 			b.ops += 2;
 		}
 		const size_t keep = std::min(b.stage_h.size(), (size_t)(T - 1) * wunit);
@@ -749,6 +753,28 @@ extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_chann
 	if (rechannelize_ratio(p, q))
 		return OFDMRX_E_ARG;
 	return begin_wideband(h, n_channels, centre_hz, p, q, fmt);
+}
+
+// the grid front end: channel j is slot slots[j] of the raster rate / 2 (slots = NULL with n_slots = 2 decim: all)
+extern "C" int ofdmrx_bank_begin_wideband_grid(ofdmrx_handle *h, size_t n_slots, const int32_t *slots, int decim, int fmt)
+{
+	std::vector<int32_t> list;
+	if (!h || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channelize_grid_decim(decim) || channelize_grid_slots(decim, slots, n_slots, list))
+		return OFDMRX_E_ARG;
+	if (h->bank)
+		return OFDMRX_E_ARG;
+	int r = begin(h, n_slots, OFDMRX_FMT_F32, 2, false);
+	if (r)
+		return r;
+	if ((r = channelize_grid_setup(h, decim, list))) {
+		bank_free(h);
+		return r;
+	}
+	h->bank->wide = true;
+	h->bank->p = decim;
+	h->bank->q = 1;
+	h->bank->wfmt = fmt;
+	return 0;
 }
 
 extern "C" int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, size_t n_wide, int end_all, size_t max_records, uint8_t *payload_out,

@@ -81,16 +81,11 @@ int rechannelize_ratio(int &p, int &q)
 // a capture cut into blocks); anything else - other centres, another ratio, an integer decimation after a ratio - waits for the
 // stream first, since a kernel enqueued earlier may still read the old values.  The device holds the taps transposed, [T][q], as
 // k_rechannelize reads them; at q = 1 that is channelize_taps' own order, which k_channelize reads
-int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels)
+// grid: a grid table (q = 1, the M / 2 = p roots of the transform behind the taps); it is part of the key, so a
+// grid call after a plain call at the same D uploads again, and the reverse
+static int channelize_upload(ofdmrx_handle *h, int p, int q, bool grid, const std::vector<unsigned> &inc)
 {
-	const double rw = (double)h->rate * (double)p / (double)q;
-	std::vector<unsigned> inc(n_channels);
-	for (size_t c = 0; c < n_channels; ++c) {
-		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw)
-			return OFDMRX_E_ARG;
-		inc[c] = channelize_inc(centre_hz[c], rw);
-	}
-	if (p == h->chz_p && q == h->chz_q && inc == h->chz_inc_h)
+	if (p == h->chz_p && q == h->chz_q && grid == h->chz_grid && inc == h->chz_inc_h)
 		return 0;
 	HIP_OK(hipSetDevice(h->cfg.device));
 	HIP_OK(hipStreamSynchronize(h->stream));
@@ -102,16 +97,76 @@ int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, si
 	for (size_t r = 0; r < (size_t)q; ++r)
 		for (size_t j = 0; j < T; ++j)
 			h->chz_taps_h[j * (size_t)q + r] = rows[r * T + j];
+	h->chz_tw_at = 0;
+	if (grid) {                                                   // e^{+2 pi i j / M}, j = 0 .. M / 2 - 1, on an 8-byte boundary
+		const double pi = 3.14159265358979323846;
+		h->chz_tw_at = (T + 1) / 2 * 2;
+		h->chz_taps_h.resize(h->chz_tw_at + 2 * (size_t)p, 0.f);
+		for (int j = 0; j < p; ++j) {
+			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j] = (float)std::cos(pi * (double)j / (double)p);
+			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j + 1] = (float)std::sin(pi * (double)j / (double)p);
+		}
+	}
 	h->chz_inc_h = inc;
 	int r = h->chz_taps.ensure(h->chz_taps_h.size() * sizeof(float));
-	r = r ? r : h->chz_inc.ensure(n_channels * sizeof(unsigned));
+	r = r ? r : h->chz_inc.ensure(inc.size() * sizeof(unsigned));
 	if (r)
 		return r;
 	HIP_OK(hipMemcpyAsync(h->chz_taps.p, h->chz_taps_h.data(), h->chz_taps_h.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-	HIP_OK(hipMemcpyAsync(h->chz_inc.p, h->chz_inc_h.data(), n_channels * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+	HIP_OK(hipMemcpyAsync(h->chz_inc.p, h->chz_inc_h.data(), inc.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
 	h->chz_p = p;
 	h->chz_q = q;
+	h->chz_grid = grid;
 	return 0;
+}
+
+int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels)
+{
+	const double rw = (double)h->rate * (double)p / (double)q;
+	std::vector<unsigned> inc(n_channels);
+	for (size_t c = 0; c < n_channels; ++c) {
+		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw)
+			return OFDMRX_E_ARG;
+		inc[c] = channelize_inc(centre_hz[c], rw);
+	}
+	return channelize_upload(h, p, q, false, inc);
+}
+
+int channelize_grid_decim(int decim)
+{
+	return (decim >= 2 && decim <= 512 && !(decim & (decim - 1))) ? 0 : OFDMRX_E_ARG;
+}
+
+int channelize_grid_slots(int decim, const int32_t *slots, size_t n_slots, std::vector<int32_t> &out)
+{
+	const int M = 2 * decim;
+	if (n_slots < 1 || n_slots > 65535 || (!slots && n_slots != (size_t)M))
+		return OFDMRX_E_ARG;
+	out.resize(n_slots);
+	for (size_t j = 0; j < n_slots; ++j) {
+		out[j] = slots ? slots[j] : (int32_t)j - M / 2;
+		if (out[j] < -M / 2 || out[j] > M / 2 - 1)
+			return OFDMRX_E_ARG;
+	}
+	return 0;
+}
+
+// slot k's increment k 2^32 / M mod 2^32: what channelize_inc gives for the centre k rate / 2, without a rounding
+int channelize_grid_setup(ofdmrx_handle *h, int decim, const std::vector<int32_t> &slots)
+{
+	const unsigned step = (unsigned)(4294967296ULL / (unsigned long long)(2 * decim));
+	std::vector<unsigned> inc(slots.size());
+	for (size_t j = 0; j < slots.size(); ++j)
+		inc[j] = (unsigned)slots[j] * step;
+	return channelize_upload(h, decim, 1, true, inc);
+}
+
+void channelize_tables(const ofdmrx_handle *h, ChannelizeArgs &a)
+{
+	a.taps = h->chz_taps.as<float>();
+	a.inc = h->chz_inc.as<unsigned>();
+	a.grid = h->chz_grid;
+	a.tw = h->chz_grid ? (const float2 *)(h->chz_taps.as<float>() + h->chz_tw_at) : nullptr;
 }
 
 extern "C" int ofdmrx_util_channelize_taps(int decim, float *taps)
@@ -128,16 +183,18 @@ extern "C" int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps)
 	return rechannelize_taps(p, q, taps);
 }
 
-// one call at the reduced ratio p / q (q = 1: the integer decimation p)
+// one call at the reduced ratio p / q (q = 1: the integer decimation p).  grid: the grid front end at decimation p, whose channels are
+// the slots (nullable: all of them) and not centres
 static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
-	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride,
+	bool grid = false, const int32_t *slots = nullptr)
 {
 	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
-	if (!h || !d_in || !d_out || !centre_hz || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
+	if (!h || !d_in || !d_out || (!grid && !centre_hz) || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
 		return OFDMRX_E_ARG;
 	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || out_first < 0 || out_stride < n_out)
 		return OFDMRX_E_ARG;
-	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)channelize_max_outputs(q) || out_stride > (size_t)FAR / 65536)
+	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)(grid ? channelize_grid_max_outputs() : channelize_max_outputs(q)) || out_stride > (size_t)FAR / 65536)
 		return OFDMRX_E_ARG;
 	const size_t unit = 2 * sample_bytes(sample_format);
 	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))
@@ -151,12 +208,15 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 		if (a < b + out_bytes && b < a + n_in * unit)
 			return OFDMRX_E_ARG;
 	}
-	for (size_t c = 0; c < n_channels; ++c)
+	std::vector<int32_t> slot_list;
+	if (grid && channelize_grid_slots(p, slots, n_channels, slot_list))
+		return OFDMRX_E_ARG;
+	for (size_t c = 0; c < n_channels && !grid; ++c)
 		if (!std::isfinite(centre_hz[c]))
 			return OFDMRX_E_ARG;
 	if (h->busy_live())                                           // (an open wideband bank owns the taps and increments on the device)
 		return OFDMRX_E_ARG;
-	int r = channelize_setup(h, p, q, centre_hz, n_channels);
+	int r = grid ? channelize_grid_setup(h, p, slot_list) : channelize_setup(h, p, q, centre_hz, n_channels);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -167,15 +227,17 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 	a.q = q;
 	a.in_first = in_first;
 	a.n_in = (long long)n_in;
-	a.taps = h->chz_taps.as<float>();
-	a.inc = h->chz_inc.as<unsigned>();
+	channelize_tables(h, a);
 	a.n_channels = (int)n_channels;
 	a.out_first = out_first;
 	a.n_out = (long long)n_out;
 	a.out = d_out;
 	a.out_stride = (long long)out_stride;
 	a.dst = nullptr;
-	launch_channelize(h->stream, a);
+	if (a.grid)
+		launch_channelize_grid(h->stream, a);
+	else
+		launch_channelize(h->stream, a);
 	HIP_OK(hipGetLastError());
 	return 0;
 }
@@ -194,4 +256,19 @@ extern "C" int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, 
 	if (rechannelize_ratio(p, q))
 		return OFDMRX_E_ARG;
 	return channelize_call(h, d_in, sample_format, in_first, n_in, p, q, centre_hz, n_channels, out_first, n_out, d_out, out_stride);
+}
+
+extern "C" int ofdmrx_util_channelize_grid_taps(int decim, float *taps)
+{
+	if (channelize_grid_decim(decim) || !taps)
+		return OFDMRX_E_ARG;
+	return channelize_taps(decim, taps);
+}
+
+extern "C" int ofdmrx_util_channelize_grid(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	const int32_t *slots, size_t n_slots, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+{
+	if (channelize_grid_decim(decim))
+		return OFDMRX_E_ARG;
+	return channelize_call(h, d_in, sample_format, in_first, n_in, decim, 1, nullptr, n_slots, out_first, n_out, d_out, out_stride, true, slots);
 }

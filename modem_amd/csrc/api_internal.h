@@ -230,6 +230,8 @@ struct ofdmrx_handle {
 	// from - the reduced ratio chz_p / chz_q (an integer decimation D is D / 1; 0 / 0: none) and the host copies the uploads read
 	DevBuf chz_taps, chz_inc;
 	int chz_p = 0, chz_q = 0;
+	bool chz_grid = false;               // the table is a grid table: the roots of the transform stand behind the taps (at chz_tw_at floats)
+	size_t chz_tw_at = 0;
 	std::vector<float> chz_taps_h;
 	std::vector<unsigned> chz_inc_h;
 	// the wideband synthesizer (api_synthesize.cpp): a small ring of parameter sets - the channels' (start, inc, gain) and the taps
@@ -297,4 +299,11 @@ int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, 
 // p / q -> lowest terms; OFDMRX_E_ARG unless p, q > 0, the reduced q <= 16 and 2 <= p / q <= 32
 int rechannelize_ratio(int &p, int &q);                                                     // api_channelize.cpp
 int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels);   // (p / q reduced; q = 1: decimation p)
+// the grid front end: decim a power of two 2 .. 512 (else OFDMRX_E_ARG); the slots of a grid table, -decim ..
+// decim - 1 each (slots = nullptr: all 2 decim in ascending order, n_slots must be 2 decim), and the table itself on the device
+int channelize_grid_decim(int decim);
+int channelize_grid_slots(int decim, const int32_t *slots, size_t n_slots, std::vector<int32_t> &out);
+int channelize_grid_setup(ofdmrx_handle *h, int decim, const std::vector<int32_t> &slots);
+// the ChannelizeArgs fields the device tables give: taps, inc, grid, tw (the table set up last)
+void channelize_tables(const ofdmrx_handle *h, ChannelizeArgs &a);
 void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank (or feed) and its windows go

@@ -19,6 +19,10 @@
 // on stderr, and then exactly the form above runs with that list.  The file is read twice, so `auto` does not take standard input.
 // DECIM may be a ratio P/Q in both forms - it is one when it holds a '/' (Q <= 16, 2 <= P / Q <= 32): the
 // capture's rate x Q / P must be a supported rate, and the bank is opened with ofdmrx_bank_begin_wideband_ratio.
+// `decode_stream --grid DECIM K1,K2,...|all OUTROOT WIDE.wav`: the same through the grid front end (DESIGN.md section 4.19,
+// ofdmrx_bank_begin_wideband_grid): DECIM a power of two 2 .. 512, the capture's rate DECIM x a supported rate, channel i the slot Ki
+// (-DECIM .. DECIM - 1; `all`: every slot in ascending order) centred at Ki x rate / 2.  Every opened slot's centre is printed on
+// stderr first; the files and lines are those of --wideband.
 #include "survey_cli.h"
 #include <algorithm>
 #include <cstdlib>
@@ -325,10 +329,38 @@ static std::string survey_centres(const Decimation &decim, const char *input_nam
 	return list;
 }
 
-// one wideband capture block by block through a wideband bank
-static int run_wideband(const Decimation &decim, const char *centre_list, const std::string &outroot, const char *input_name)
+// one wideband capture block by block through a wideband bank (grid: through a grid bank - centre_list holds slot numbers, or `all`)
+static int run_wideband(const Decimation &decim, const char *centre_list, const std::string &outroot, const char *input_name, bool grid = false)
 {
 	std::vector<double> centres;
+	std::vector<int32_t> slots;
+	if (grid) {
+		if (decim.ratio || decim.p < 2 || decim.p > 512 || (decim.p & (decim.p - 1))) {
+			std::fprintf(stderr, "A grid bank takes a decimation that is a power of two 2 .. 512.\n");
+			return 1;
+		}
+		if (!std::strcmp(centre_list, "all")) {
+			for (int k = -decim.p; k < decim.p; ++k)
+				slots.push_back(k);
+		} else {
+			for (const char *p = centre_list; *p;) {
+				char *e = nullptr;
+				const long k = std::strtol(p, &e, 10);
+				if (e == p || (*e && *e != ',') || k < -decim.p || k > decim.p - 1) {
+					std::fprintf(stderr, "Slots are `all` or a comma-separated list of numbers %d .. %d.\n", -decim.p, decim.p - 1);
+					return 1;
+				}
+				slots.push_back((int32_t)k);
+				p = *e ? e + 1 : e;
+			}
+		}
+		if (slots.empty() || slots.size() > 65535) {
+			std::fprintf(stderr, "A grid bank takes 1 .. 65535 slots.\n");
+			return 1;
+		}
+		centres.assign(slots.size(), 0.0);                            // (filled in below, once the rate is known)
+		centre_list = "";
+	}
 	for (const char *p = centre_list; *p;) {
 		char *e = nullptr;
 		const double f = std::strtod(p, &e);
@@ -339,7 +371,7 @@ static int run_wideband(const Decimation &decim, const char *centre_list, const 
 		centres.push_back(f);
 		p = *e ? e + 1 : e;
 	}
-	if (!decim.valid() || centres.empty() || centres.size() > 65535) {
+	if ((!grid && !decim.valid()) || centres.empty() || centres.size() > 65535) {
 		std::fprintf(stderr, "A wideband bank takes a decimation of 2 .. 32 (a ratio P/Q: Q <= 16) and 1 .. 65535 centre frequencies.\n");
 		return 1;
 	}
@@ -368,7 +400,12 @@ static int run_wideband(const Decimation &decim, const char *centre_list, const 
 		prefixes[i] = std::to_string(i) + ":";
 		(void)mkdir(dirs[i].c_str(), 0777);
 	}
-	int r = decim.ratio ? ofdmrx_bank_begin_wideband_ratio(h, S, centres.data(), decim.p, decim.q, w.fmt)
+	for (size_t i = 0; i < S && grid; ++i) {
+		centres[i] = (double)slots[i] * 0.5 * (double)decim.rate_of(w.rate);
+		std::fprintf(stderr, "%zu: slot %d, centre %.17g Hz\n", i, (int)slots[i], centres[i]);
+	}
+	int r = grid ? ofdmrx_bank_begin_wideband_grid(h, S, slots.data(), decim.p, w.fmt)
+		: decim.ratio ? ofdmrx_bank_begin_wideband_ratio(h, S, centres.data(), decim.p, decim.q, w.fmt)
 		: ofdmrx_bank_begin_wideband(h, S, centres.data(), decim.p, w.fmt);
 	std::vector<uint8_t> out(cap * OFDMRX_PAYLOAD_BYTES), pcm;
 	std::vector<ofdmrx_frame_result> res(cap);
@@ -413,14 +450,16 @@ int main(int argc, char **argv)
 	}
 	if (argc == 6 && !std::strcmp(argv[1], "--wideband"))
 		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5]);
+	if (argc == 6 && !std::strcmp(argv[1], "--grid"))
+		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5], true);
 	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
 		return run_live_batch(argv[3], argc - 4, argv + 4);
 	if (argc >= 4 && !std::strcmp(argv[1], "--batch"))
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n",
-			argv[0], argv[0], argv[0]);
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM K1,K2,...|all OUTROOT INPUT\n",
+			argv[0], argv[0], argv[0], argv[0]);
 		return 1;
 	}
 	const std::string outdir = argv[live ? 2 : 1];

@@ -355,11 +355,18 @@ struct ChannelizeArgs {
 	float *out;
 	long long out_stride;          // I/Q pairs per channel row
 	const long long *dst;          // device, [n_channels] addresses, nullable
+	// the grid front end (k_channelize_grid.hip): grid != 0, q = 1, p = D a power of two 2 .. 512, M = 2 D; channel c is
+	// slot k_c = inc[c] >> (32 - log2 M) (inc[c] = k_c 2^32 / M mod 2^32: the increment of its centre k_c rate / 2, exactly);
+	// tw: device, the M / 2 roots e^{+2 pi i j / M}, rounded once from double
+	int grid;
+	const float2 *tw;
 };
 // k_channelize where a.q == 1, k_rechannelize (launch_channelize_ratio) otherwise: each keeps its own summation order (see the files)
 void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
 void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a);   // k_rechannelize.hip: launch_channelize's q > 1
 long long channelize_max_outputs(int q);
+void launch_channelize_grid(hipStream_t s, const ChannelizeArgs &a);    // k_channelize_grid.hip: a.grid != 0 (the callers choose)
+long long channelize_grid_max_outputs();
 // what a workgroup's tile of k_rechannelize looks like: T, the outputs per residue M (a tile is q M outputs), the rows of history,
 // the rows of a plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
 struct RechannelizeShape { int n_taps, m, hist, rows, passes; size_t lds; };

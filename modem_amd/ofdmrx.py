@@ -38,6 +38,7 @@ EXPORTS = [
     "ofdmrx_util_survey_window", "ofdmrx_util_survey", "ofdmrx_util_find_bands",
     "ofdmrx_util_channelize_ratio_taps", "ofdmrx_util_channelize_ratio", "ofdmrx_bank_begin_wideband_ratio",
     "ofdmrx_util_synthesize_ratio",
+    "ofdmrx_util_channelize_grid_taps", "ofdmrx_util_channelize_grid", "ofdmrx_bank_begin_wideband_grid",
 ]
 
 
@@ -103,6 +104,34 @@ def channelize_taps(decim):
     if n != taps.size:
         raise OfdmRxError("channelize_taps: decim must be 2 .. 32")
     return taps
+
+
+def channelize_grid_taps(decim):
+    """the 24 decim + 1 fp32 taps of the grid front end's prototype low pass for decimation decim (a power of two 2 .. 512): DESIGN.md
+    section 4.19; for decim <= 32 they are channelize_taps(decim)"""
+    decim = int(decim)
+    taps = np.zeros(24 * min(max(decim, 0), 512) + 1, np.float32)
+    n = load_library().ofdmrx_util_channelize_grid_taps(decim, _ptr(taps))
+    if n != taps.size:
+        raise OfdmRxError("channelize_grid_taps: decim must be a power of two 2 .. 512")
+    return taps
+
+
+def _grid_slots(decim, slots):
+    """-> the slots of a grid of decimation decim as int32 (None: all 2 decim of them, ascending)"""
+    decim = int(decim)
+    if decim < 2 or decim > 512 or decim & (decim - 1):
+        raise OfdmRxError("grid: decim must be a power of two 2 .. 512")
+    k = np.arange(-decim, decim, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+    if k.size < 1 or k.size > 65535 or k.min() < -decim or k.max() > decim - 1:
+        raise OfdmRxError("grid: 1 .. 65535 slots, each -decim .. decim - 1")
+    return k
+
+
+def grid_centres(decim, rate, slots=None):
+    """the centre frequencies in Hz of the slots of the grid front end: slot k of decimation decim at the
+    handle rate `rate` lies at k rate / 2, k = -decim .. decim - 1 (slots None: all of them, ascending)"""
+    return _grid_slots(decim, slots).astype(np.float64) * (float(rate) / 2.0)
 
 
 def _ratio(decim):
@@ -287,6 +316,10 @@ def load_library():
     L.ofdmrx_util_channelize_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
                                                C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_bank_begin_wideband_ratio.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.ofdmrx_util_channelize_grid_taps.argtypes = [C.c_int, C.c_void_p]
+    L.ofdmrx_util_channelize_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                              C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.ofdmrx_bank_begin_wideband_grid.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     L.ofdmrx_util_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_util_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -439,6 +472,11 @@ class Receiver:
         the centre frequencies centres_hz: push the capture block by block.  decim: an int, or a ratio - a pair (p, q) or a
         fractions.Fraction"""
         return WidebandBank(self, centres_hz, decim, dtype, esn0_rows)
+
+    def wideband_grid_bank(self, slots, decim, dtype=np.int16, esn0_rows=False):
+        """open a bank whose channels are slots of the raster rate / 2 of one wideband I/Q capture at decim x the handle's rate (decim a
+        power of two 2 .. 512; slots None: all 2 decim): push the capture block by block"""
+        return WidebandGridBank(self, slots, decim, dtype, esn0_rows)
 
     def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
         """device pointers (ints), or pinned host outputs; -> n_preambles (the call synchronises once, after the scan)"""
@@ -670,6 +708,14 @@ class Receiver:
             return
         self._check(self._lib.ofdmrx_util_channelize(self._h, d_in, fmt, in_first, n_in, decim, _ptr(f), f.size, out_first, n_out, d_out,
                                                      n_out if out_stride is None else out_stride))
+
+    def channelize_grid(self, d_in, fmt, in_first, n_in, decim, slots, out_first, n_out, d_out, out_stride=None):
+        """the grid front end on device buffers (ints): as channelize, for a decim that is a power of two 2 ..
+        512 and channels on the raster rate / 2: row j of the output is slot slots[j] (-decim .. decim - 1; None: every slot, ascending),
+        centred at grid_centres(decim, rate, slots)[j]"""
+        k = _grid_slots(decim, slots)
+        self._check(self._lib.ofdmrx_util_channelize_grid(self._h, d_in, fmt, in_first, n_in, int(decim), _ptr(k), k.size, out_first, n_out,
+                                                          d_out, n_out if out_stride is None else out_stride))
 
     def synthesize(self, d_in, in_fmt, n_in, interp, centres_hz, starts, gains, out_first, n_out, d_out, out_fmt, in_stride=None):
         """the wideband synthesizer on device buffers (ints): channel c's n_in sample frames (interleaved I/Q of in_fmt, S16 or F32) lie
@@ -934,3 +980,19 @@ class WidebandBank(Bank):
         n = pcm.shape[0]
         return self._call(lambda first, cap, o, r, ch, ix, a, b: self._lib.ofdmrx_bank_push_wideband(
             self._h, _ptr(pcm) if n and first else None, n if first else 0, 1 if end and first else 0, cap, o, r, ch, ix, a, b), max_records)
+
+
+class WidebandGridBank(WidebandBank):
+    """A wideband bank whose channels are slots of the grid front end (ofdmrx_bank_begin_wideband_grid): channel
+    j is slot slots[j], centred at centres_hz[j]; push and end are WidebandBank's.  The records of channel j are what
+    Receiver.decode_stream returns for row j of Receiver.channelize_grid over the whole capture, however it is cut."""
+
+    def __init__(self, rx, slots, decim, dtype=np.int16, esn0_rows=False):
+        self._rx, self._lib, self._h = rx, rx._lib, rx._h
+        k = _grid_slots(decim, slots)
+        self.slots, self.decim, self.centres_hz = k, int(decim), grid_centres(decim, rx.sample_rate, k)
+        self.n_channels, self.channels, self.dtype, self._rows = k.size, 2, np.dtype(dtype), bool(esn0_rows)
+        rx._check(self._lib.ofdmrx_bank_begin_wideband_grid(self._h, k.size, _ptr(k), self.decim, rx._fmt(self.dtype)))
+        self.open = True
+        self.n_left = 0
+        self._ops = 0

@@ -11,6 +11,11 @@ data (host wall time: these calls block).
 DESIGN.md section 4.17): for 1, 16 and 256 channels, beside k_channelize at the neighbouring integer D on the same bytes, beside
 k_awgn_tile and the arithmetic floor N n_out T 4 FMAs, with the time per FMA relative to k_channelize's; then one wideband second x
 64 channels through the ratio bank.
+--grid D [SLOTS] (repeatable; SLOTS a comma list, default all 2 D; D:SLOTS where the list begins with a negative slot) times the grid front end instead (ofdmrx_util_channelize_grid,
+k_channelize_grid.hip) beside three yardsticks: k_awgn_tile on the same bytes; the arithmetic floor - per
+output time 13 M real-by-complex multiply-adds (2 FMAs each) and (M / 2) log2 M butterflies of 8 operations - at the same 0.86 ns per
+wave64 FMA and SIMD; and, for D <= 32, k_channelize on the same centres in the same run.  Then one wideband second through the grid
+bank with those slots.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import ctypes as C
@@ -217,8 +222,97 @@ def child_ratio(args):
     print(json.dumps({"tool": "channelize_bench", "samples": W, "ratio_rows": rows, "ratio_banks": banks}), flush=True)
 
 
+def child_grid(args):
+    import numpy as np
+    import torch
+    import modem_amd
+    import modem_amd.ofdmrx as M
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    W = args.samples
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    d_in = torch.randint(-20000, 20000, (W, 2), dtype=torch.int16, device=dev, generator=gen)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    grids = []
+    for g in args.grid:                                               # D, D SLOTS or D:SLOTS (a list that begins with a negative slot)
+        g = g[0].split(":") if ":" in g[0] else g
+        grids.append((int(g[0]), None if len(g) < 2 else [int(t) for t in g[1].split(",")]))
+    rows = []
+    for D, slots in grids:
+        Mm = 2 * D
+        N = Mm if slots is None else len(slots)
+        n_out = -(-W // D)
+        d_out = torch.empty((N, n_out, 2), dtype=torch.float32, device=dev)
+        ms = timed(lambda k: rx.channelize_grid(d_in.data_ptr(), 0, 0, W, D, slots, 0, n_out, d_out.data_ptr()))
+        plain = None
+        if D <= 32:                                                  # the direct form on the same centres, in the same run
+            f = modem_amd.grid_centres(D, 8000, slots)
+            plain = timed(lambda k: rx.channelize(d_in.data_ptr(), 0, 0, W, D, f, 0, n_out, d_out.data_ptr()))
+        nbytes = W * 4 + N * n_out * 8
+        spf = 4096
+        frames = max(1, nbytes // (2 * spf * 4))
+        d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+        d_b = torch.empty_like(d_a)
+        awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+        ops = n_out * (13 * Mm * 2 + (Mm // 2) * (Mm.bit_length() - 1) * 8)
+        floor = ops / 64.0 * FMA_NS * 1e-6 / SIMDS
+        rows.append(dict(decim=D, slots=N, n_out=n_out, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1),
+                         k_channelize_ms=None if plain is None else round(plain, 4), speedup=None if plain is None else round(plain / ms, 2),
+                         awgn_tile_ms=round(awgn, 4), floor_ms=round(floor, 4), nearer="arithmetic" if floor > awgn else "memory",
+                         over_bound=round(ms / max(floor, awgn), 2)))
+        del d_out, d_a, d_b
+    rx.close()
+
+    outs = (np.zeros((64, 5380), np.uint8), np.zeros(64, M.RESULT_DTYPE), np.zeros(64, np.int32), np.zeros(64, np.int64))
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    p = M._ptr
+    banks = []
+    for D, slots in grids:
+        sec = 8000 * D
+        rng = np.random.default_rng(2)
+        cap = rng.integers(-300, 300, size=(sec, 2)).astype(np.int16)
+        rxw = modem_amd.Receiver(device=0)
+        L, h = rxw._lib, rxw._h
+        k = M._grid_slots(D, slots)
+        assert L.ofdmrx_bank_begin_wideband_grid(h, k.size, p(k), D, 0) == 0
+        wide = []
+        for _ in range(args.warmup + args.reps):
+            t = time.perf_counter()
+            assert L.ofdmrx_bank_push_wideband(h, p(cap), sec, 0, 64, p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), C.byref(a), C.byref(b)) == 0
+            wide.append((time.perf_counter() - t) * 1e3)
+        ops = int(L.ofdmrx_bank_last_stage_ops(h))
+        rxw.close()
+        banks.append(dict(decim=D, slots=int(k.size), wideband_samples=sec, push_ms=round(statistics.median(wide[args.warmup:]), 3), stage_ops=ops))
+    print("decim slots   n_out      ms    GB/s  k_channelize ms  speedup  awgn_tile ms  floor ms  nearer bound  time / bound")
+    for r in rows:
+        print("%5d %5d %7d %7.4f %7.1f %16s %8s %13.4f %9.4f  %-12s %6.2f"
+              % (r["decim"], r["slots"], r["n_out"], r["ms"], r["gb_per_s"], "-" if r["k_channelize_ms"] is None else "%.4f" % r["k_channelize_ms"],
+                 "-" if r["speedup"] is None else "%.2f" % r["speedup"], r["awgn_tile_ms"], r["floor_ms"], r["nearer"], r["over_bound"]))
+    for k in banks:
+        print("one wideband second (%d samples, D = %d) x %d slots through the grid bank: push %.3f ms (%d stage ops)"
+              % (k["wideband_samples"], k["decim"], k["slots"], k["push_ms"], k["stage_ops"]))
+    print(json.dumps({"tool": "channelize_bench", "samples": W, "grid_rows": rows, "grid_banks": banks}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", action="append", nargs="+", default=[], metavar="D", help="time the grid front end at decimation D [SLOTS] (repeatable)")
     ap.add_argument("--ratio", action="append", default=[], metavar="P/Q", help="time the front end at this rational decimation (repeatable)")
     ap.add_argument("--samples", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=7)
@@ -227,10 +321,12 @@ def main():
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
-        return child_ratio(args) if args.ratio else child(args)
+        return child_grid(args) if args.grid else child_ratio(args) if args.ratio else child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
     for r in args.ratio:
         cmd += ["--ratio", r]
+    for g in args.grid:
+        cmd += ["--grid"] + g
     try:
         return subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
