@@ -62,7 +62,8 @@ extern "C" {
  *      ofdmrx_util_survey, ofdmrx_util_find_bands; the wideband front end at a rational decimation -
  *      ofdmrx_util_channelize_ratio_taps, ofdmrx_util_channelize_ratio, ofdmrx_bank_begin_wideband_ratio; the wideband synthesizer
  *      at a rational interpolation - ofdmrx_util_synthesize_ratio; the wideband front end on a channel grid (a polyphase filter bank) -
- *      ofdmrx_util_channelize_grid_taps, ofdmrx_util_channelize_grid, ofdmrx_bank_begin_wideband_grid */
+ *      ofdmrx_util_channelize_grid_taps, ofdmrx_util_channelize_grid, ofdmrx_bank_begin_wideband_grid; the wideband synthesizer on
+ *      a channel grid (a polyphase synthesis bank) - ofdmrx_util_synthesize_grid, ofdmrx_util_synthesize_grid_chunk */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -712,6 +713,30 @@ int ofdmrx_util_synthesize(ofdmrx_handle *h, const void *d_in, int in_format, si
 int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
 	const double *centre_hz, const long long *start, const float *gain, size_t n_channels, long long out_first, size_t n_out,
 	void *d_out, int out_format);
+
+/* Wideband synthesizer on a channel grid (added within revision 1.9, detected by symbol), the mirror image of the front end on a
+ * channel grid: a polyphase synthesis bank for rows on the raster rate / 2, interp a power of two 2 .. 512.  DESIGN.md section 4.20
+ * is the definition, held component by component to a float64 model.  With D = interp, M = 2 D, T = 24 D + 1 and h[k] the fp32 taps
+ * ofdmrx_util_channelize_grid_taps(D, .) writes - there is no new filter - row c belongs to slot k_c = slots[c] in -M/2 .. M/2 - 1
+ * (a host array of pairwise distinct slots; NULL with n_slots = M: every slot in ascending k), with its centre at k_c rate / 2:
+ *   output  w[m] = sum_c G_c e^{+2 pi i k_c m / M} sum_j h[m - start[c] - j D] x_c[j], over the j with 0 <= m - start[c] - j D <=
+ *           T - 1; G_c = D gain[c] as in ofdmrx_util_synthesize; start[c] >= 0 in wideband samples, a MULTIPLE OF D.
+ * This is ofdmrx_util_synthesize's output for the centres k_c rate / 2 (within the two tolerances: the sums are formed in another
+ * order), at a cost per output that does not grow with the number of rows: one M-point transform per input time shared by all
+ * slots, one pass of the filter, no NCO.  F32 and S16 output as ofdmrx_util_synthesize writes them: a zero always +0, never
+ * -32768.  No state: a capture made window by window has the bytes of one made in one call.  Through ofdmrx_util_channelize_grid
+ * at the same D and slot, sample j of row c comes out at index j + 24 + start[c] / D, exactly.
+ * Arguments, memory spaces, asynchrony and the ring of parameter sets (a grid set is never taken for a plain one at the same D, nor
+ * the reverse) are ofdmrx_util_synthesize's.  The handle keeps a scratch buffer of at most 32 MiB and cuts a call into chunks of
+ * ofdmrx_util_synthesize_grid_chunk(interp) outputs, counted from out_first rounded down to a multiple of D; a seam changes no byte.
+ * OFDMRX_E_ARG, before any device call and with the output untouched: everything ofdmrx_util_synthesize refuses except its range of
+ * interp; an interp that is no power of two in 2 .. 512; a slot outside -M/2 .. M/2 - 1 or given twice; n_slots outside 1 .. M;
+ * NULL slots with n_slots != M; a start that interp does not divide.
+ * ofdmrx_util_synthesize_grid_chunk: host only; the outputs per chunk (a multiple of D), OFDMRX_E_ARG for such an interp. */
+int ofdmrx_util_synthesize_grid(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
+	const int32_t *slots, const long long *start, const float *gain, size_t n_slots, long long out_first, size_t n_out,
+	void *d_out, int out_format);
+long long ofdmrx_util_synthesize_grid_chunk(int interp);
 
 /* Wideband survey (added within revision 1.9, detected by symbol): which bands of a wideband capture are occupied - the centres to
  * open the front end or a wideband bank on.  DESIGN.md section 4.16 is the definition, held bin by bin to a float64 model.

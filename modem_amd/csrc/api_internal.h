@@ -242,11 +242,14 @@ struct ofdmrx_handle {
 		std::vector<SynthChannel> ch;   // (the host copy the upload reads: it lives as long as the slot)
 		std::vector<float> taps;
 		int p = 0, q = 0;               // the reduced ratio the set was made for (q = 1: the integer synthesizer's interp); 0: none
+		bool grid = false;              // a grid set: inc spells the slot, the M / 2 roots stand behind the taps (at tw_at floats)
+		size_t tw_at = 0;
 		hipEvent_t done = nullptr;
 		~SynSlot() { if (done) (void)hipEventDestroy(done); }
 	};
 	SynSlot syn[4];
 	int syn_cur = 0;
+	DevBuf syn_scratch;                  // the grid synthesizer's V of one chunk (api_synthesize.cpp: SYG_SCRATCH_BYTES at most)
 	// the wideband survey (api_survey.cpp): per transform length (1280, 2560, 5120) the window and the roots on the device, uploaded
 	// on the first call with that length and never written again; the partials of the last call (grown on demand)
 	struct SurveyPlan {

@@ -18,11 +18,13 @@ static void resynthesize_taps(int p, int q, std::vector<float> &rows)
 // last launch that read it is over (the upload reads the slot's own host copy, which nothing touches before then either)
 // q = 1: the 24 p + 1 taps of the integer synthesizer at interp p; q > 1: the ratio's taps transposed, [p][RSY_ROW].  The taps lie
 // behind the channels (16 bytes each), so they begin on a 16-byte boundary
-static int synthesize_setup(ofdmrx_handle *h, int p, int q, const std::vector<SynthChannel> &ch, const ofdmrx_handle::SynSlot **out)
+// grid: a grid set (q = 1, the M / 2 = p roots of the transform behind the taps, on an 8-byte boundary); it is part
+// of the key, so a grid call after a plain call at the same D uploads anew, and the reverse
+static int synthesize_setup(ofdmrx_handle *h, int p, int q, bool grid, const std::vector<SynthChannel> &ch, const ofdmrx_handle::SynSlot **out)
 {
 	constexpr int RING = (int)(sizeof(h->syn) / sizeof(h->syn[0]));
 	ofdmrx_handle::SynSlot *s = &h->syn[h->syn_cur];
-	if (s->p == p && s->q == q && s->ch.size() == ch.size() && !std::memcmp(s->ch.data(), ch.data(), ch.size() * sizeof(SynthChannel))) {
+	if (s->p == p && s->q == q && s->grid == grid && s->ch.size() == ch.size() && !std::memcmp(s->ch.data(), ch.data(), ch.size() * sizeof(SynthChannel))) {
 		*out = s;
 		return 0;
 	}
@@ -41,6 +43,16 @@ static int synthesize_setup(ofdmrx_handle *h, int p, int q, const std::vector<Sy
 	} else {
 		resynthesize_taps(p, q, s->taps);
 	}
+	s->tw_at = 0;
+	if (grid) {                                                   // e^{+2 pi i j / M}, j = 0 .. M / 2 - 1, as the grid front end makes them
+		const double pi = 3.14159265358979323846;
+		s->tw_at = (s->taps.size() + 1) / 2 * 2;
+		s->taps.resize(s->tw_at + 2 * (size_t)p, 0.f);
+		for (int j = 0; j < p; ++j) {
+			s->taps[s->tw_at + 2 * (size_t)j] = (float)std::cos(pi * (double)j / (double)p);
+			s->taps[s->tw_at + 2 * (size_t)j + 1] = (float)std::sin(pi * (double)j / (double)p);
+		}
+	}
 	const size_t ch_bytes = ch.size() * sizeof(SynthChannel), tap_bytes = s->taps.size() * sizeof(float);
 	const int r = s->dev.ensure(ch_bytes + tap_bytes);
 	if (r)
@@ -50,6 +62,7 @@ static int synthesize_setup(ofdmrx_handle *h, int p, int q, const std::vector<Sy
 	HIP_OK(hipEventRecord(s->done, h->stream));                   // (a failed launch below still leaves the slot waitable)
 	s->p = p;
 	s->q = q;
+	s->grid = grid;
 	*out = s;
 	return 0;
 }
@@ -90,7 +103,7 @@ static int synthesize_call(ofdmrx_handle *h, const void *d_in, int in_format, si
 	if (h->busy_live())
 		return OFDMRX_E_ARG;
 	const ofdmrx_handle::SynSlot *slot = nullptr;
-	int r = synthesize_setup(h, p, q, ch, &slot);
+	int r = synthesize_setup(h, p, q, false, ch, &slot);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -130,4 +143,110 @@ extern "C" int ofdmrx_util_synthesize_ratio(ofdmrx_handle *h, const void *d_in, 
 	if (rechannelize_ratio(p, q))
 		return OFDMRX_E_ARG;
 	return synthesize_call(h, d_in, in_format, in_stride, n_in, p, q, centre_hz, start, gain, n_channels, out_first, n_out, d_out, out_format);
+}
+
+// ---- the synthesizer on a channel grid.  The scratch holds V - M float2 per input time, two per output - so a call
+// is cut into chunks of output times; a chunk's transform launch includes the 24 times before it, and V_j is a function of j alone,
+// so a seam changes no byte.  SYG_SCRATCH_BYTES bounds the scratch: well inside the 256 MiB last-level cache
+#ifndef SYG_SCRATCH_BYTES
+#define SYG_SCRATCH_BYTES (32u << 20)
+#endif
+
+// output times per chunk at interpolation D: whole tiles of the filter kernel, with the 24 times of history and the round-up to
+// whole tiles of the transform kernel inside the bound
+static long long synthesize_grid_chunk_times(int D)
+{
+	const long long per_time = 2LL * D * (long long)sizeof(float2), tile = synthesize_grid_tile_times(D), ft = synthesize_grid_filter_times(D);
+	const long long fit = ((long long)SYG_SCRATCH_BYTES / per_time - 24 - tile) / ft * ft;
+	return fit > ft ? fit : ft;
+}
+
+extern "C" long long ofdmrx_util_synthesize_grid_chunk(int interp)
+{
+	if (channelize_grid_decim(interp))
+		return OFDMRX_E_ARG;
+	return synthesize_grid_chunk_times(interp) * interp;
+}
+
+extern "C" int ofdmrx_util_synthesize_grid(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int interp,
+	const int32_t *slots, const long long *start, const float *gain, size_t n_slots, long long out_first, size_t n_out, void *d_out,
+	int out_format)
+{
+	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
+	if (!h || !d_in || !d_out || !start || !gain || !n_in || !n_out || channelize_grid_decim(interp))
+		return OFDMRX_E_ARG;
+	const int D = interp, M = 2 * D;
+	if (n_slots < 1 || n_slots > (size_t)M || (!slots && n_slots != (size_t)M))
+		return OFDMRX_E_ARG;
+	if ((in_format != OFDMRX_FMT_S16 && in_format != OFDMRX_FMT_F32) || (out_format != OFDMRX_FMT_S16 && out_format != OFDMRX_FMT_F32) ||
+		in_stride < n_in || out_first < 0)
+		return OFDMRX_E_ARG;
+	if (out_first > FAR || in_stride > (size_t)FAR / 65536 || n_out > (size_t)synthesize_max_outputs(1))
+		return OFDMRX_E_ARG;
+	const size_t in_unit = 2 * sample_bytes(in_format), out_unit = 2 * sample_bytes(out_format);
+	if ((size_t)d_in % in_unit || (size_t)d_out % out_unit)
+		return OFDMRX_E_ARG;
+	{
+		const char *a = (const char *)d_in, *b = (const char *)d_out;
+		const size_t in_bytes = ((n_slots - 1) * in_stride + n_in) * in_unit;
+		if (a < b + n_out * out_unit && b < a + in_bytes)
+			return OFDMRX_E_ARG;
+	}
+	std::vector<int32_t> slot_list;
+	if (channelize_grid_slots(D, slots, n_slots, slot_list))
+		return OFDMRX_E_ARG;
+	const unsigned step = (unsigned)(4294967296ULL / (unsigned long long)M);
+	std::vector<SynthChannel> ch(n_slots);
+	std::vector<char> taken((size_t)M, 0);
+	for (size_t c = 0; c < n_slots; ++c) {
+		char &t = taken[(size_t)(slot_list[c] + M / 2)];
+		if (t || !std::isfinite(gain[c]) || start[c] < 0 || start[c] > FAR || start[c] % D)
+			return OFDMRX_E_ARG;                                      // a slot given twice; a start the interpolation does not divide
+		t = 1;
+		ch[c].start = start[c];
+		ch[c].inc = (unsigned)slot_list[c] * step;                    // k 2^32 / M mod 2^32: what channelize_inc gives for k rate / 2, without a rounding
+		ch[c].gain = (float)((double)D * (double)gain[c]);
+		if (!std::isfinite(ch[c].gain))
+			return OFDMRX_E_ARG;
+	}
+	if (h->busy_live())
+		return OFDMRX_E_ARG;
+	const ofdmrx_handle::SynSlot *slot = nullptr;
+	int r = synthesize_setup(h, D, 1, true, ch, &slot);
+	if (r)
+		return r;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	const long long q_lo = out_first / D, q_hi = (out_first + (long long)n_out - 1) / D, nq_all = q_hi - q_lo + 1;
+	const long long chunk = synthesize_grid_chunk_times(D), tile = synthesize_grid_tile_times(D);
+	// the times a launch's scratch holds: the chunk's own, rounded up to the filter's 8 per work item, the 24 before, whole tiles
+	auto times_of = [&](long long nq) { return ((nq + 7) / 8 * 8 + 24 + tile - 1) / tile * tile; };
+	r = h->syn_scratch.ensure((size_t)times_of(nq_all < chunk ? nq_all : chunk) * (size_t)M * sizeof(float2));
+	if (r)
+		return r;
+	SynthesizeGridArgs a{};
+	a.in = d_in;
+	a.in_fmt = in_format;
+	a.out_fmt = out_format;
+	a.p = D;
+	a.in_stride = (long long)in_stride;
+	a.n_in = (long long)n_in;
+	a.ch = slot->dev.as<SynthChannel>();
+	a.taps = (const float *)((const char *)slot->dev.p + n_slots * sizeof(SynthChannel));
+	a.tw = (const float2 *)(a.taps + slot->tw_at);
+	a.n_channels = (int)n_slots;
+	a.out_first = out_first;
+	a.n_out = (long long)n_out;
+	a.out = d_out;
+	a.scratch = h->syn_scratch.as<float2>();
+	for (long long at = 0; at < nq_all; at += chunk) {
+		const long long nq = nq_all - at < chunk ? nq_all - at : chunk;
+		a.q_first = q_lo + at;
+		a.j_first = a.q_first - 24;
+		a.nq = (int)nq;
+		a.n_times = (int)times_of(nq);
+		launch_synthesize_grid(h->stream, a);
+		HIP_OK(hipGetLastError());
+	}
+	HIP_OK(hipEventRecord(slot->done, h->stream));
+	return 0;
 }

@@ -406,6 +406,32 @@ void launch_synthesize(hipStream_t s, const SynthesizeArgs &a);
 void launch_synthesize_ratio(hipStream_t s, const SynthesizeArgs &a);   // k_resynthesize.hip: launch_synthesize's q > 1
 long long synthesize_max_outputs(int q);
 
+// ---- the wideband synthesizer on a channel grid (k_synthesize_grid.hip): n_channels rows, row c in slot
+// k_c = ch[c].inc >> (32 - log2 M) (inc = k_c 2^32 / M mod 2^32, as in 4.19), ch[c].start a multiple of D = p, the slots pairwise
+// distinct -> one wideband capture at D times their rate.  One launch makes a chunk of output times q = q_first .. q_first + nq - 1
+// (output m belongs to time m div D) and writes the outputs of those times that lie in out_first .. out_first + n_out - 1.
+// scratch: device, n_times M float2 - V of the absolute input times j_first = q_first - 24 .. j_first + n_times - 1 as [time][r];
+// n_times is a multiple of synthesize_grid_tile_times(D) and at least nq rounded up to 8, plus 24.
+struct SynthesizeGridArgs {
+	const void *in;
+	int in_fmt, out_fmt;           // OFDMRX_FMT_S16 or OFDMRX_FMT_F32
+	int p;                         // D, a power of two 2 .. 512
+	long long in_stride, n_in;     // sample frames
+	const SynthChannel *ch;        // device, [n_channels]
+	const float *taps;             // device, the 24 D + 1 taps of channelize_taps
+	const float2 *tw;              // device, the M / 2 roots e^{+2 pi i j / M}, rounded once from double
+	int n_channels;
+	long long out_first, n_out;
+	void *out;
+	float2 *scratch;
+	long long j_first, q_first;
+	int n_times, nq;
+};
+// the transform kernel over the scratch's n_times, then the filter kernel over the chunk's nq
+void launch_synthesize_grid(hipStream_t s, const SynthesizeGridArgs &a);
+int synthesize_grid_tile_times(int interp);     // input times per workgroup of the transform kernel
+int synthesize_grid_filter_times(int interp);   // output times per workgroup of the filter kernel
+
 // ---- the wideband survey (k_survey.hip): a Welch power spectrum of one wideband capture, n_rows rows of nfft bins.
 // in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); the caller has checked that every position the
 // rows need is there.  Row r (row_first .. row_first + n_rows - 1) averages the segs_per_row segments from r segs_per_row on, in

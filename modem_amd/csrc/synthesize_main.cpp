@@ -4,6 +4,9 @@
 // channels of 16 bits at INTERP x that rate and is as long as the last channel's support: what `decode_stream --wideband INTERP
 // c1,c2,.. OUTROOT OUT.wav` reads.  INTERP may be a ratio P/Q - it is one when it holds a '/' (Q <= 16,
 // 2 <= P / Q <= 32; ofdmrx_util_synthesize_ratio): OUT.wav is then at that rate x P / Q, which must be an integer.
+// `synthesize --grid OUT.wav INTERP SLOT:START:GAIN_DB:IN.wav [...]`: the same through the grid synthesizer (DESIGN.md section 4.20,
+// ofdmrx_util_synthesize_grid): INTERP a power of two 2 .. 512, every IN.wav in a slot of its own, SLOT = -INTERP .. INTERP - 1 with
+// its centre at SLOT x rate / 2, START a multiple of INTERP: what `decode_stream --grid INTERP SLOTS OUTROOT OUT.wav` reads.
 // Exit status 0, or 1 on argument, WAV or library errors.
 #include "survey_cli.h"
 #include <hip/hip_runtime.h>
@@ -17,17 +20,28 @@ static void put16(uint8_t *p, uint16_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(
 
 int main(int argc, char **argv)
 {
+	const char *program = argv[0];
+	const bool grid = argc > 1 && !std::strcmp(argv[1], "--grid");
+	if (grid) {
+		++argv;
+		--argc;
+	}
 	if (argc < 4) {
-		std::fprintf(stderr, "usage: %s OUT.wav INTERP CENTRE_HZ:START:GAIN_DB:IN.wav [...]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s OUT.wav INTERP CENTRE_HZ:START:GAIN_DB:IN.wav [...]\n       %s --grid OUT.wav INTERP SLOT:START:GAIN_DB:IN.wav [...]\n", program, program);
 		return 1;
 	}
 	const char *output_name = argv[1];
 	const Decimation interp(argv[2]);
 	const size_t C = (size_t)(argc - 3);
-	if (!interp.valid() || C > 65535) {
+	if (grid && (interp.ratio || interp.p < 2 || interp.p > 512 || (interp.p & (interp.p - 1)) || C > (size_t)(2 * interp.p))) {
+		std::fprintf(stderr, "A grid capture takes an interpolation that is a power of two 2 .. 512 and 1 .. 2 INTERP channels.\n");
+		return 1;
+	}
+	if (!grid && (!interp.valid() || C > 65535)) {
 		std::fprintf(stderr, "A wideband capture takes an interpolation of 2 .. 32 (a ratio P/Q: Q <= 16) and 1 .. 65535 channels.\n");
 		return 1;
 	}
+	std::vector<int32_t> slot(C);
 	std::vector<double> centre(C);
 	std::vector<long long> start(C);
 	std::vector<float> gain(C);
@@ -48,6 +62,15 @@ int main(int argc, char **argv)
 			p = e + 1;
 			db = std::strtod(p, &e);
 			ok = e != p && *e == ':' && e[1] && std::isfinite(db);
+		}
+		if (grid) {                                                   // a whole slot number on the grid, in a slot of its own; START on the grid of INTERP
+			slot[c] = (int32_t)std::lrint(centre[c]);
+			const bool fits = ok && centre[c] == (double)slot[c] && slot[c] >= -interp.p && slot[c] < interp.p && start[c] % interp.p == 0 &&
+				std::find(slot.begin(), slot.begin() + (long)c, slot[c]) == slot.begin() + (long)c;
+			if (!fits) {
+				std::fprintf(stderr, "A grid channel is SLOT:START:GAIN_DB:IN.wav, SLOT = -INTERP .. INTERP - 1 and given once, START a multiple of INTERP.\n");
+				return 1;
+			}
 		}
 		if (!ok) {
 			std::fprintf(stderr, "A channel is CENTRE_HZ:START:GAIN_DB:IN.wav, START a count of wideband samples.\n");
@@ -118,7 +141,9 @@ int main(int argc, char **argv)
 	e = e == hipSuccess ? hipMalloc(&d_out, (size_t)bytes) : e;
 	e = e == hipSuccess ? hipMemcpy(d_in, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice) : e;
 	if (e == hipSuccess) {
-		r = interp.ratio ? ofdmrx_util_synthesize_ratio(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, interp.q, centre.data(), start.data(),
+		r = grid ? ofdmrx_util_synthesize_grid(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, slot.data(), start.data(), gain.data(), C, 0,
+			(size_t)n_out, d_out, OFDMRX_FMT_S16)
+			: interp.ratio ? ofdmrx_util_synthesize_ratio(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, interp.q, centre.data(), start.data(),
 			gain.data(), C, 0, (size_t)n_out, d_out, OFDMRX_FMT_S16)
 			: ofdmrx_util_synthesize(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, centre.data(), start.data(), gain.data(), C, 0, (size_t)n_out,
 			d_out, OFDMRX_FMT_S16);

@@ -39,6 +39,7 @@ EXPORTS = [
     "ofdmrx_util_channelize_ratio_taps", "ofdmrx_util_channelize_ratio", "ofdmrx_bank_begin_wideband_ratio",
     "ofdmrx_util_synthesize_ratio",
     "ofdmrx_util_channelize_grid_taps", "ofdmrx_util_channelize_grid", "ofdmrx_bank_begin_wideband_grid",
+    "ofdmrx_util_synthesize_grid", "ofdmrx_util_synthesize_grid_chunk",
 ]
 
 
@@ -169,6 +170,16 @@ def synthesize_support(n_in, interp):
         raise OfdmRxError("synthesize_support: n_in, p and q must be positive")
     g = math.gcd(p, q)
     return ((int(n_in) - 1 + 24) * (p // g)) // (q // g) + 1
+
+
+def synthesize_grid_chunk(interp):
+    """the outputs per host chunk of the grid synthesizer at interpolation interp (a power of two 2 .. 512), counted from out_first
+    rounded down to a multiple of interp: DESIGN.md section 4.20.  A seam changes no byte; the number is there for the curious"""
+    L = load_library()
+    n = L.ofdmrx_util_synthesize_grid_chunk(int(interp))
+    if n <= 0:
+        raise OfdmRxError("synthesize_grid_chunk: interp must be a power of two 2 .. 512")
+    return int(n)
 
 
 SURVEY_NFFT = (1280, 2560, 5120)
@@ -326,6 +337,10 @@ def load_library():
                                          C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
     L.ofdmrx_util_synthesize_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
+    L.ofdmrx_util_synthesize_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
+    L.ofdmrx_util_synthesize_grid_chunk.argtypes = [C.c_int]
+    L.ofdmrx_util_synthesize_grid_chunk.restype = C.c_longlong
     L.ofdmrx_util_survey_window.argtypes = [C.c_int, C.c_void_p]
     L.ofdmrx_util_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_longlong, C.c_size_t,
                                      C.c_void_p]
@@ -734,6 +749,18 @@ class Receiver:
             return
         self._check(self._lib.ofdmrx_util_synthesize(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, interp, _ptr(f), _ptr(s),
                                                      _ptr(g), f.size, out_first, n_out, d_out, out_fmt))
+
+    def synthesize_grid(self, d_in, in_fmt, n_in, interp, slots, starts, gains, out_first, n_out, d_out, out_fmt, in_stride=None):
+        """the grid synthesizer on device buffers (ints): as synthesize, for an interp that is a power of two
+        2 .. 512 and rows on the raster rate / 2: row c belongs to slot slots[c] (-interp .. interp - 1, pairwise distinct; None: every
+        slot, ascending), centred at grid_centres(interp, rate, slots)[c]; starts are multiples of interp"""
+        k = _grid_slots(interp, slots)
+        s = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        if not (k.size == s.size == g.size):
+            raise OfdmRxError("synthesize_grid: slots, starts and gains must have one length")
+        self._check(self._lib.ofdmrx_util_synthesize_grid(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, int(interp),
+                                                          _ptr(k), _ptr(s), _ptr(g), k.size, out_first, n_out, d_out, out_fmt))
 
     def survey(self, d_wide, sample_format, nfft=1280, segs_per_row=None, in_first=0, row_first=0, n_rows=None):
         """the wideband survey: d_wide, a contiguous device tensor of interleaved I/Q of sample_format, holds

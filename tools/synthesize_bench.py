@@ -10,6 +10,10 @@ At D = 6 and D = 24, with hipEvents on the handle's stream, median of `--reps` a
   6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs) - C_met the channels a tile meets - and which of the two is nearer.
 --ratio P/Q times the ratio synthesizer (ofdmrx_util_synthesize_ratio, k_resynthesize.hip; section 4.18) in place of those two, and
 beside it k_synthesize at the neighbouring integer D = round(P / Q) on the same input bytes, against the same yardsticks.
+--grid times the grid synthesizer (ofdmrx_util_synthesize_grid, k_synthesize_grid.hip; section 4.20) in place of those: D = 2, 8 and
+32 with all 2 D slots, D = 32 with 4 and 16 slots, D = 64, 128 and 512 with all slots, overlapping rows of `--samples` outputs
+(default 2^22 there), against the same yardsticks - the traffic is the rows, V written and read twice over (16 + 32 bytes per
+output) and the output - and, for D <= 32, beside k_synthesize on the same centres, starts and gains in the same run.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import json
@@ -88,20 +92,88 @@ def child(args):
     print(json.dumps({"tool": "synthesize_bench", "samples": args.samples, "rows": rows}), flush=True)
 
 
+def child_grid(args):
+    import numpy as np
+    import torch
+    import modem_amd
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    rows = []
+    for D, N in ((2, 4), (8, 16), (32, 64), (32, 4), (32, 16), (64, 128), (128, 256), (512, 1024)):
+        n_in = args.samples // D
+        slots = np.arange(-D, D, dtype=np.int32) if N == 2 * D else (np.arange(N, dtype=np.int32) * (2 * D // N) - D)
+        starts = (np.arange(N, dtype=np.int64) % 5) * D
+        n_out = int(starts.max()) + modem_amd.synthesize_support(n_in, D)
+        g = np.full(N, 0.5 / N, np.float32)
+        d_in = torch.randint(-20000, 20000, (N, n_in, 2), dtype=torch.int16, device=dev, generator=gen)
+        d_out = torch.empty((n_out, 2), dtype=torch.int16, device=dev)
+        ms = timed(lambda k: rx.synthesize_grid(d_in.data_ptr(), 0, n_in, D, slots, starts, g, 0, n_out, d_out.data_ptr(), 0))
+        plain = None
+        if D <= 32:
+            f = modem_amd.grid_centres(D, 8000, slots)
+            plain = timed(lambda k: rx.synthesize(d_in.data_ptr(), 0, n_in, D, f, starts, g, 0, n_out, d_out.data_ptr(), 0))
+        spf = 4096
+        frames = max(1, n_out // spf)
+        d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+        d_b = torch.empty_like(d_a)
+        awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+        # arithmetic: the output's 25 x 2 FMAs, and per input time M / 2 log2 M butterflies of 10 operations (6 of them FMA-like issues)
+        logm = (2 * D).bit_length() - 1
+        floor = (n_out * 25 * 2 + (n_out / D) * D * logm * 6) / 64.0 * FMA_NS * 1e-6 / SIMDS
+        nbytes = N * n_in * 4 + n_out * 4
+        traffic = nbytes + n_out * 48
+        rows.append(dict(interp=D, slots=N, n_out=n_out, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1), traffic_gb_per_s=round(traffic / ms / 1e6, 1),
+                         awgn_tile_ms=round(awgn, 4), fma_floor_ms=round(floor, 4), nearer="arithmetic" if floor > awgn else "memory",
+                         over_bound=round(ms / max(floor, awgn), 2), k_synthesize_ms=None if plain is None else round(plain, 4),
+                         ratio=None if plain is None else round(plain / ms, 2)))
+        del d_in, d_out, d_a, d_b
+    chunk = {D: modem_amd.synthesize_grid_chunk(D) for D in (2, 8, 32, 64, 128, 512)}
+    rx.close()
+    print("interp slots    n_out      ms  in+out GB/s  with V GB/s  awgn_tile ms  FMA floor ms  nearer bound  time / bound  k_synthesize ms  k_synthesize / grid")
+    for r in rows:
+        print("%6d %5d %8d %7.4f %12.1f %12.1f %13.4f %13.4f  %-12s %6.2f %16s %10s" % (
+            r["interp"], r["slots"], r["n_out"], r["ms"], r["gb_per_s"], r["traffic_gb_per_s"], r["awgn_tile_ms"], r["fma_floor_ms"], r["nearer"],
+            r["over_bound"], "-" if r["k_synthesize_ms"] is None else "%.4f" % r["k_synthesize_ms"], "-" if r["ratio"] is None else "%.2f" % r["ratio"]))
+    print(json.dumps({"tool": "synthesize_bench", "grid": True, "samples": args.samples, "chunk_outputs": chunk, "rows": rows}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--samples", type=int, default=1 << 20, help="wideband samples an overlapping channel spans")
+    ap.add_argument("--samples", type=int, default=None, help="wideband samples an overlapping channel spans (2^20; --grid: 2^22)")
+    ap.add_argument("--grid", action="store_true", help="the grid synthesizer, beside k_synthesize for D <= 32")
     ap.add_argument("--ratio", default=None, help="P/Q: the ratio synthesizer beside k_synthesize at round(P / Q)")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=240, help="seconds the GPU step may take")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
+    if args.samples is None:
+        args.samples = 1 << 22 if args.grid else 1 << 20
     if args.child:
-        return child(args)
+        return child_grid(args) if args.grid else child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
     if args.ratio is not None:
         cmd += ["--ratio", args.ratio]
+    if args.grid:
+        cmd += ["--grid"]
     try:
         return subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
