@@ -63,7 +63,8 @@ extern "C" {
  *      ofdmrx_util_channelize_ratio_taps, ofdmrx_util_channelize_ratio, ofdmrx_bank_begin_wideband_ratio; the wideband synthesizer
  *      at a rational interpolation - ofdmrx_util_synthesize_ratio; the wideband front end on a channel grid (a polyphase filter bank) -
  *      ofdmrx_util_channelize_grid_taps, ofdmrx_util_channelize_grid, ofdmrx_bank_begin_wideband_grid; the wideband synthesizer on
- *      a channel grid (a polyphase synthesis bank) - ofdmrx_util_synthesize_grid, ofdmrx_util_synthesize_grid_chunk */
+ *      a channel grid (a polyphase synthesis bank) - ofdmrx_util_synthesize_grid, ofdmrx_util_synthesize_grid_chunk; the grid
+ *      survey (per-slot power from the filter bank) - ofdmrx_util_survey_grid, ofdmrx_util_find_slots */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -778,6 +779,45 @@ int ofdmrx_util_survey(ofdmrx_handle *h, const void *d_in, int sample_format, lo
 	int segs_per_row, long long row_first, size_t n_rows, float *d_out);
 int ofdmrx_util_find_bands(const float *psd, int nfft, double rate_wide, double thr_db, double gap_hz, double min_width_hz,
 	double abs_floor, size_t max_bands, ofdmrx_band *bands, size_t *n_bands, double *floor_out);
+
+/* Grid survey (added within revision 1.9, detected by symbol): which slots of the channel grid hold a signal - the slots to open the
+ * grid front end or a grid bank on.  DESIGN.md section 4.21 is the definition, held slot by slot to a float64 model.
+ * ofdmrx_util_survey_grid: the mean output power of every slot of the grid front end's filter bank, one row or a waterfall of rows.
+ * With D = decim (a power of two 2 .. 512), M = 2 D, the taps and y_k[n] of the grid front end above at ABSOLUTE output times n (the
+ * capture zero at negative positions) and S = times_per_row, a multiple of 8 in 8 .. 65536:
+ *   row r   P[r][k + M / 2] = (1 / S) sum_{n = r S .. r S + S - 1} |y_k[n]|^2,  k = -M / 2 .. M / 2 - 1: ASCENDING slot order, index i
+ *           is slot i - M / 2 at (i - M / 2) rate / 2.  No further normalisation: P is the mean power the slot's decoder sees, and
+ *           white noise of power sigma^2 per complex sample reads sigma^2 sum h^2, about 0.7071 sigma^2 / D.
+ * Row r needs the wideband positions max(0, (r S - 24) D) .. ((r + 1) S - 1) D.  Every output is a closed form of absolute indices:
+ * there is no state, and a capture surveyed row by row, each call given only the positions its rows need, gives the same bytes as
+ * one call (the fp32 sums run over groups of 8 consecutive output times, then over a row's groups, both ascending).
+ * DEVICE buffers, asynchronous on the handle's stream.  d_in holds the wideband positions in_first .. in_first + n_in - 1 as
+ * interleaved I/Q of sample_format; row r (row_first .. row_first + n_rows - 1) lands at d_out + (r - row_first) M floats.
+ * OFDMRX_E_ARG, before any device call and with the output untouched: NULL pointers or zero counts; a bad format; decim outside the
+ * set; S no multiple of 8 or outside 8 .. 65536; a negative in_first or row_first; a position the rows need that is not in the
+ * buffer - there is no zero padding other than below position 0; d_in off the sample-frame boundary, d_out off 4 bytes; d_out
+ * overlapping d_in; positions or counts above 2^50; n_rows (S / 8) M above 2^28 (the partial sums of one call: 1 GiB); a handle
+ * with an open feed or bank.
+ * ofdmrx_util_find_slots: host only, float64; the occupied slots of ONE row row[0 .. M - 1] at the handle rate `rate`:
+ *   floor     abs_floor if that is > 0, else the median of the M values (the mean of the two middle values).  Unlike find_bands'
+ *             floor it is NOT the larger of the two: a bank with a few strong frames has more than half its slots above the noise
+ *             (every frame lights its two neighbours through the filter's transition band), and only a given floor brings it down.
+ *   occupied  slot i with row[i] > floor 10^(thr_db / 10) and row[i] > 0
+ *   shadowed  slot i with a cyclic neighbour j = i +- 1 mod M whose row[j] > row[i] 10^(sep_db / 10): an edge of the neighbour's
+ *             signal.  The rule's blind spot: a real signal more than sep_db below a neighbouring slot's is not found.
+ * The occupied, unshadowed slots come in ascending order; *n_slots counts all of them, only the first max_slots are written:
+ * slot = i - M / 2, centre_hz = slot rate / 2, power = row[i], level_db = 10 log10(power / floor).  *floor_out (nullable) gets the
+ * floor.  OFDMRX_E_ARG: NULL row, slots or n_slots; decim outside the set; a rate that is not finite or <= 0; thr_db, sep_db or
+ * abs_floor that is not finite or negative. */
+typedef struct ofdmrx_slot {
+	int slot;
+	double centre_hz, power;
+	float level_db;
+} ofdmrx_slot;
+int ofdmrx_util_survey_grid(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	int times_per_row, long long row_first, size_t n_rows, float *d_out);
+int ofdmrx_util_find_slots(const float *row, int decim, double rate, double thr_db, double sep_db, double abs_floor,
+	size_t max_slots, ofdmrx_slot *slots, size_t *n_slots, double *floor_out);
 
 /* ---- N2: the transmitter on the device (replaces Encoder<value,cmplx,rate>(pcm, inp, count=1, freq_off,
  * call_sign, oper_mode), encode.cc:271,424-436, for batches; rate = the handle's sample_rate).  d_payload:

@@ -1,5 +1,6 @@
 // api_survey.cpp -- the wideband survey behind include/ofdmrx.h: the window, ofdmrx_util_survey, and the
-// band finder ofdmrx_util_find_bands (host only, float64).  Everything the kernels rely on is checked here, before any device call.
+// band finder ofdmrx_util_find_bands (host only, float64); and the grid survey (section 4.21): ofdmrx_util_survey_grid and the slot
+// finder ofdmrx_util_find_slots.  Everything the kernels rely on is checked here, before any device call.
 #include "api_internal.h"
 
 namespace rx {
@@ -159,6 +160,115 @@ extern "C" int ofdmrx_util_find_bands(const float *psd, int nfft, double rate_wi
 	if (first >= 0)
 		close(first, last);
 	*n_bands = count;
+	if (floor_out)
+		*floor_out = floor;
+	return 0;
+}
+
+// ---- the grid survey: the mean power of every slot of the grid front end's bank, and the slot finder
+
+extern "C" int ofdmrx_util_survey_grid(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
+	int times_per_row, long long row_first, size_t n_rows, float *d_out)
+{
+	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
+	if (!h || !d_in || !d_out || !n_in || !n_rows || channelize_grid_decim(decim))
+		return OFDMRX_E_ARG;
+	if (times_per_row < SURVEY_GRID_G || times_per_row > 65536 || times_per_row % SURVEY_GRID_G)
+		return OFDMRX_E_ARG;
+	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || row_first < 0)
+		return OFDMRX_E_ARG;
+	if (in_first > FAR || row_first > FAR || n_in > (size_t)FAR || n_rows > (size_t)FAR)
+		return OFDMRX_E_ARG;
+	const size_t unit = 2 * sample_bytes(sample_format);
+	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float))
+		return OFDMRX_E_ARG;
+	const int M = 2 * decim;
+	{
+		// a position the rows need is not in the buffer: there is no zero padding other than below position 0
+		const __int128 S = times_per_row, D = decim;
+		__int128 lo = ((__int128)row_first * S - 24) * D;
+		lo = lo < 0 ? 0 : lo;
+		const __int128 hi = (((__int128)row_first + (__int128)n_rows) * S - 1) * D;
+		if (lo < (__int128)in_first || hi > (__int128)in_first + (__int128)n_in - 1 || hi >= (__int128)FAR)
+			return OFDMRX_E_ARG;
+	}
+	const int n_groups = times_per_row / SURVEY_GRID_G;
+	if ((__int128)n_rows * n_groups * M > (__int128)survey_max_partial_floats())   // what the handle's partial buffer may hold
+		return OFDMRX_E_ARG;
+	{
+		const char *a = (const char *)d_in, *b = (const char *)d_out;
+		if (a < b + n_rows * (size_t)M * sizeof(float) && b < a + n_in * unit)
+			return OFDMRX_E_ARG;
+	}
+	if (h->busy_live())
+		return OFDMRX_E_ARG;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	// the taps and the roots of the grid table of 4.19: the one on the device if it is a grid table of this D (whatever its slots),
+	// else a new one under the usual key - a plain table of the same D is never read as a grid table, nor the reverse
+	int r = 0;
+	if (!(h->chz_p == decim && h->chz_q == 1 && h->chz_grid))
+		r = channelize_grid_setup(h, decim, std::vector<int32_t>(1, 0));
+	r = r ? r : h->survey_part.ensure(n_rows * (size_t)n_groups * (size_t)M * sizeof(float));
+	if (r)
+		return r;
+	ChannelizeArgs t{};
+	channelize_tables(h, t);
+	SurveyGridArgs a{};
+	a.in = d_in;
+	a.fmt = sample_format;
+	a.logm = 0;
+	while ((1 << a.logm) < M)
+		++a.logm;
+	a.in_first = in_first;
+	a.n_in = (long long)n_in;
+	a.taps = t.taps;
+	a.tw = t.tw;
+	a.t_first = row_first * (long long)times_per_row;
+	a.n_times = (long long)n_rows * (long long)times_per_row;
+	a.n_groups = n_groups;
+	a.n_rows = (long long)n_rows;
+	a.part = h->survey_part.as<float>();
+	a.out = d_out;
+	launch_survey_grid(h->stream, a, (float)(1.0 / (double)times_per_row));
+	HIP_OK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int ofdmrx_util_find_slots(const float *row, int decim, double rate, double thr_db, double sep_db, double abs_floor,
+	size_t max_slots, ofdmrx_slot *slots, size_t *n_slots, double *floor_out)
+{
+	if (!row || !slots || !n_slots || channelize_grid_decim(decim))
+		return OFDMRX_E_ARG;
+	if (!std::isfinite(rate) || rate <= 0.0 || !std::isfinite(thr_db) || thr_db < 0.0 || !std::isfinite(sep_db) || sep_db < 0.0)
+		return OFDMRX_E_ARG;
+	if (!std::isfinite(abs_floor) || abs_floor < 0.0)
+		return OFDMRX_E_ARG;
+	const int M = 2 * decim;
+	double floor = abs_floor;
+	if (!(abs_floor > 0.0)) {
+		std::vector<double> v(row, row + M);
+		std::sort(v.begin(), v.end());
+		floor = 0.5 * (v[(size_t)M / 2 - 1] + v[(size_t)M / 2]);
+	}
+	const double level = floor * std::pow(10.0, thr_db / 10.0), sep = std::pow(10.0, sep_db / 10.0);
+	size_t count = 0;
+	for (int i = 0; i < M; ++i) {
+		const double p = (double)row[i];
+		if (!(p > level && p > 0.0))
+			continue;
+		const double below = (double)row[(i + M - 1) % M], above = (double)row[(i + 1) % M];
+		if (below > p * sep || above > p * sep)                   // shadowed: a neighbour's edge through the filter's transition band
+			continue;
+		if (count < max_slots) {
+			ofdmrx_slot &s = slots[count];
+			s.slot = i - M / 2;
+			s.centre_hz = (double)(i - M / 2) * rate / 2.0;
+			s.power = p;
+			s.level_db = (float)(10.0 * std::log10(p / floor));
+		}
+		++count;
+	}
+	*n_slots = count;
 	if (floor_out)
 		*floor_out = floor;
 	return 0;

@@ -23,6 +23,9 @@
 // ofdmrx_bank_begin_wideband_grid): DECIM a power of two 2 .. 512, the capture's rate DECIM x a supported rate, channel i the slot Ki
 // (-DECIM .. DECIM - 1; `all`: every slot in ascending order) centred at Ki x rate / 2.  Every opened slot's centre is printed on
 // stderr first; the files and lines are those of --wideband.
+// `decode_stream --grid DECIM auto[:FLOOR_DB] OUTROOT WIDE.wav`: the capture is surveyed first (what `survey
+// --grid WIDE.wav DECIM [FLOOR_DB]` prints), the slots found are printed on stderr, and then exactly the form above runs with that
+// list.  The file is read twice, so `auto` does not take standard input; no slot found is an error.
 #include "survey_cli.h"
 #include <algorithm>
 #include <cstdlib>
@@ -329,6 +332,58 @@ static std::string survey_centres(const Decimation &decim, const char *input_nam
 	return list;
 }
 
+// the occupied slots of a grid capture, as the list run_wideband takes with grid = true ("" with a message: none, or an error).
+// how: `auto` or `auto:FLOOR_DB`
+static std::string survey_slots(const char *decim_arg, const char *how, const char *input_name)
+{
+	if (!std::strcmp(input_name, "-") || !std::strcmp(input_name, "/dev/stdin")) {
+		std::fprintf(stderr, "`auto` reads the capture twice: give a file, not standard input.\n");
+		return "";
+	}
+	const int decim = std::atoi(decim_arg);
+	double abs_floor = 0.0;
+	if (!grid_decim_valid(decim) || std::strchr(decim_arg, '/')) {
+		std::fprintf(stderr, "A grid bank takes a decimation that is a power of two 2 .. 512.\n");
+		return "";
+	}
+	if (how[4] && !survey_floor_arg(how + 5, abs_floor)) {
+		std::fprintf(stderr, "`auto:FLOOR_DB` takes a floor in dB re full scale.\n");
+		return "";
+	}
+	Wav w;
+	if (!read_wav(input_name, w) || w.frames == 0) {
+		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
+		return "";
+	}
+	if (w.channels != 2) {
+		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
+		return "";
+	}
+	if (w.rate % decim || !supported(2, w.rate / decim)) {
+		if (w.rate % decim)
+			std::fprintf(stderr, "Unsupported sample rate.\n");
+		return "";
+	}
+	ofdmrx_handle *h = create(w.rate / decim);
+	if (!h)
+		return "";
+	std::vector<ofdmrx_slot> slots;
+	double floor = 0.0;
+	const bool ok = survey_grid_capture(h, w, decim, abs_floor, slots, floor);
+	ofdmrx_destroy(h);
+	if (!ok)
+		return "";
+	if (slots.empty()) {
+		std::fprintf(stderr, "The survey found no occupied slot (floor %.6g).\n", floor);
+		return "";
+	}
+	std::string list;
+	for (const ofdmrx_slot &s : slots)
+		list += (list.empty() ? "" : ",") + std::to_string(s.slot);
+	std::fprintf(stderr, "survey: floor %.6g, slots %s\n", floor, list.c_str());
+	return list;
+}
+
 // one wideband capture block by block through a wideband bank (grid: through a grid bank - centre_list holds slot numbers, or `all`)
 static int run_wideband(const Decimation &decim, const char *centre_list, const std::string &outroot, const char *input_name, bool grid = false)
 {
@@ -450,6 +505,10 @@ int main(int argc, char **argv)
 	}
 	if (argc == 6 && !std::strcmp(argv[1], "--wideband"))
 		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5]);
+	if (argc == 6 && !std::strcmp(argv[1], "--grid") && !std::strncmp(argv[3], "auto", 4) && (!argv[3][4] || argv[3][4] == ':')) {
+		const std::string found = survey_slots(argv[2], argv[3], argv[5]);
+		return found.empty() ? 1 : run_wideband(Decimation(argv[2]), found.c_str(), argv[4], argv[5], true);
+	}
 	if (argc == 6 && !std::strcmp(argv[1], "--grid"))
 		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5], true);
 	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
@@ -458,7 +517,7 @@ int main(int argc, char **argv)
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM K1,K2,...|all OUTROOT INPUT\n",
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
 			argv[0], argv[0], argv[0], argv[0]);
 		return 1;
 	}

@@ -457,4 +457,27 @@ inline long long survey_max_partial_floats() { return 1LL << 28; }   // the part
 // host: the periodic Hann window of nfft points, rounded once to fp32 (returns nfft)
 int survey_window(int nfft, float *w);
 
+// ---- the grid survey (k_survey_grid.hip): the mean power of every slot of the grid front end's bank (4.19), n_rows
+// rows of M = 2^logm = 2 D slots.  in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); a position below
+// 0 reads as zero, and the caller has checked that every other position the rows need is there.  The call covers the absolute output
+// times t_first = row_first S .. t_first + n_times - 1, n_times = n_rows S, S a multiple of SURVEY_GRID_G: k_survey_grid leaves the
+// power of group j (the times t_first + 8 j ..) at part + j M floats in the order of the transform's output (slot k mod M at
+// brev(k mod M)); k_survey_grid_rows sums a row's n_groups = S / 8 groups in ascending order, multiplies by scale and writes row r
+// in ascending slot order at out + (r - row_first) M.  taps, tw: the grid table of 4.19 (ChannelizeArgs).
+constexpr int SURVEY_GRID_G = 8;       // output times per group: part of the definition's summation order
+struct SurveyGridArgs {
+	const void *in;
+	int fmt;                       // OFDMRX_FMT_*
+	int logm;                      // 2 .. 10
+	long long in_first, n_in;
+	const float *taps;             // device, the 24 D + 1 taps
+	const float2 *tw;              // device, the M / 2 roots e^{+2 pi i j / M}
+	long long t_first, n_times;
+	int n_groups;                  // S / 8
+	long long n_rows;              // n_rows n_groups M <= survey_max_partial_floats()
+	float *part;                   // device, n_rows n_groups M floats
+	float *out;
+};
+void launch_survey_grid(hipStream_t s, const SurveyGridArgs &a, float scale);
+
 }  // namespace rx

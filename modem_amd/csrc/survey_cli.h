@@ -1,10 +1,12 @@
 // survey_cli.h -- what `survey` and `decode_stream --wideband DECIM|P/Q auto` share: the decimation argument, and the occupied bands
 // of a whole wideband capture
-// (ofdmrx_util_survey + ofdmrx_util_find_bands) with the finder's default parameters.
+// (ofdmrx_util_survey + ofdmrx_util_find_bands) with the finder's default parameters; and what `survey --grid`
+// and `decode_stream --grid DECIM auto[:FLOOR_DB]` share: the occupied slots of a whole grid capture (section 4.21).
 #pragma once
 #include "wav_read.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -91,5 +93,75 @@ static bool survey_capture(ofdmrx_handle *h, const Wav &w, int nfft, std::vector
 		return false;
 	}
 	bands.resize(n);
+	return true;
+}
+
+// ---- what `survey --grid` and `decode_stream --grid DECIM auto[:FLOOR_DB]` share: the occupied slots of a whole grid capture
+// (ofdmrx_util_survey_grid + ofdmrx_util_find_slots) with the finder's default parameters.
+constexpr double SURVEY_SEP_DB = 8.0;
+constexpr int SURVEY_GRID_TIMES = 4096;                           // output times per row
+
+inline bool grid_decim_valid(int d) { return d >= 2 && d <= 512 && !(d & (d - 1)); }
+
+// FLOOR_DB, an absolute floor as 10 log10 of the per-slot power re full scale -> the finder's abs_floor (false: not a number)
+static bool survey_floor_arg(const char *arg, double &abs_floor)
+{
+	char *e = nullptr;
+	const double db = std::strtod(arg, &e);
+	if (e == arg || *e || !(db > -400.0 && db < 400.0))
+		return false;
+	abs_floor = std::pow(10.0, db / 10.0);
+	return true;
+}
+
+// w: a 2-channel capture read by read_wav.  The file is surveyed in blocks of whole rows of 4096 output times, each call given the
+// positions its rows need; the per-slot maximum over the rows (peak hold) goes to the finder, so a burst does not vanish in a long
+// file's mean.  A trailing partial row is dropped.  abs_floor 0: the median.  Returns false with a message on stderr; slots may come
+// back empty.
+static bool survey_grid_capture(ofdmrx_handle *h, const Wav &w, int decim, double abs_floor, std::vector<ofdmrx_slot> &slots, double &floor)
+{
+	const size_t D = (size_t)decim, M = 2 * D, S = SURVEY_GRID_TIMES;
+	const size_t times = w.frames ? (w.frames - 1) / D + 1 : 0, n_rows = times / S;
+	if (!n_rows) {
+		std::fprintf(stderr, "The capture is shorter than one row of %zu output times (%zu samples).\n", S, (S - 1) * D + 1);
+		return false;
+	}
+	const size_t unit = w.pcm.size() / w.frames, per_block = std::max<size_t>(1, 1024 / D);
+	const size_t max_in = (per_block * S + 24) * D;
+	void *d_in = nullptr, *d_out = nullptr;
+	std::vector<float> rows(per_block * M), peak(M, 0.f);
+	hipError_t e = hipMalloc(&d_in, max_in * unit);
+	e = e == hipSuccess ? hipMalloc(&d_out, rows.size() * sizeof(float)) : e;
+	int r = 0;
+	for (size_t r0 = 0; r0 < n_rows && e == hipSuccess && !r; r0 += per_block) {
+		const size_t nb = std::min(per_block, n_rows - r0);
+		const size_t first = r0 * S > 24 ? (r0 * S - 24) * D : 0, count = ((r0 + nb) * S - 1) * D - first + 1;
+		e = hipMemcpy(d_in, w.pcm.data() + first * unit, count * unit, hipMemcpyHostToDevice);
+		if (e != hipSuccess)
+			break;
+		r = ofdmrx_util_survey_grid(h, d_in, w.fmt, (long long)first, count, decim, (int)S, (long long)r0, nb, (float *)d_out);
+		r = r ? r : ofdmrx_synchronize(h);
+		if (r) {
+			std::fprintf(stderr, "ofdmrx_util_survey_grid: %s\n", ofdmrx_strerror(r));
+			break;
+		}
+		e = hipMemcpy(rows.data(), d_out, nb * M * sizeof(float), hipMemcpyDeviceToHost);
+		for (size_t j = 0; j < nb * M && e == hipSuccess; ++j)
+			peak[j % M] = std::max(peak[j % M], rows[j]);
+	}
+	if (e != hipSuccess)
+		std::fprintf(stderr, "survey: %s\n", hipGetErrorString(e));
+	(void)hipFree(d_in);
+	(void)hipFree(d_out);
+	if (r || e != hipSuccess)
+		return false;
+	size_t n = 0;
+	slots.resize(M);
+	r = ofdmrx_util_find_slots(peak.data(), decim, (double)w.rate / (double)decim, SURVEY_THR_DB, SURVEY_SEP_DB, abs_floor, slots.size(), slots.data(), &n, &floor);
+	if (r) {
+		std::fprintf(stderr, "ofdmrx_util_find_slots: %s\n", ofdmrx_strerror(r));
+		return false;
+	}
+	slots.resize(n);
 	return true;
 }

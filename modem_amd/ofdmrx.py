@@ -40,6 +40,7 @@ EXPORTS = [
     "ofdmrx_util_synthesize_ratio",
     "ofdmrx_util_channelize_grid_taps", "ofdmrx_util_channelize_grid", "ofdmrx_bank_begin_wideband_grid",
     "ofdmrx_util_synthesize_grid", "ofdmrx_util_synthesize_grid_chunk",
+    "ofdmrx_util_survey_grid", "ofdmrx_util_find_slots",
 ]
 
 
@@ -216,6 +217,42 @@ def find_bands(psd_row, rate_wide, thr_db=6.0, gap_hz=200.0, min_width_hz=1000.0
     return (out, floor.value) if with_floor else out
 
 
+class Slot(C.Structure):
+    _fields_ = [("slot", C.c_int), ("centre_hz", C.c_double), ("power", C.c_double), ("level_db", C.c_float)]
+
+
+def survey_grid_span(decim, times_per_row, row_first, n_rows):
+    """the wideband positions the rows row_first .. row_first + n_rows - 1 of the grid survey need -> (first position, count):
+    max(0, (row_first S - 24) D) .. ((row_first + n_rows) S - 1) D with S = times_per_row, D = decim"""
+    D, S, r0, n = int(decim), int(times_per_row), int(row_first), int(n_rows)
+    _grid_slots(D, None)
+    if S < 8 or S > 65536 or S % 8 or r0 < 0 or n < 1:
+        raise OfdmRxError("survey_grid_span: times_per_row a multiple of 8 in 8 .. 65536, row_first >= 0, n_rows >= 1")
+    first = max(0, (r0 * S - 24) * D)
+    return first, ((r0 + n) * S - 1) * D - first + 1
+
+
+def find_slots(row, decim, rate, thr_db=6.0, sep_db=8.0, abs_floor=0.0, with_floor=False):
+    """the occupied slots of ONE grid survey row (fp32 [2 decim], ascending slot order, on the host or a device tensor) at the handle
+    rate `rate` -> a list of dicts (slot, centre_hz, power, level_db) in ascending order; with_floor: -> (list, floor).  The floor is
+    abs_floor where that is > 0, else the row's median; a slot more than sep_db below a cyclic neighbour is taken for that
+    neighbour's edge and dropped - so a real signal that far below a neighbouring one is not found"""
+    if hasattr(row, "detach"):
+        row = row.detach().cpu().numpy()
+    row = np.ascontiguousarray(row, dtype=np.float32).reshape(-1)
+    decim = int(decim)
+    if decim < 2 or decim > 512 or decim & (decim - 1) or row.size != 2 * decim:
+        raise OfdmRxError("find_slots: decim must be a power of two 2 .. 512 and the row 2 decim values")
+    L = load_library()
+    slots = (Slot * row.size)()
+    n, floor = C.c_size_t(0), C.c_double(0.0)
+    r = L.ofdmrx_util_find_slots(_ptr(row), decim, rate, thr_db, sep_db, abs_floor, row.size, slots, C.byref(n), C.byref(floor))
+    if r != 0:
+        raise OfdmRxError("find_slots: %s (%d)" % (L.ofdmrx_strerror(r).decode(), r))
+    out = [{k: getattr(slots[i], k) for k, _ in Slot._fields_} for i in range(n.value)]
+    return (out, floor.value) if with_floor else out
+
+
 class Timing(C.Structure):
     _fields_ = [("ms", C.c_float * 9), ("launches", C.c_int32 * 9)]
 
@@ -346,6 +383,10 @@ def load_library():
                                      C.c_void_p]
     L.ofdmrx_util_find_bands.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ofdmrx_util_survey_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_longlong,
+                                          C.c_size_t, C.c_void_p]
+    L.ofdmrx_util_find_slots.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
     L.ofdmrx_tx_frame_samples.restype = C.c_long
     L.ofdmrx_tx_frame_samples.argtypes = [C.c_int]
     L.ofdmrx_frame_samples.restype = C.c_long
@@ -783,6 +824,31 @@ class Receiver:
         torch.cuda.current_stream(d_wide.device).synchronize()
         self._check(self._lib.ofdmrx_util_survey(self._h, d_wide.data_ptr(), sample_format, in_first, n_in, nfft, segs_per_row, row_first,
                                                  max(n_rows, 0), out.data_ptr()))
+        self.synchronize()
+        return out
+
+    def survey_grid(self, d_wide, sample_format, decim, times_per_row=None, in_first=0, row_first=0, n_rows=None):
+        """the grid survey: d_wide, a contiguous device tensor of interleaved I/Q of sample_format, holds the
+        wideband positions in_first .. of a capture at decim x the handle's rate -> the mean power of every slot of the grid front
+        end's bank, torch.float32 [n_rows, 2 decim] on the device in ascending slot order (index i: slot i - decim at (i - decim) rate
+        / 2), rows row_first .. of times_per_row output times each (a multiple of 8).  times_per_row=None: one row over every whole
+        group of 8 output times the buffer holds (its first 65536 times if it holds more); n_rows=None: every whole row from row_first
+        on that the buffer holds.  Waits for torch's current stream before the launch and for the handle's stream after it"""
+        import torch
+        unit = {FMT_S16: 4, FMT_U8: 2, FMT_F32: 8}[sample_format]
+        decim = int(decim)
+        n_in = d_wide.numel() * d_wide.element_size() // unit
+        times = (in_first + n_in - 1) // max(decim, 1) + 1 if n_in else 0   # the output times 0 .. times - 1 end inside the buffer
+        if times_per_row is None:
+            if in_first or row_first:
+                raise OfdmRxError("survey_grid: times_per_row=None surveys a buffer that starts at position 0, as row 0")
+            times_per_row, n_rows = min(times // 8 * 8, 65536), 1
+        if n_rows is None:
+            n_rows = times // max(times_per_row, 1) - row_first
+        out = torch.empty((max(n_rows, 0), 2 * max(decim, 0)), dtype=torch.float32, device=d_wide.device)
+        torch.cuda.current_stream(d_wide.device).synchronize()
+        self._check(self._lib.ofdmrx_util_survey_grid(self._h, d_wide.data_ptr(), sample_format, in_first, n_in, decim, times_per_row,
+                                                      row_first, max(n_rows, 0), out.data_ptr()))
         self.synchronize()
         return out
 

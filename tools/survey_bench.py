@@ -8,6 +8,11 @@ on the handle's stream, median of `--reps` after `--warmup`:
   beside k_awgn_tile on a buffer of the same bytes (the comparison DESIGN.md 4.13 / 4.14 used) and beside the arithmetic floor of
   the transforms - per segment 2.5 N log2 N fused multiply-adds (5 N log2 N flops, every pair taken as one FMA) + 2 N products of
   the window + 2 N of |X|^2 - at DESIGN.md section 6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs), and which of the two is nearer.
+`--grid [D ...]` times the grid survey instead (ofdmrx_util_survey_grid, k_survey_grid.hip): for every D
+(default 2, 8, 32, 64, 128, 512) the two launches at S = 4096 and at S = 8 output times per row (8: one group per row, so the second
+launch has nothing to add up and the row isolates the first kernel) over every whole row of the capture, beside k_channelize_grid
+storing ALL slots of the same output times of the same capture in the same run - the same arithmetic, 16 x the bytes written - and
+beside k_awgn_tile on the capture's bytes.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import json
@@ -80,17 +85,86 @@ def child(args):
     print(json.dumps({"tool": "survey_bench", "samples": W, "rows": rows}), flush=True)
 
 
+def grid_child(args):
+    import torch
+    import modem_amd
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    W = args.samples
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    d_in = torch.randint(-20000, 20000, (W, 2), dtype=torch.int16, device=dev, generator=gen)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    nbytes = W * 4
+    spf = 4096
+    frames = max(1, nbytes // (2 * spf * 4))
+    d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+    d_b = torch.empty_like(d_a)
+    awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+    rows = []
+    L, h = rx._lib, rx._h
+    for D in args.grid:
+        M = 2 * D
+        times = ((W - 1) // D + 1) // 4096 * 4096                    # whole rows of 4096: the same output times for every entry
+        d_all = torch.empty((M, times, 2), dtype=torch.float32, device=dev)
+
+        def front(k):
+            assert L.ofdmrx_util_channelize_grid(h, d_in.data_ptr(), 0, 0, W, D, None, M, 0, times, d_all.data_ptr(), times) == 0
+
+        chg = timed(front)
+        for S in (4096, 8):
+            n_rows = times // S
+            d_out = torch.empty((n_rows, M), dtype=torch.float32, device=dev)
+
+            def run(k):
+                assert L.ofdmrx_util_survey_grid(h, d_in.data_ptr(), 0, 0, W, D, S, 0, n_rows, d_out.data_ptr()) == 0
+
+            ms = timed(run)
+            rows.append(dict(decim=D, times_per_row=S, rows=n_rows, times=times, ms=round(ms, 4), channelize_grid_ms=round(chg, 4),
+                             ratio=round(ms / chg, 3), gb_per_s=round(nbytes / ms / 1e6, 1), awgn_tile_ms=round(awgn, 4)))
+            del d_out
+        del d_all
+    rx.close()
+    print("    D  times/row    rows     times  survey ms  channelize_grid ms  survey / front end  input GB/s  awgn_tile ms")
+    for r in rows:
+        print("%5d %10d %7d %9d %10.4f %19.4f %19.3f %11.1f %13.4f" % (r["decim"], r["times_per_row"], r["rows"], r["times"], r["ms"],
+                                                                    r["channelize_grid_ms"], r["ratio"], r["gb_per_s"], r["awgn_tile_ms"]))
+    print(json.dumps({"tool": "survey_bench --grid", "samples": W, "rows": rows}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--samples", type=int, default=1 << 20)
+    ap.add_argument("--grid", type=int, nargs="*", default=None, help="time the grid survey at these decimations (none given: 2 8 32 64 128 512)")
+    ap.add_argument("--samples", type=int, default=None, help="default 2^20 (2^22 with --grid)")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=120, help="seconds the GPU step may take")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
+    if args.grid is not None and not args.grid:
+        args.grid = [2, 8, 32, 64, 128, 512]
+    if args.samples is None:
+        args.samples = 1 << (20 if args.grid is None else 22)
     if args.child:
-        return child(args)
+        return child(args) if args.grid is None else grid_child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    if args.grid is not None:
+        cmd += ["--grid"] + [str(d) for d in args.grid]
     try:
         return subprocess.run(cmd, timeout=args.timeout).returncode
     except subprocess.TimeoutExpired:
