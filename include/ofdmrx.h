@@ -64,7 +64,9 @@ extern "C" {
  *      at a rational interpolation - ofdmrx_util_synthesize_ratio; the wideband front end on a channel grid (a polyphase filter bank) -
  *      ofdmrx_util_channelize_grid_taps, ofdmrx_util_channelize_grid, ofdmrx_bank_begin_wideband_grid; the wideband synthesizer on
  *      a channel grid (a polyphase synthesis bank) - ofdmrx_util_synthesize_grid, ofdmrx_util_synthesize_grid_chunk; the grid
- *      survey (per-slot power from the filter bank) - ofdmrx_util_survey_grid, ofdmrx_util_find_slots */
+ *      survey (per-slot power from the filter bank) - ofdmrx_util_survey_grid, ofdmrx_util_find_slots; the wideband front end on a
+ *      channel grid at any ratio P / Q (a mixed-radix filter bank) - ofdmrx_util_channelize_grid_ratio_taps,
+ *      ofdmrx_util_grid_ratio_slots, ofdmrx_util_channelize_grid_ratio, ofdmrx_bank_begin_wideband_grid_ratio */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -659,6 +661,33 @@ int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_
 int ofdmrx_util_channelize_grid_taps(int decim, float *taps);
 int ofdmrx_util_channelize_grid(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
 	const int32_t *slots, size_t n_slots, long long out_first, size_t n_out, float *d_out, size_t out_stride);
+
+/* Wideband front end on a channel grid at any ratio P / Q (added within revision 1.9, detected by symbol): the filter bank above for
+ * the capture rates that are no power of two times the handle's rate.  DESIGN.md section 4.22 is the definition, held component by
+ * component to a float64 model.  p / q is reduced by its gcd here; then 1 <= q <= 16, 2 q <= p <= 512 and p has no prime factor
+ * other than 2, 3 and 5.  Rw = rate p / q, M = 2 p, T = 24 p div q + 1; the taps h_r[j] are ofdmrx_util_channelize_ratio_taps' (the
+ * same formula beyond p / q = 32), the output times u_n = n p, i_n = u_n div q, q_n = u_n mod q those of ofdmrx_util_channelize_ratio.
+ * Slot k lies at k rate / 2; the slots are the k with -p <= k q < p: k_first = -(p div q) .. ceil(p / q) - 1.
+ *   output  y_k[n] = sum_{j = 0 .. T - 1} h_{q_n}[j] x[i_n - j] e^{-2 pi i (k q (i_n - j) mod M) / M}, x zero at negative indices;
+ *           fp32 I/Q, no clip; the phase is integer arithmetic.  Group delay, sc_start + 12, the ceil(W q / p) outputs per channel
+ *           and the positions a call needs are ofdmrx_util_channelize_ratio's
+ *   form    u_n[r] = sum_a h_{q_n}[r + M a] x[i_n - r - M a] over the a with r + M a <= T - 1: one fp32 fused multiply-add chain
+ *           per component, a ascending, positions outside the buffer entering as +0; a transform of length M from radix 5, 3, 4
+ *           and 2 stages whose order is fixed by M alone; one complex multiply by the root of k q i_n mod M
+ * No state: a capture cut into blocks (each handed over with the T - 1 samples before it) gives the same bytes as one call.  At q = 1
+ * with p a power of two every entry below is the grid entry above at decim = p: its kernel, its bytes.
+ * ofdmrx_util_channelize_grid_ratio_taps: host only; writes q rows of T floats, returns T.
+ * ofdmrx_util_grid_ratio_slots: host only; the first slot and the number of slots.
+ * ofdmrx_util_channelize_grid_ratio: row j of the output is slot slots[j] (a host array; NULL with n_slots = n_all: every slot in
+ * ascending k); the other arguments, memory spaces, asynchrony and refusals are those of ofdmrx_util_channelize_ratio.
+ * ofdmrx_bank_begin_wideband_grid_ratio: ofdmrx_bank_begin_wideband_grid at the ratio; push, end and the queries are the bank's.
+ * OFDMRX_E_ARG besides, before any device call and with the output untouched: a ratio outside the above, a slot outside the range,
+ * n_slots outside 1..65535, NULL slots with n_slots != n_all, a NULL pointer. */
+int ofdmrx_util_channelize_grid_ratio_taps(int p, int q, float *taps);
+int ofdmrx_util_grid_ratio_slots(int p, int q, int32_t *k_first, size_t *n_all);
+int ofdmrx_util_channelize_grid_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	const int32_t *slots, size_t n_slots, long long out_first, size_t n_out, float *d_out, size_t out_stride);
+int ofdmrx_bank_begin_wideband_grid_ratio(ofdmrx_handle *h, size_t n_slots, const int32_t *slots, int p, int q, int sample_format);
 
 /* Wideband synthesizer (added within revision 1.9, detected by symbol), the mirror image of the wideband front end: n_channels
  * narrowband transmissions at the handle's rate - what the device transmitter and the channel kernels leave - are each placed at a

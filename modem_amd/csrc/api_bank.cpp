@@ -349,10 +349,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 			a.out_first = o0;
 			a.n_out = o1 - o0;
 			a.dst = dpar + P_PL_DST * P;
-			if (a.grid)
-				launch_channelize_grid(s, a);
-			else
-				launch_channelize(s, a);
+			launch_channelize_any(s, a);
 			b.ops += 2;
 		}
 		const size_t keep = std::min(b.stage_h.size(), (size_t)(T - 1) * wunit);
@@ -773,6 +770,28 @@ extern "C" int ofdmrx_bank_begin_wideband_grid(ofdmrx_handle *h, size_t n_slots,
 	h->bank->wide = true;
 	h->bank->p = decim;
 	h->bank->q = 1;
+	h->bank->wfmt = fmt;
+	return 0;
+}
+
+// the same at a ratio p / q (slots = NULL with n_slots = n_all of ofdmrx_util_grid_ratio_slots: all)
+extern "C" int ofdmrx_bank_begin_wideband_grid_ratio(ofdmrx_handle *h, size_t n_slots, const int32_t *slots, int p, int q, int fmt)
+{
+	std::vector<int32_t> list;
+	if (!h || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || channelize_grid_ratio(p, q) || channelize_grid_ratio_slots(p, q, slots, n_slots, list))
+		return OFDMRX_E_ARG;
+	if (h->bank)
+		return OFDMRX_E_ARG;
+	int r = begin(h, n_slots, OFDMRX_FMT_F32, 2, false);
+	if (r)
+		return r;
+	if ((r = channelize_grid_ratio_setup(h, p, q, list))) {
+		bank_free(h);
+		return r;
+	}
+	h->bank->wide = true;
+	h->bank->p = p;
+	h->bank->q = q;
 	h->bank->wfmt = fmt;
 	return 0;
 }

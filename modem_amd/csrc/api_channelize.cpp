@@ -83,7 +83,8 @@ int rechannelize_ratio(int &p, int &q)
 // k_rechannelize reads them; at q = 1 that is channelize_taps' own order, which k_channelize reads
 // grid: a grid table (q = 1, the M / 2 = p roots of the transform behind the taps); it is part of the key, so a
 // grid call after a plain call at the same D uploads again, and the reverse
-static int channelize_upload(ofdmrx_handle *h, int p, int q, bool grid, const std::vector<unsigned> &inc)
+// grid 2: a ratio-grid table (any q, the M = 2 p roots e^{-2 pi i j / M} behind the taps), a third kind of the key
+static int channelize_upload(ofdmrx_handle *h, int p, int q, int grid, const std::vector<unsigned> &inc)
 {
 	if (p == h->chz_p && q == h->chz_q && grid == h->chz_grid && inc == h->chz_inc_h)
 		return 0;
@@ -99,12 +100,13 @@ static int channelize_upload(ofdmrx_handle *h, int p, int q, bool grid, const st
 			h->chz_taps_h[j * (size_t)q + r] = rows[r * T + j];
 	h->chz_tw_at = 0;
 	if (grid) {                                                   // e^{+2 pi i j / M}, j = 0 .. M / 2 - 1, on an 8-byte boundary
-		const double pi = 3.14159265358979323846;
-		h->chz_tw_at = (T + 1) / 2 * 2;
-		h->chz_taps_h.resize(h->chz_tw_at + 2 * (size_t)p, 0.f);
-		for (int j = 0; j < p; ++j) {
+		const double pi = 3.14159265358979323846;                     // (grid 2: e^{-2 pi i j / M}, j = 0 .. M - 1)
+		const int n_tw = grid == 2 ? 2 * p : p;
+		h->chz_tw_at = ((size_t)q * T + 1) / 2 * 2;
+		h->chz_taps_h.resize(h->chz_tw_at + 2 * (size_t)n_tw, 0.f);
+		for (int j = 0; j < n_tw; ++j) {
 			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j] = (float)std::cos(pi * (double)j / (double)p);
-			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j + 1] = (float)std::sin(pi * (double)j / (double)p);
+			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j + 1] = (float)(grid == 2 ? -std::sin(pi * (double)j / (double)p) : std::sin(pi * (double)j / (double)p));
 		}
 	}
 	h->chz_inc_h = inc;
@@ -129,7 +131,7 @@ int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, si
 			return OFDMRX_E_ARG;
 		inc[c] = channelize_inc(centre_hz[c], rw);
 	}
-	return channelize_upload(h, p, q, false, inc);
+	return channelize_upload(h, p, q, 0, inc);
 }
 
 int channelize_grid_decim(int decim)
@@ -158,7 +160,76 @@ int channelize_grid_setup(ofdmrx_handle *h, int decim, const std::vector<int32_t
 	std::vector<unsigned> inc(slots.size());
 	for (size_t j = 0; j < slots.size(); ++j)
 		inc[j] = (unsigned)slots[j] * step;
-	return channelize_upload(h, decim, 1, true, inc);
+	return channelize_upload(h, decim, 1, 1, inc);
+}
+
+// the grid front end at a ratio: p / q reduced here; 1 <= q <= 16, 2 q <= p <= 512, p = 2^a 3^b 5^c
+int channelize_grid_ratio(int &p, int &q)
+{
+	if (p <= 0 || q <= 0)
+		return OFDMRX_E_ARG;
+	int a = p, b = q;
+	while (b) {
+		const int t = a % b;
+		a = b;
+		b = t;
+	}
+	p /= a;
+	q /= a;
+	if (q > 16 || p < 2 * q || p > 512)
+		return OFDMRX_E_ARG;
+	int m = p;
+	for (int f : { 2, 3, 5 })
+		while (m % f == 0)
+			m /= f;
+	return m == 1 ? 0 : OFDMRX_E_ARG;
+}
+
+// its slots: the k with -p <= k q < p, k_first = -(p div q) .. ceil(p / q) - 1
+void channelize_grid_ratio_range(int p, int q, int32_t &k_first, size_t &n_all)
+{
+	k_first = -(p / q);
+	n_all = (size_t)((p + q - 1) / q + p / q);
+}
+
+int channelize_grid_ratio_slots(int p, int q, const int32_t *slots, size_t n_slots, std::vector<int32_t> &out)
+{
+	int32_t k_first;
+	size_t n_all;
+	channelize_grid_ratio_range(p, q, k_first, n_all);
+	if (n_slots < 1 || n_slots > 65535 || (!slots && n_slots != n_all))
+		return OFDMRX_E_ARG;
+	out.resize(n_slots);
+	for (size_t j = 0; j < n_slots; ++j) {
+		out[j] = slots ? slots[j] : k_first + (int32_t)j;
+		if (out[j] < k_first || out[j] > k_first + (int32_t)n_all - 1)
+			return OFDMRX_E_ARG;
+	}
+	return 0;
+}
+
+// q = 1 with p a power of two is 4.19 itself: its table, its kernel, its bytes
+int channelize_grid_ratio_setup(ofdmrx_handle *h, int p, int q, const std::vector<int32_t> &slots)
+{
+	if (q == 1 && !channelize_grid_decim(p))
+		return channelize_grid_setup(h, p, slots);
+	const GridRatioPlan pl = channelize_grid_ratio_plan(p, q);
+	std::vector<unsigned> inc(slots.size());
+	for (size_t j = 0; j < slots.size(); ++j) {
+		const int kq = ((slots[j] * q) % pl.m + pl.m) % pl.m;
+		inc[j] = (unsigned)channelize_grid_ratio_row(pl, (pl.m - kq) % pl.m) | (unsigned)kq << 16;
+	}
+	return channelize_upload(h, p, q, 2, inc);
+}
+
+void launch_channelize_any(hipStream_t s, const ChannelizeArgs &a)
+{
+	if (a.grid == 2)
+		launch_channelize_grid_ratio(s, a);
+	else if (a.grid)
+		launch_channelize_grid(s, a);
+	else
+		launch_channelize(s, a);
 }
 
 void channelize_tables(const ofdmrx_handle *h, ChannelizeArgs &a)
@@ -183,8 +254,8 @@ extern "C" int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps)
 	return rechannelize_taps(p, q, taps);
 }
 
-// one call at the reduced ratio p / q (q = 1: the integer decimation p).  grid: the grid front end at decimation p, whose channels are
-// the slots (nullable: all of them) and not centres
+// one call at the reduced ratio p / q (q = 1: the integer decimation p).  grid: the grid front end at decimation p / q, whose channels
+// are the slots (nullable: all of them) and not centres - section 4.19's where q = 1 and p is a power of two, else section 4.22's
 static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride,
 	bool grid = false, const int32_t *slots = nullptr)
@@ -194,7 +265,7 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 		return OFDMRX_E_ARG;
 	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || out_first < 0 || out_stride < n_out)
 		return OFDMRX_E_ARG;
-	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)(grid ? channelize_grid_max_outputs() : channelize_max_outputs(q)) || out_stride > (size_t)FAR / 65536)
+	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)(!grid ? channelize_max_outputs(q) : (q == 1 && !channelize_grid_decim(p)) ? channelize_grid_max_outputs() : channelize_grid_ratio_max_outputs()) || out_stride > (size_t)FAR / 65536)
 		return OFDMRX_E_ARG;
 	const size_t unit = 2 * sample_bytes(sample_format);
 	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))
@@ -209,14 +280,14 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 			return OFDMRX_E_ARG;
 	}
 	std::vector<int32_t> slot_list;
-	if (grid && channelize_grid_slots(p, slots, n_channels, slot_list))
+	if (grid && channelize_grid_ratio_slots(p, q, slots, n_channels, slot_list))
 		return OFDMRX_E_ARG;
 	for (size_t c = 0; c < n_channels && !grid; ++c)
 		if (!std::isfinite(centre_hz[c]))
 			return OFDMRX_E_ARG;
 	if (h->busy_live())                                           // (an open wideband bank owns the taps and increments on the device)
 		return OFDMRX_E_ARG;
-	int r = grid ? channelize_grid_setup(h, p, slot_list) : channelize_setup(h, p, q, centre_hz, n_channels);
+	int r = grid ? channelize_grid_ratio_setup(h, p, q, slot_list) : channelize_setup(h, p, q, centre_hz, n_channels);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -234,10 +305,7 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 	a.out = d_out;
 	a.out_stride = (long long)out_stride;
 	a.dst = nullptr;
-	if (a.grid)
-		launch_channelize_grid(h->stream, a);
-	else
-		launch_channelize(h->stream, a);
+	launch_channelize_any(h->stream, a);
 	HIP_OK(hipGetLastError());
 	return 0;
 }
@@ -271,4 +339,28 @@ extern "C" int ofdmrx_util_channelize_grid(ofdmrx_handle *h, const void *d_in, i
 	if (channelize_grid_decim(decim))
 		return OFDMRX_E_ARG;
 	return channelize_call(h, d_in, sample_format, in_first, n_in, decim, 1, nullptr, n_slots, out_first, n_out, d_out, out_stride, true, slots);
+}
+
+// the grid front end at a ratio
+extern "C" int ofdmrx_util_channelize_grid_ratio_taps(int p, int q, float *taps)
+{
+	if (channelize_grid_ratio(p, q) || !taps)
+		return OFDMRX_E_ARG;
+	return rechannelize_taps(p, q, taps);
+}
+
+extern "C" int ofdmrx_util_grid_ratio_slots(int p, int q, int32_t *k_first, size_t *n_all)
+{
+	if (channelize_grid_ratio(p, q) || !k_first || !n_all)
+		return OFDMRX_E_ARG;
+	channelize_grid_ratio_range(p, q, *k_first, *n_all);
+	return 0;
+}
+
+extern "C" int ofdmrx_util_channelize_grid_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	const int32_t *slots, size_t n_slots, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+{
+	if (channelize_grid_ratio(p, q))
+		return OFDMRX_E_ARG;
+	return channelize_call(h, d_in, sample_format, in_first, n_in, p, q, nullptr, n_slots, out_first, n_out, d_out, out_stride, true, slots);
 }

@@ -230,7 +230,7 @@ struct ofdmrx_handle {
 	// from - the reduced ratio chz_p / chz_q (an integer decimation D is D / 1; 0 / 0: none) and the host copies the uploads read
 	DevBuf chz_taps, chz_inc;
 	int chz_p = 0, chz_q = 0;
-	bool chz_grid = false;               // the table is a grid table: the roots of the transform stand behind the taps (at chz_tw_at floats)
+	int chz_grid = 0;                    // the table is a grid table: the roots of the transform stand behind the taps (at chz_tw_at floats); 2: a ratio-grid table (4.22)
 	size_t chz_tw_at = 0;
 	std::vector<float> chz_taps_h;
 	std::vector<unsigned> chz_inc_h;
@@ -307,6 +307,13 @@ int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, si
 int channelize_grid_decim(int decim);
 int channelize_grid_slots(int decim, const int32_t *slots, size_t n_slots, std::vector<int32_t> &out);
 int channelize_grid_setup(ofdmrx_handle *h, int decim, const std::vector<int32_t> &slots);
+// the grid front end at a ratio: the reduced p / q (else OFDMRX_E_ARG), its slots, its table - 4.19's where q = 1 and
+// p is a power of two; launch_channelize_any: the kernel the table set up last belongs to
+int channelize_grid_ratio(int &p, int &q);
+void channelize_grid_ratio_range(int p, int q, int32_t &k_first, size_t &n_all);
+int channelize_grid_ratio_slots(int p, int q, const int32_t *slots, size_t n_slots, std::vector<int32_t> &out);
+int channelize_grid_ratio_setup(ofdmrx_handle *h, int p, int q, const std::vector<int32_t> &slots);
+void launch_channelize_any(hipStream_t s, const ChannelizeArgs &a);
 // the ChannelizeArgs fields the device tables give: taps, inc, grid, tw (the table set up last)
 void channelize_tables(const ofdmrx_handle *h, ChannelizeArgs &a);
 void bank_free(ofdmrx_handle *h);                                                           // api_bank.cpp: the open bank (or feed) and its windows go

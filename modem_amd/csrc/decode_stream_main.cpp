@@ -23,6 +23,9 @@
 // ofdmrx_bank_begin_wideband_grid): DECIM a power of two 2 .. 512, the capture's rate DECIM x a supported rate, channel i the slot Ki
 // (-DECIM .. DECIM - 1; `all`: every slot in ascending order) centred at Ki x rate / 2.  Every opened slot's centre is printed on
 // stderr first; the files and lines are those of --wideband.
+// `decode_stream --grid P/Q K1,K2,...|all OUTROOT WIDE.wav`: the grid front end at a ratio (DESIGN.md section 4.22,
+// ofdmrx_bank_begin_wideband_grid_ratio): the spelling with '/' - 6/1 is a 48 kHz capture at an 8 kHz handle; the slots are the K with
+// -P <= K Q < P.  A bare integer keeps the power-of-two rule.  `--grid P/Q auto` is refused: the grid survey at a ratio is not built.
 // `decode_stream --grid DECIM auto[:FLOOR_DB] OUTROOT WIDE.wav`: the capture is surveyed first (what `survey
 // --grid WIDE.wav DECIM [FLOOR_DB]` prints), the slots found are printed on stderr, and then exactly the form above runs with that
 // list.  The file is read twice, so `auto` does not take standard input; no slot found is an error.
@@ -342,7 +345,11 @@ static std::string survey_slots(const char *decim_arg, const char *how, const ch
 	}
 	const int decim = std::atoi(decim_arg);
 	double abs_floor = 0.0;
-	if (!grid_decim_valid(decim) || std::strchr(decim_arg, '/')) {
+	if (std::strchr(decim_arg, '/')) {
+		std::fprintf(stderr, "The grid survey at a ratio P/Q is not built: `--grid P/Q auto` is refused; name the slots or give `all`.\n");
+		return "";
+	}
+	if (!grid_decim_valid(decim)) {
 		std::fprintf(stderr, "A grid bank takes a decimation that is a power of two 2 .. 512.\n");
 		return "";
 	}
@@ -390,19 +397,27 @@ static int run_wideband(const Decimation &decim, const char *centre_list, const 
 	std::vector<double> centres;
 	std::vector<int32_t> slots;
 	if (grid) {
-		if (decim.ratio || decim.p < 2 || decim.p > 512 || (decim.p & (decim.p - 1))) {
+		// a bare integer keeps the power-of-two rule; the spelling P/Q is the grid front end at a ratio
+		int32_t k_first = -decim.p;
+		size_t n_all = 2 * (size_t)(decim.p > 0 ? decim.p : 0);
+		if (decim.ratio && ofdmrx_util_grid_ratio_slots(decim.p, decim.q, &k_first, &n_all)) {
+			std::fprintf(stderr, "A grid bank at a ratio takes P/Q with, in lowest terms, Q 1 .. 16 and P 2 Q .. 512 with no prime factor other than 2, 3 and 5.\n");
+			return 1;
+		}
+		if (!decim.ratio && (decim.p < 2 || decim.p > 512 || (decim.p & (decim.p - 1)))) {
 			std::fprintf(stderr, "A grid bank takes a decimation that is a power of two 2 .. 512.\n");
 			return 1;
 		}
+		const long k_last = (long)k_first + (long)n_all - 1;
 		if (!std::strcmp(centre_list, "all")) {
-			for (int k = -decim.p; k < decim.p; ++k)
-				slots.push_back(k);
+			for (long k = k_first; k <= k_last; ++k)
+				slots.push_back((int32_t)k);
 		} else {
 			for (const char *p = centre_list; *p;) {
 				char *e = nullptr;
 				const long k = std::strtol(p, &e, 10);
-				if (e == p || (*e && *e != ',') || k < -decim.p || k > decim.p - 1) {
-					std::fprintf(stderr, "Slots are `all` or a comma-separated list of numbers %d .. %d.\n", -decim.p, decim.p - 1);
+				if (e == p || (*e && *e != ',') || k < k_first || k > k_last) {
+					std::fprintf(stderr, "Slots are `all` or a comma-separated list of numbers %d .. %ld.\n", (int)k_first, k_last);
 					return 1;
 				}
 				slots.push_back((int32_t)k);
@@ -459,7 +474,8 @@ static int run_wideband(const Decimation &decim, const char *centre_list, const 
 		centres[i] = (double)slots[i] * 0.5 * (double)decim.rate_of(w.rate);
 		std::fprintf(stderr, "%zu: slot %d, centre %.17g Hz\n", i, (int)slots[i], centres[i]);
 	}
-	int r = grid ? ofdmrx_bank_begin_wideband_grid(h, S, slots.data(), decim.p, w.fmt)
+	int r = grid && decim.ratio ? ofdmrx_bank_begin_wideband_grid_ratio(h, S, slots.data(), decim.p, decim.q, w.fmt)
+		: grid ? ofdmrx_bank_begin_wideband_grid(h, S, slots.data(), decim.p, w.fmt)
 		: decim.ratio ? ofdmrx_bank_begin_wideband_ratio(h, S, centres.data(), decim.p, decim.q, w.fmt)
 		: ofdmrx_bank_begin_wideband(h, S, centres.data(), decim.p, w.fmt);
 	std::vector<uint8_t> out(cap * OFDMRX_PAYLOAD_BYTES), pcm;
@@ -517,7 +533,7 @@ int main(int argc, char **argv)
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM|P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
 			argv[0], argv[0], argv[0], argv[0]);
 		return 1;
 	}

@@ -367,6 +367,21 @@ void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a);   // k_rec
 long long channelize_max_outputs(int q);
 void launch_channelize_grid(hipStream_t s, const ChannelizeArgs &a);    // k_channelize_grid.hip: a.grid != 0 (the callers choose)
 long long channelize_grid_max_outputs();
+// the grid front end at a ratio (k_channelize_grid_ratio.hip): a.grid == 2, p / q in lowest terms with p = 2^a 3^b 5^c
+// (not q = 1 with p a power of two: that is 4.19's kernel), M = 2 p; taps as launch_channelize_ratio reads them; tw: device, the M
+// roots e^{-2 pi i j / M}, rounded once from double; channel c is slot k_c with
+// inc[c] = channelize_grid_ratio_row(plan, (-k_c q) mod M) | (k_c q mod M) << 16
+struct GridRatioPlan {
+	int m, n_taps;                 // M = 2 p, T = 24 p div q + 1
+	int nt;                        // output times per tile
+	int ch, groups;                // times per run of the branch sums (1, 2, 4, 8 or 16), runs per residue of 2 q
+	unsigned radices;              // the transform's stages, four bits each, the first lowest: every 5, every 3, every 4, a last 2
+	size_t lds;                    // dynamic LDS in bytes
+};
+GridRatioPlan channelize_grid_ratio_plan(int p, int q);
+int channelize_grid_ratio_row(const GridRatioPlan &pl, int bin);   // where a bin stands behind the transform
+void launch_channelize_grid_ratio(hipStream_t s, const ChannelizeArgs &a);
+long long channelize_grid_ratio_max_outputs();
 // what a workgroup's tile of k_rechannelize looks like: T, the outputs per residue M (a tile is q M outputs), the rows of history,
 // the rows of a plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
 struct RechannelizeShape { int n_taps, m, hist, rows, passes; size_t lds; };

@@ -16,6 +16,10 @@ static int run_grid(int argc, char **argv)
 {
 	const int decim = std::atoi(argv[3]);
 	double abs_floor = 0.0;
+	if (std::strchr(argv[3], '/')) {
+		std::fprintf(stderr, "The grid survey at a ratio P/Q is not built (DESIGN.md section 4.22): a grid survey takes a power of two 2 .. 512.\n");
+		return 1;
+	}
 	if (!grid_decim_valid(decim) || std::strchr(argv[3], '/') || (argc == 5 && !survey_floor_arg(argv[4], abs_floor))) {
 		std::fprintf(stderr, "A grid survey takes a decimation that is a power of two 2 .. 512 and, optionally, a floor in dB re full scale.\n");
 		return 1;

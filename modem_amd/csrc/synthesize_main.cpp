@@ -33,6 +33,10 @@ int main(int argc, char **argv)
 	const char *output_name = argv[1];
 	const Decimation interp(argv[2]);
 	const size_t C = (size_t)(argc - 3);
+	if (grid && interp.ratio) {
+		std::fprintf(stderr, "The grid synthesizer at a ratio P/Q is not built (DESIGN.md section 4.22): a grid capture takes a power of two 2 .. 512.\n");
+		return 1;
+	}
 	if (grid && (interp.ratio || interp.p < 2 || interp.p > 512 || (interp.p & (interp.p - 1)) || C > (size_t)(2 * interp.p))) {
 		std::fprintf(stderr, "A grid capture takes an interpolation that is a power of two 2 .. 512 and 1 .. 2 INTERP channels.\n");
 		return 1;

@@ -41,6 +41,8 @@ EXPORTS = [
     "ofdmrx_util_channelize_grid_taps", "ofdmrx_util_channelize_grid", "ofdmrx_bank_begin_wideband_grid",
     "ofdmrx_util_synthesize_grid", "ofdmrx_util_synthesize_grid_chunk",
     "ofdmrx_util_survey_grid", "ofdmrx_util_find_slots",
+    "ofdmrx_util_channelize_grid_ratio_taps", "ofdmrx_util_grid_ratio_slots", "ofdmrx_util_channelize_grid_ratio",
+    "ofdmrx_bank_begin_wideband_grid_ratio",
 ]
 
 
@@ -110,8 +112,15 @@ def channelize_taps(decim):
 
 def channelize_grid_taps(decim):
     """the 24 decim + 1 fp32 taps of the grid front end's prototype low pass for decimation decim (a power of two 2 .. 512): DESIGN.md
-    section 4.19; for decim <= 32 they are channelize_taps(decim)"""
-    decim = int(decim)
+    section 4.19; for decim <= 32 they are channelize_taps(decim).  A ratio - a pair (p, q) or a fractions.Fraction - gives the taps
+    [q', T] of the grid front end at that ratio"""
+    decim, q = _ratio(decim)
+    if q is not None:
+        p, q, _, _ = _grid_ratio(decim, q)
+        taps = np.zeros((q, 24 * p // q + 1), np.float32)
+        if load_library().ofdmrx_util_channelize_grid_ratio_taps(p, q, _ptr(taps)) != taps.shape[1]:
+            raise OfdmRxError("channelize_grid_taps: the library refused the ratio")
+        return taps
     taps = np.zeros(24 * min(max(decim, 0), 512) + 1, np.float32)
     n = load_library().ofdmrx_util_channelize_grid_taps(decim, _ptr(taps))
     if n != taps.size:
@@ -119,9 +128,30 @@ def channelize_grid_taps(decim):
     return taps
 
 
+def _grid_ratio(p, q):
+    """-> (p', q', k_first, n_all) of the grid front end at the ratio p / q, reduced to lowest terms"""
+    p, q = int(p), int(q)
+    k0, n = C.c_int32(0), C.c_size_t(0)
+    if p <= 0 or q <= 0 or load_library().ofdmrx_util_grid_ratio_slots(p, q, C.byref(k0), C.byref(n)):
+        raise OfdmRxError("grid: in lowest terms q must be 1 .. 16, p 2 q .. 512 with no prime factor other than 2, 3 and 5")
+    g = math.gcd(p, q)
+    return p // g, q // g, k0.value, n.value
+
+
+def _grid_ratio_slots(p, q, slots):
+    """-> (p', q', the slots as int32 (None: all of them, ascending))"""
+    p, q, k0, n = _grid_ratio(p, q)
+    k = np.arange(k0, k0 + n, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+    if k.size < 1 or k.size > 65535 or k.min() < k0 or k.max() > k0 + n - 1:
+        raise OfdmRxError("grid: 1 .. 65535 slots, each %d .. %d" % (k0, k0 + n - 1))
+    return p, q, k
+
+
 def _grid_slots(decim, slots):
     """-> the slots of a grid of decimation decim as int32 (None: all 2 decim of them, ascending)"""
-    decim = int(decim)
+    decim, q = _ratio(decim)
+    if q is not None:
+        return _grid_ratio_slots(decim, q, slots)[2]
     if decim < 2 or decim > 512 or decim & (decim - 1):
         raise OfdmRxError("grid: decim must be a power of two 2 .. 512")
     k = np.arange(-decim, decim, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
@@ -132,7 +162,8 @@ def _grid_slots(decim, slots):
 
 def grid_centres(decim, rate, slots=None):
     """the centre frequencies in Hz of the slots of the grid front end: slot k of decimation decim at the
-    handle rate `rate` lies at k rate / 2, k = -decim .. decim - 1 (slots None: all of them, ascending)"""
+    handle rate `rate` lies at k rate / 2, k = -decim .. decim - 1 (slots None: all of them, ascending).  decim: an int, or a ratio - a
+    pair (p, q) or a fractions.Fraction - whose slots are the k with -p <= k q < p (section 4.22)"""
     return _grid_slots(decim, slots).astype(np.float64) * (float(rate) / 2.0)
 
 
@@ -368,6 +399,11 @@ def load_library():
     L.ofdmrx_util_channelize_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                               C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_bank_begin_wideband_grid.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
+    L.ofdmrx_util_channelize_grid_ratio_taps.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.ofdmrx_util_grid_ratio_slots.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.ofdmrx_util_channelize_grid_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                                    C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.ofdmrx_bank_begin_wideband_grid_ratio.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.ofdmrx_util_channelize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_util_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -531,7 +567,8 @@ class Receiver:
 
     def wideband_grid_bank(self, slots, decim, dtype=np.int16, esn0_rows=False):
         """open a bank whose channels are slots of the raster rate / 2 of one wideband I/Q capture at decim x the handle's rate (decim a
-        power of two 2 .. 512; slots None: all 2 decim): push the capture block by block"""
+        power of two 2 .. 512; slots None: all 2 decim): push the capture block by block.  decim may be a ratio
+        - a pair (p, q) or a fractions.Fraction (section 4.22)"""
         return WidebandGridBank(self, slots, decim, dtype, esn0_rows)
 
     def decode_stream_device(self, d_samples, fmt, channels, n_samples, max_frames, d_payload, d_results):
@@ -768,7 +805,13 @@ class Receiver:
     def channelize_grid(self, d_in, fmt, in_first, n_in, decim, slots, out_first, n_out, d_out, out_stride=None):
         """the grid front end on device buffers (ints): as channelize, for a decim that is a power of two 2 ..
         512 and channels on the raster rate / 2: row j of the output is slot slots[j] (-decim .. decim - 1; None: every slot, ascending),
-        centred at grid_centres(decim, rate, slots)[j]"""
+        centred at grid_centres(decim, rate, slots)[j].  decim may be a ratio - a pair (p, q) or a fractions.Fraction (section 4.22)"""
+        decim, q = _ratio(decim)
+        if q is not None:
+            p, q, k = _grid_ratio_slots(decim, q, slots)
+            self._check(self._lib.ofdmrx_util_channelize_grid_ratio(self._h, d_in, fmt, in_first, n_in, p, q, _ptr(k), k.size, out_first, n_out,
+                                                                    d_out, n_out if out_stride is None else out_stride))
+            return
         k = _grid_slots(decim, slots)
         self._check(self._lib.ofdmrx_util_channelize_grid(self._h, d_in, fmt, in_first, n_in, int(decim), _ptr(k), k.size, out_first, n_out,
                                                           d_out, n_out if out_stride is None else out_stride))
@@ -1082,6 +1125,16 @@ class WidebandGridBank(WidebandBank):
 
     def __init__(self, rx, slots, decim, dtype=np.int16, esn0_rows=False):
         self._rx, self._lib, self._h = rx, rx._lib, rx._h
+        p, q = _ratio(decim)
+        if q is not None:
+            p, q, k = _grid_ratio_slots(p, q, slots)
+            self.slots, self.decim, self.centres_hz = k, (p, q), k.astype(np.float64) * (float(rx.sample_rate) / 2.0)
+            self.n_channels, self.channels, self.dtype, self._rows = k.size, 2, np.dtype(dtype), bool(esn0_rows)
+            rx._check(self._lib.ofdmrx_bank_begin_wideband_grid_ratio(self._h, k.size, _ptr(k), p, q, rx._fmt(self.dtype)))
+            self.open = True
+            self.n_left = 0
+            self._ops = 0
+            return
         k = _grid_slots(decim, slots)
         self.slots, self.decim, self.centres_hz = k, int(decim), grid_centres(decim, rx.sample_rate, k)
         self.n_channels, self.channels, self.dtype, self._rows = k.size, 2, np.dtype(dtype), bool(esn0_rows)

@@ -16,6 +16,10 @@ k_channelize_grid.hip) beside three yardsticks: k_awgn_t
 output time 13 M real-by-complex multiply-adds (2 FMAs each) and (M / 2) log2 M butterflies of 8 operations - at the same 0.86 ns per
 wave64 FMA and SIMD; and, for D <= 32, k_channelize on the same centres in the same run.  Then one wideband second through the grid
 bank with those slots.
+--grid P/Q [SLOTS] (repeatable; the spelling with `/`) times the grid front end at a ratio (ofdmrx_util_channelize_grid_ratio,
+k_channelize_grid_ratio.hip), with one slot (slot 0, or SLOTS) and with all slots, beside: the direct form
+(k_rechannelize / k_channelize) on the same centres in the same run where P / Q <= 32; k_channelize_grid at the next power of two
+>= P on the same samples, for Q = 1; k_awgn_tile on the same bytes.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import ctypes as C
@@ -310,9 +314,78 @@ def child_grid(args):
     print(json.dumps({"tool": "channelize_bench", "samples": W, "grid_rows": rows, "grid_banks": banks}), flush=True)
 
 
+def child_grid_ratio(args):
+    import numpy as np
+    import torch
+    import modem_amd
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    W = args.samples
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    d_in = torch.randint(-20000, 20000, (W, 2), dtype=torch.int16, device=dev, generator=gen)
+
+    def timed(f):
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            f(k)
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms)
+
+    rows = []
+    for g in args.grid:
+        P, Q = (int(t) for t in g[0].split("/"))
+        one = [0] if len(g) < 2 else [int(t) for t in g[1].split(",")]
+        n_out = -(-W * Q // P)
+        n_all = len(modem_amd.grid_centres((P, Q), 8000))
+        pow2 = None
+        if Q == 1:                                                   # 4.19's kernel at the next power of two, all its slots, on the same samples
+            D2 = 1 << (P - 1).bit_length()
+            n2 = -(-W // D2)
+            d2 = torch.empty((2 * D2, n2, 2), dtype=torch.float32, device=dev)
+            pow2 = (D2, timed(lambda k: rx.channelize_grid(d_in.data_ptr(), 0, 0, W, D2, None, 0, n2, d2.data_ptr())))
+            del d2
+        for slots in (one, None):
+            N = n_all if slots is None else len(slots)
+            d_out = torch.empty((N, n_out, 2), dtype=torch.float32, device=dev)
+            ms = timed(lambda k: rx.channelize_grid(d_in.data_ptr(), 0, 0, W, (P, Q), slots, 0, n_out, d_out.data_ptr()))
+            plain = None
+            if P <= 32 * Q:                                          # the direct form on the same centres, in the same run
+                f = modem_amd.grid_centres((P, Q), 8000, slots)
+                plain = timed(lambda k: rx.channelize(d_in.data_ptr(), 0, 0, W, P if Q == 1 else (P, Q), f, 0, n_out, d_out.data_ptr()))
+            nbytes = W * 4 + N * n_out * 8
+            spf = 4096
+            frames = max(1, nbytes // (2 * spf * 4))
+            d_a = torch.zeros((frames, spf, 2), dtype=torch.int16, device=dev)
+            d_b = torch.empty_like(d_a)
+            awgn = timed(lambda k: rx.awgn_tile(d_a.data_ptr(), frames, d_b.data_ptr(), frames, spf, -30.0, 7, k * frames))
+            rows.append(dict(ratio="%d/%d" % (P, Q), m=2 * P, slots=N, n_out=n_out, ms=round(ms, 4), gb_per_s=round(nbytes / ms / 1e6, 1),
+                             us_per_slot=round(1e3 * ms / N, 3), direct_ms=None if plain is None else round(plain, 4),
+                             speedup=None if plain is None else round(plain / ms, 2), pow2_decim=None if pow2 is None else pow2[0],
+                             k_channelize_grid_ms=None if pow2 is None else round(pow2[1], 4), awgn_tile_ms=round(awgn, 4)))
+            del d_out, d_a, d_b
+    rx.close()
+    print("ratio       M slots   n_out      ms    GB/s  us / slot  direct form ms  speedup  k_channelize_grid D ms  awgn_tile ms")
+    for r in rows:
+        print("%-7s %5d %5d %7d %7.4f %7.1f %10.3f %15s %8s %13s %9s %13.4f"
+              % (r["ratio"], r["m"], r["slots"], r["n_out"], r["ms"], r["gb_per_s"], r["us_per_slot"],
+                 "-" if r["direct_ms"] is None else "%.4f" % r["direct_ms"], "-" if r["speedup"] is None else "%.2f" % r["speedup"],
+                 "-" if r["pow2_decim"] is None else "%d" % r["pow2_decim"],
+                 "-" if r["k_channelize_grid_ms"] is None else "%.4f" % r["k_channelize_grid_ms"], r["awgn_tile_ms"]))
+    print(json.dumps({"tool": "channelize_bench", "samples": W, "grid_ratio_rows": rows}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--grid", action="append", nargs="+", default=[], metavar="D", help="time the grid front end at decimation D [SLOTS] (repeatable)")
+    ap.add_argument("--grid", action="append", nargs="+", default=[], metavar="D", help="time the grid front end at decimation D, or at the ratio P/Q, [SLOTS] (repeatable)")
     ap.add_argument("--ratio", action="append", default=[], metavar="P/Q", help="time the front end at this rational decimation (repeatable)")
     ap.add_argument("--samples", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=7)
@@ -321,6 +394,11 @@ def main():
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
+        if args.grid and any("/" in g[0] for g in args.grid):
+            if not all("/" in g[0] for g in args.grid):
+                print("channelize_bench: --grid takes either ratios P/Q or powers of two in one run", file=sys.stderr)
+                return 2
+            return child_grid_ratio(args)
         return child_grid(args) if args.grid else child_ratio(args) if args.ratio else child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
     for r in args.ratio:
