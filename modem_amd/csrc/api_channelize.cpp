@@ -60,7 +60,7 @@ int rechannelize_taps(int p, int q, float *taps)
 
 }  // namespace rx
 
-int rechannelize_ratio(int &p, int &q)
+int reduce_ratio(int &p, int &q)
 {
 	if (p <= 0 || q <= 0)
 		return OFDMRX_E_ARG;
@@ -72,9 +72,24 @@ int rechannelize_ratio(int &p, int &q)
 	}
 	p /= a;
 	q /= a;
-	if (q > 16 || p < 2 * q || p > 32 * q)
+	return 0;
+}
+
+int rechannelize_ratio(int &p, int &q)
+{
+	if (reduce_ratio(p, q) || q > 16 || p < 2 * q || p > 32 * q)
 		return OFDMRX_E_ARG;
 	return 0;
+}
+
+void grid_roots(int p, int n, bool negative, float *dst)
+{
+	const double pi = 3.14159265358979323846;
+	for (int j = 0; j < n; ++j) {
+		const double s = std::sin(pi * (double)j / (double)p);
+		dst[2 * j] = (float)std::cos(pi * (double)j / (double)p);
+		dst[2 * j + 1] = (float)(negative ? -s : s);
+	}
 }
 
 // the taps of the reduced ratio p / q and the increments of the centres on the device.  What is there already stays (a bank's pushes,
@@ -100,14 +115,10 @@ static int channelize_upload(ofdmrx_handle *h, int p, int q, int grid, const std
 			h->chz_taps_h[j * (size_t)q + r] = rows[r * T + j];
 	h->chz_tw_at = 0;
 	if (grid) {                                                   // e^{+2 pi i j / M}, j = 0 .. M / 2 - 1, on an 8-byte boundary
-		const double pi = 3.14159265358979323846;                     // (grid 2: e^{-2 pi i j / M}, j = 0 .. M - 1)
-		const int n_tw = grid == 2 ? 2 * p : p;
+		const int n_tw = grid == 2 ? 2 * p : p;                       // (grid 2: e^{-2 pi i j / M}, j = 0 .. M - 1)
 		h->chz_tw_at = ((size_t)q * T + 1) / 2 * 2;
 		h->chz_taps_h.resize(h->chz_tw_at + 2 * (size_t)n_tw, 0.f);
-		for (int j = 0; j < n_tw; ++j) {
-			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j] = (float)std::cos(pi * (double)j / (double)p);
-			h->chz_taps_h[h->chz_tw_at + 2 * (size_t)j + 1] = (float)(grid == 2 ? -std::sin(pi * (double)j / (double)p) : std::sin(pi * (double)j / (double)p));
-		}
+		grid_roots(p, n_tw, grid == 2, h->chz_taps_h.data() + h->chz_tw_at);
 	}
 	h->chz_inc_h = inc;
 	int r = h->chz_taps.ensure(h->chz_taps_h.size() * sizeof(float));
@@ -166,17 +177,7 @@ int channelize_grid_setup(ofdmrx_handle *h, int decim, const std::vector<int32_t
 // the grid front end at a ratio: p / q reduced here; 1 <= q <= 16, 2 q <= p <= 512, p = 2^a 3^b 5^c
 int channelize_grid_ratio(int &p, int &q)
 {
-	if (p <= 0 || q <= 0)
-		return OFDMRX_E_ARG;
-	int a = p, b = q;
-	while (b) {
-		const int t = a % b;
-		a = b;
-		b = t;
-	}
-	p /= a;
-	q /= a;
-	if (q > 16 || p < 2 * q || p > 512)
+	if (reduce_ratio(p, q) || q > 16 || p < 2 * q || p > 512)
 		return OFDMRX_E_ARG;
 	int m = p;
 	for (int f : { 2, 3, 5 })
@@ -209,9 +210,11 @@ int channelize_grid_ratio_slots(int p, int q, const int32_t *slots, size_t n_slo
 }
 
 // q = 1 with p a power of two is 4.19 itself: its table, its kernel, its bytes
+static bool is_plain_grid(int p, int q) { return q == 1 && !channelize_grid_decim(p); }
+
 int channelize_grid_ratio_setup(ofdmrx_handle *h, int p, int q, const std::vector<int32_t> &slots)
 {
-	if (q == 1 && !channelize_grid_decim(p))
+	if (is_plain_grid(p, q))
 		return channelize_grid_setup(h, p, slots);
 	const GridRatioPlan pl = channelize_grid_ratio_plan(p, q);
 	std::vector<unsigned> inc(slots.size());
@@ -265,7 +268,7 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 		return OFDMRX_E_ARG;
 	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || out_first < 0 || out_stride < n_out)
 		return OFDMRX_E_ARG;
-	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)(!grid ? channelize_max_outputs(q) : (q == 1 && !channelize_grid_decim(p)) ? channelize_grid_max_outputs() : channelize_grid_ratio_max_outputs()) || out_stride > (size_t)FAR / 65536)
+	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)(!grid ? channelize_max_outputs(q) : is_plain_grid(p, q) ? channelize_grid_max_outputs() : channelize_grid_ratio_max_outputs()) || out_stride > (size_t)FAR / 65536)
 		return OFDMRX_E_ARG;
 	const size_t unit = 2 * sample_bytes(sample_format);
 	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))

@@ -299,8 +299,12 @@ int finish_call(ofdmrx_handle *h, int r);                                       
 // channel q would lie at fb.samples + org[q] bytes and the channel has len[q] sample frames so far (kernels.h: WindowBatch)
 struct RecordSources { const int *src_of; const int *src_len; size_t stride_bytes; const long long *org = nullptr; const long long *len = nullptr; };
 int decode_records(ofdmrx_handle *h, FrameBatch fb, const SyncState *d_records, size_t n, Outputs out, const RecordSources &srcs);
-// p / q -> lowest terms; OFDMRX_E_ARG unless p, q > 0, the reduced q <= 16 and 2 <= p / q <= 32
-int rechannelize_ratio(int &p, int &q);                                                     // api_channelize.cpp
+// p / q -> lowest terms (OFDMRX_E_ARG unless p, q > 0); rechannelize_ratio: and the reduced q <= 16 and 2 <= p / q <= 32
+int reduce_ratio(int &p, int &q);                                                           // api_channelize.cpp
+int rechannelize_ratio(int &p, int &q);
+// the roots of a grid table: dst[2 j], dst[2 j + 1] = e^{+-i pi j / p}, j = 0 .. n - 1 (negative: the minus sign), made in double and
+// rounded once
+void grid_roots(int p, int n, bool negative, float *dst);
 int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels);   // (p / q reduced; q = 1: decimation p)
 // the grid front end: decim a power of two 2 .. 512 (else OFDMRX_E_ARG); the slots of a grid table, -decim ..
 // decim - 1 each (slots = nullptr: all 2 decim in ascending order, n_slots must be 2 decim), and the table itself on the device

@@ -216,9 +216,7 @@ extern "C" int ofdmrx_util_survey_grid(ofdmrx_handle *h, const void *d_in, int s
 	SurveyGridArgs a{};
 	a.in = d_in;
 	a.fmt = sample_format;
-	a.logm = 0;
-	while ((1 << a.logm) < M)
-		++a.logm;
+	a.logm = grid_logm(decim);
 	a.in_first = in_first;
 	a.n_in = (long long)n_in;
 	a.taps = t.taps;

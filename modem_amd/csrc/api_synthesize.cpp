@@ -44,14 +44,10 @@ static int synthesize_setup(ofdmrx_handle *h, int p, int q, bool grid, const std
 		resynthesize_taps(p, q, s->taps);
 	}
 	s->tw_at = 0;
-	if (grid) {                                                   // e^{+2 pi i j / M}, j = 0 .. M / 2 - 1, as the grid front end makes them
-		const double pi = 3.14159265358979323846;
+	if (grid) {                                                   // e^{+2 pi i j / M}, j = 0 .. M / 2 - 1: the grid front end's table
 		s->tw_at = (s->taps.size() + 1) / 2 * 2;
 		s->taps.resize(s->tw_at + 2 * (size_t)p, 0.f);
-		for (int j = 0; j < p; ++j) {
-			s->taps[s->tw_at + 2 * (size_t)j] = (float)std::cos(pi * (double)j / (double)p);
-			s->taps[s->tw_at + 2 * (size_t)j + 1] = (float)std::sin(pi * (double)j / (double)p);
-		}
+		grid_roots(p, p, false, s->taps.data() + s->tw_at);
 	}
 	const size_t ch_bytes = ch.size() * sizeof(SynthChannel), tap_bytes = s->taps.size() * sizeof(float);
 	const int r = s->dev.ensure(ch_bytes + tap_bytes);

@@ -21,6 +21,7 @@
 // Contract on order: u_n[r] is one FMA chain per component, a ascending; a position outside [in_first, in_first + n_in) is never
 // loaded and enters as +0.  No state: a capture cut into blocks, each with the T - 1 samples before it, gives the bytes of one call.
 #include "dev_common.h"
+#include "grid_bank.h"
 #include "kernels.h"
 
 namespace rx {
@@ -29,9 +30,11 @@ constexpr int CGR_THREADS = 256;
 constexpr int CGR_HIST = 13;           // taps per branch at most: T <= 12 M + 1
 constexpr int CGR_LDS = 61440;         // bytes of a tile at most
 
+// grid_bank.h's multiply on a cf
 __device__ __forceinline__ cf cgr_mul(cf a, float2 w)
 {
-	return mk(__builtin_fmaf(a.re, w.x, -(a.im * w.y)), __builtin_fmaf(a.re, w.y, a.im * w.x));
+	const float2 v = grid_mul(make_float2(a.re, a.im), w);
+	return mk(v.x, v.y);
 }
 
 // one stage of radix R on blocks of N points, every time of the tile

@@ -4,7 +4,7 @@
 //   row r:  P[r][k + M / 2] = (1 / S) sum_{n = r S .. r S + S - 1} |y_k[n]|^2,   k = -M / 2 .. M / 2 - 1.
 // k_survey_grid: one workgroup of 256 threads per tile of NT = max(8, 4096 / M) output times, the tiles counted from the call's first
 // time row_first S - a multiple of 8, so a tile holds whole groups of 8 times (group g: the times 8 g .. 8 g + 7) and no group
-// straddles a row.  Steps 1 and 2 are k_channelize_grid's, restated here so that that file and its code stay as they are:
+// straddles a row.  Steps 1 and 2 are k_channelize_grid's: the same code, grid_bank.h's, so the same bytes in LDS:
 //   1. the branch sums u_n[r] of the tile into LDS (time minor, rows of NT + 1), one FMA chain per component with a ascending;
 //   2. the radix-2 decimation-in-frequency transform in place: natural order in, slot k's sum in row brev(k mod M) out;
 //   3. every (LDS row, group of the tile) is reduced to one float and stored at part[(group counted from the call's first)][LDS row]:
@@ -20,134 +20,30 @@
 // fp32 chain over the 8 times of a group in ascending time, one fp32 chain over a row's groups in ascending order, one product.
 // No float atomics, no "last workgroup finishes".  All-zero input gives +0.
 #include "dev_common.h"
+#include "grid_bank.h"
 #include "kernels.h"
 
 namespace rx {
 
-constexpr int SVG_THREADS = 256;
-// output times per tile: 4096 points of LDS, and never fewer than one group
-__host__ __device__ constexpr int svg_tile(int logm) { return (4096 >> logm) > SURVEY_GRID_G ? (4096 >> logm) : SURVEY_GRID_G; }
-
-__device__ __forceinline__ float2 svg_mul(float2 a, float2 w)
-{
-	return make_float2(__builtin_fmaf(a.x, w.x, -(a.y * w.y)), __builtin_fmaf(a.x, w.y, a.y * w.x));
-}
-// one butterfly of the stage whose root for this pair is w
-__device__ __forceinline__ void svg_bfly(float2 &p, float2 &q, float2 w)
-{
-	const float2 s = make_float2(p.x + q.x, p.y + q.y), d = make_float2(p.x - q.x, p.y - q.y);
-	p = s;
-	q = svg_mul(d, w);
-}
-
 template <int FMT, int LOGM>
-__global__ __launch_bounds__(SVG_THREADS) void k_survey_grid(SurveyGridArgs a)
+__global__ __launch_bounds__(GRID_THREADS) void k_survey_grid(SurveyGridArgs a)
 {
-	constexpr int M = 1 << LOGM, D = M / 2, NT = svg_tile(LOGM), NTS = NT + 1, HIST = 12, GRP = SURVEY_GRID_G;
-	static_assert(NT % GRP == 0, "a tile holds whole groups");
+	constexpr int M = 1 << LOGM, NT = grid_tile(LOGM), NTS = NT + 1, GRP = SURVEY_GRID_G;
+	static_assert(grid_tile(LOGM) % SURVEY_GRID_G == 0, "a tile holds whole groups");
 	__shared__ float2 u[M * NTS];
 	const int tid = threadIdx.x;
 	const long long j0 = (long long)blockIdx.x * NT;              // the tile's first time, counted from the call's first
 	const long long n0 = a.t_first + j0;
 	const int nt = (int)(a.n_times - j0 < NT ? a.n_times - j0 : NT);  // times of the tile that exist: a multiple of 8
 
-	// ---- 1. the branch sums (k_channelize_grid's step 1: a thread takes a run of CH times of one parity of its branch r and loads
-	// the CH + 12 samples j = -(CH - 1) .. 12 once each; sample j meets time s at tap a = j + s, ascending in a for every s)
-	{
-		constexpr int G = M < SVG_THREADS ? SVG_THREADS / M : 1;      // threads per branch
-		constexpr int CH = M < SVG_THREADS ? 16 : NT / 2;             // times per run (G CH = NT, or 2 CH = NT)
-		static_assert((G > 1 ? G * CH : 2 * CH) == NT, "the runs tile the times");
-		const int g = M < SVG_THREADS ? tid >> LOGM : 0;
-		for (int r = tid & (M < SVG_THREADS ? M - 1 : SVG_THREADS - 1); r < M; r += SVG_THREADS) {
-			float h[HIST + 1];
-			#pragma unroll
-			for (int i = 0; i < HIST; ++i)
-				h[i] = a.taps[r + M * i];
-			h[HIST] = r == 0 ? a.taps[M * HIST] : 0.f;
-			for (int run = 0; run < (G > 1 ? 1 : 2); ++run) {
-				const int e = G > 1 ? g & 1 : run, s0 = G > 1 ? (g >> 1) * CH : 0;
-				const int tf = e + 2 * s0;                                // the run's first time: t = tf + 2 s
-				float re[CH], im[CH];
-				#pragma unroll
-				for (int s = 0; s < CH; ++s)
-					re[s] = im[s] = 0.f;
-				const long long m0 = (n0 + tf) * D - r - a.in_first;      // sample j = 0 of the run, counted from the buffer's first
-				#pragma unroll
-				for (int j = -(CH - 1); j <= HIST; ++j) {
-					if (j == HIST && r != 0)                                  // tap a = 12 exists for branch 0 alone
-						continue;
-					const long long m = m0 - (long long)M * j;
-					float2 x = make_float2(0.f, 0.f);
-					if (m >= 0 && m < a.n_in)                                 // (below position 0, or a time past the tile's last that exists)
-						x = iq_sample<FMT>(a.in, (size_t)m);
-					#pragma unroll
-					for (int s = 0; s < CH; ++s) {
-						const int i = j + s;                                  // the tap
-						if (i < 0 || i > HIST || (i == HIST && r != 0))
-							continue;
-						re[s] = __builtin_fmaf(h[i], x.x, re[s]);
-						im[s] = __builtin_fmaf(h[i], x.y, im[s]);
-					}
-				}
-				#pragma unroll
-				for (int s = 0; s < CH; ++s)
-					u[r * NTS + tf + 2 * s] = make_float2(re[s], im[s]);
-			}
-		}
-	}
-	__syncthreads();
-
-	// ---- 2. the transform (k_channelize_grid's step 2): the stages of half-length M / 2, M / 4 .. 1, two per pass
-	const float2 *tw = a.tw;
-	#pragma unroll
-	for (int lq = LOGM - 2; lq >= 0; lq -= 2) {
-		const int Q = 1 << lq;
-		for (int it = tid; it < (M / 4) * NT; it += SVG_THREADS) {
-			int b, t;
-			if (NT >= 64) {
-				t = it & (NT - 1);
-				b = it / NT;
-			} else {
-				b = it & (M / 4 - 1);
-				t = it >> (LOGM - 2);
-			}
-			const int j = b & (Q - 1), i = ((b >> lq) << (lq + 2)) + j;
-			float2 *x = u + i * NTS + t;
-			float2 x0 = x[0], x1 = x[Q * NTS], x2 = x[2 * Q * NTS], x3 = x[3 * Q * NTS];
-			const float2 wa = tw[j << (LOGM - 2 - lq)], wb = tw[(j + Q) << (LOGM - 2 - lq)], wc = tw[j << (LOGM - 1 - lq)];
-			svg_bfly(x0, x2, wa);
-			svg_bfly(x1, x3, wb);
-			svg_bfly(x0, x1, wc);
-			svg_bfly(x2, x3, wc);
-			x[0] = x0;
-			x[Q * NTS] = x1;
-			x[2 * Q * NTS] = x2;
-			x[3 * Q * NTS] = x3;
-		}
-		__syncthreads();
-	}
-	if (LOGM & 1) {                                               // the stage of half-length 1: its root is 1
-		for (int it = tid; it < (M / 2) * NT; it += SVG_THREADS) {
-			int b, t;
-			if (NT >= 64) {
-				t = it & (NT - 1);
-				b = it / NT;
-			} else {
-				b = it & (M / 2 - 1);
-				t = it >> (LOGM - 1);
-			}
-			float2 *x = u + 2 * b * NTS + t;
-			float2 x0 = x[0], x1 = x[NTS];
-			svg_bfly(x0, x1, tw[0]);
-			x[0] = x0;
-			x[NTS] = x1;
-		}
-		__syncthreads();
-	}
+	// ---- 1. the branch sums (a position below 0, or of a time past the tile's last that exists, lies outside the buffer: not loaded),
+	// 2. the transform: slot k's sum in row brev(k mod M)
+	grid_branch_sums<FMT, LOGM>(u, a, n0, tid);
+	grid_dif<LOGM>(u, a.tw, tid);
 
 	// ---- 3. the groups' powers: item (group g of the tile, LDS row), rows along the lanes; the tile's partials are one contiguous run
 	float *dst = a.part + (size_t)(j0 / GRP) * M;
-	for (int it = tid; it < (nt / GRP) * M; it += SVG_THREADS) {
+	for (int it = tid; it < (nt / GRP) * M; it += GRID_THREADS) {
 		const int row = it & (M - 1), g = it >> LOGM;
 		const float2 *x = u + row * NTS + g * GRP;
 		float s = 0.f;
@@ -241,25 +137,12 @@ __global__ __launch_bounds__(256) void k_survey_grid_rows_staged(SurveyGridArgs 
 	}
 }
 
-template <int FMT, int LOGM> static void svg_launch2(hipStream_t s, const SurveyGridArgs &a)
-{
-	constexpr int NT = svg_tile(LOGM);
-	hipLaunchKernelGGL((k_survey_grid<FMT, LOGM>), dim3((unsigned)((a.n_times + NT - 1) / NT)), dim3(SVG_THREADS), 0, s, a);
-}
-
 template <int FMT> static void svg_launch(hipStream_t s, const SurveyGridArgs &a)
 {
-	switch (a.logm) {
-	case 2: svg_launch2<FMT, 2>(s, a); break;
-	case 3: svg_launch2<FMT, 3>(s, a); break;
-	case 4: svg_launch2<FMT, 4>(s, a); break;
-	case 5: svg_launch2<FMT, 5>(s, a); break;
-	case 6: svg_launch2<FMT, 6>(s, a); break;
-	case 7: svg_launch2<FMT, 7>(s, a); break;
-	case 8: svg_launch2<FMT, 8>(s, a); break;
-	case 9: svg_launch2<FMT, 9>(s, a); break;
-	case 10: svg_launch2<FMT, 10>(s, a); break;
-	}
+	grid_dispatch(a.logm, [&](auto c) {
+		constexpr int LOGM = decltype(c)::value, NT = grid_tile(LOGM);
+		hipLaunchKernelGGL((k_survey_grid<FMT, LOGM>), dim3((unsigned)((a.n_times + NT - 1) / NT)), dim3(GRID_THREADS), 0, s, a);
+	});
 }
 
 void launch_survey_grid(hipStream_t s, const SurveyGridArgs &a, float scale)

@@ -9,7 +9,7 @@
 //   w[q D + b] = sum_{a = 0 .. 23, and a = 24 where b = 0} h[b + a D] V_{q - a}[b + (a mod 2) D],  0 <= b < D;  V_j = 0 for j < 0.
 // No NCO: the only irrational numbers are the transform's roots, which the host makes in double (a.tw, section 4.19's table).
 // Two kernels, since an output meets V at 25 input times and one time is up to 8 KiB:
-//   k_synthesize_grid_transform: one workgroup of 256 threads makes a tile of chg_tile(LOGM) input times in LDS, u[row][t] (time
+//   k_synthesize_grid_transform: one workgroup of 256 threads makes a tile of grid_tile(LOGM) input times in LDS, u[row][t] (time
 //     minor, rows of NT + 1).  It clears the tile, places the rows' samples - lanes along time, so a row's loads are contiguous - at
 //     row brev(k mod M), and runs the transform in place, decimation in time, radix 2, two stages per pass over LDS: bit-reversed
 //     order in, natural order out.  Stage of half-length H: (p, q) = (x[i] + w x[i + H], x[i] - w x[i + H]), w = tw[j M / (2 H)],
@@ -22,31 +22,17 @@
 // Contract on order: G_c x is one fp32 product; w is one FMA chain per component from +0, a ascending; every output passes through
 // v + 0.f (iq_store).  No state: V_j is a function of j alone, so windows, tiles and the host's chunks change no byte.
 #include "dev_common.h"
+#include "grid_bank.h"
 #include "kernels.h"
 
 namespace rx {
 
-constexpr int SYG_THREADS = 256;
 constexpr int SYG_HIST = 24;
-// input times per tile of the transform: k_channelize_grid's tile
-__host__ __device__ constexpr int syg_tile(int logm) { return (4096 >> logm) > 8 ? (4096 >> logm) : 8; }
-
-__device__ __forceinline__ float2 syg_mul(float2 a, float2 w)
-{
-	return make_float2(__builtin_fmaf(a.x, w.x, -(a.y * w.y)), __builtin_fmaf(a.x, w.y, a.y * w.x));
-}
-// one butterfly of a decimation-in-time stage whose root for this pair is w
-__device__ __forceinline__ void syg_bfly(float2 &p, float2 &q, float2 w)
-{
-	const float2 b = syg_mul(q, w);
-	q = make_float2(p.x - b.x, p.y - b.y);
-	p = make_float2(p.x + b.x, p.y + b.y);
-}
 
 template <int IFMT, int LOGM>
-__global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(SynthesizeGridArgs a)
+__global__ __launch_bounds__(GRID_THREADS) void k_synthesize_grid_transform(SynthesizeGridArgs a)
 {
-	constexpr int M = 1 << LOGM, NT = syg_tile(LOGM), NTS = NT + 1;
+	constexpr int M = 1 << LOGM, NT = grid_tile(LOGM), NTS = NT + 1;
 	__shared__ float2 u[M * NTS];
 	const int tid = threadIdx.x;
 	const int t0 = blockIdx.x * NT;                               // the tile's first time in the scratch
@@ -55,21 +41,21 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(Synth
 
 	// does any row reach the tile?  Row c holds the times sigma_c .. sigma_c + n_in - 1
 	int hit = 0;
-	for (int c = tid; c < a.n_channels; c += SYG_THREADS) {
+	for (int c = tid; c < a.n_channels; c += GRID_THREADS) {
 		const long long sg = a.ch[c].start >> (LOGM - 1);
 		hit |= sg <= j0 + NT - 1 && sg + a.n_in - 1 >= j0;
 	}
 	if (!__syncthreads_or(hit)) {
-		for (int it = tid; it < M * NT; it += SYG_THREADS)
+		for (int it = tid; it < M * NT; it += GRID_THREADS)
 			dst[it] = make_float2(0.f, 0.f);
 		return;
 	}
 
 	// ---- 1. X: zeros, then the rows' samples at row brev(k mod M); (-1)^{k j}.  The slots are distinct: no two items share a point
-	for (int it = tid; it < M * NTS; it += SYG_THREADS)
+	for (int it = tid; it < M * NTS; it += GRID_THREADS)
 		u[it] = make_float2(0.f, 0.f);
 	__syncthreads();
-	for (int it = tid; it < a.n_channels * NT; it += SYG_THREADS) {
+	for (int it = tid; it < a.n_channels * NT; it += GRID_THREADS) {
 		const int t = it & (NT - 1), c = it / NT;
 		const SynthChannel ch = a.ch[c];
 		const long long j = j0 + t, i = j - (ch.start >> (LOGM - 1));
@@ -86,10 +72,11 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(Synth
 
 	// ---- 2. the transform: the stages of half-length 1, 2 .. M / 2 (the first alone when their number is odd), then two per pass.
 	// A pass takes the points i, i + Q, i + 2 Q, i + 3 Q: stage Q pairs (i, i + Q) and (i + 2 Q, i + 3 Q), stage 2 Q pairs
-	// (i, i + 2 Q) and (i + Q, i + 3 Q).  Work item (b, t): lanes along t where a tile has 64 times
+	// (i, i + 2 Q) and (i + Q, i + 3 Q).  Work item (b, t): lanes along t where a tile has 64 times.  (The mirror image of
+	// grid_bank.h's grid_dif; why the loops stand here and not there is said in that header)
 	const float2 *tw = a.tw;
 	if (LOGM & 1) {                                               // the stage of half-length 1: its root is 1
-		for (int it = tid; it < (M / 2) * NT; it += SYG_THREADS) {
+		for (int it = tid; it < (M / 2) * NT; it += GRID_THREADS) {
 			int b, t;
 			if (NT >= 64) {
 				t = it & (NT - 1);
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(Synth
 			}
 			float2 *x = u + 2 * b * NTS + t;
 			float2 x0 = x[0], x1 = x[NTS];
-			syg_bfly(x0, x1, tw[0]);
+			grid_bfly_dit(x0, x1, tw[0]);
 			x[0] = x0;
 			x[NTS] = x1;
 		}
@@ -109,7 +96,7 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(Synth
 	#pragma unroll
 	for (int lq = LOGM & 1; lq <= LOGM - 2; lq += 2) {
 		const int Q = 1 << lq;
-		for (int it = tid; it < (M / 4) * NT; it += SYG_THREADS) {
+		for (int it = tid; it < (M / 4) * NT; it += GRID_THREADS) {
 			int b, t;
 			if (NT >= 64) {
 				t = it & (NT - 1);
@@ -123,10 +110,10 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(Synth
 			float2 x0 = x[0], x1 = x[Q * NTS], x2 = x[2 * Q * NTS], x3 = x[3 * Q * NTS];
 			// stage Q: w^{j M / (2 Q)} for both pairs; stage 2 Q: the roots w^{j' M / (4 Q)} of j' = j and j + Q
 			const float2 wc = tw[j << (LOGM - 1 - lq)], wa = tw[j << (LOGM - 2 - lq)], wb = tw[(j + Q) << (LOGM - 2 - lq)];
-			syg_bfly(x0, x1, wc);
-			syg_bfly(x2, x3, wc);
-			syg_bfly(x0, x2, wa);
-			syg_bfly(x1, x3, wb);
+			grid_bfly_dit(x0, x1, wc);
+			grid_bfly_dit(x2, x3, wc);
+			grid_bfly_dit(x0, x2, wa);
+			grid_bfly_dit(x1, x3, wb);
 			x[0] = x0;
 			x[Q * NTS] = x1;
 			x[2 * Q * NTS] = x2;
@@ -136,20 +123,20 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_transform(Synth
 	}
 
 	// ---- 3. V to the scratch: point t M + r is row r, time t of the tile
-	for (int it = tid; it < M * NT; it += SYG_THREADS)
+	for (int it = tid; it < M * NT; it += GRID_THREADS)
 		dst[it] = u[(it & (M - 1)) * NTS + (it >> LOGM)];
 }
 
 // outputs per work item, D apart; work items per tile: one per b, and 256 / D groups where D < 256
 constexpr int SYG_R = 8;
-__host__ __device__ constexpr int syg_groups(int logm) { return (1 << (logm - 1)) < SYG_THREADS ? SYG_THREADS >> (logm - 1) : 1; }
+__host__ __device__ constexpr int syg_groups(int logm) { return (1 << (logm - 1)) < GRID_THREADS ? GRID_THREADS >> (logm - 1) : 1; }
 
 template <int OFMT, int LOGM>
-__global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_filter(SynthesizeGridArgs a)
+__global__ __launch_bounds__(GRID_THREADS) void k_synthesize_grid_filter(SynthesizeGridArgs a)
 {
 	constexpr int M = 1 << LOGM, D = M / 2, G = syg_groups(LOGM), QT = G * SYG_R, R = SYG_R;
 	const long long out_hi = a.out_first + a.n_out;
-	for (int item = threadIdx.x; item < G * D; item += SYG_THREADS) {
+	for (int item = threadIdx.x; item < G * D; item += GRID_THREADS) {
 		const int g = item >> (LOGM - 1), b = item & (D - 1);
 		const int qs = blockIdx.x * QT + g * R;                       // the item's first output time, counted from the chunk's first
 		if (qs >= a.nq)
@@ -193,52 +180,16 @@ __global__ __launch_bounds__(SYG_THREADS) void k_synthesize_grid_filter(Synthesi
 	}
 }
 
-int synthesize_grid_tile_times(int interp)
-{
-	int logm = 1;
-	while ((1 << logm) < 2 * interp)
-		++logm;
-	return syg_tile(logm);
-}
-
-int synthesize_grid_filter_times(int interp)
-{
-	int logm = 1;
-	while ((1 << logm) < 2 * interp)
-		++logm;
-	return syg_groups(logm) * SYG_R;
-}
-
-template <int IFMT, int LOGM> static void syg_transform2(hipStream_t s, const SynthesizeGridArgs &a)
-{
-	hipLaunchKernelGGL((k_synthesize_grid_transform<IFMT, LOGM>), dim3((unsigned)(a.n_times / syg_tile(LOGM))), dim3(SYG_THREADS), 0, s, a);
-}
-
-template <int OFMT, int LOGM> static void syg_filter2(hipStream_t s, const SynthesizeGridArgs &a)
-{
-	constexpr int QT = syg_groups(LOGM) * SYG_R;
-	hipLaunchKernelGGL((k_synthesize_grid_filter<OFMT, LOGM>), dim3((unsigned)((a.nq + QT - 1) / QT)), dim3(SYG_THREADS), 0, s, a);
-}
-
-template <int IFMT, int OFMT, int LOGM> static void syg_launch2(hipStream_t s, const SynthesizeGridArgs &a)
-{
-	syg_transform2<IFMT, LOGM>(s, a);
-	syg_filter2<OFMT, LOGM>(s, a);
-}
+int synthesize_grid_tile_times(int interp) { return grid_tile(grid_logm(interp)); }
+int synthesize_grid_filter_times(int interp) { return syg_groups(grid_logm(interp)) * SYG_R; }
 
 template <int IFMT, int OFMT> static void syg_launch(hipStream_t s, const SynthesizeGridArgs &a)
 {
-	switch (a.p) {
-	case 2: syg_launch2<IFMT, OFMT, 2>(s, a); break;
-	case 4: syg_launch2<IFMT, OFMT, 3>(s, a); break;
-	case 8: syg_launch2<IFMT, OFMT, 4>(s, a); break;
-	case 16: syg_launch2<IFMT, OFMT, 5>(s, a); break;
-	case 32: syg_launch2<IFMT, OFMT, 6>(s, a); break;
-	case 64: syg_launch2<IFMT, OFMT, 7>(s, a); break;
-	case 128: syg_launch2<IFMT, OFMT, 8>(s, a); break;
-	case 256: syg_launch2<IFMT, OFMT, 9>(s, a); break;
-	case 512: syg_launch2<IFMT, OFMT, 10>(s, a); break;
-	}
+	grid_dispatch(grid_logm(a.p), [&](auto c) {
+		constexpr int LOGM = decltype(c)::value, QT = syg_groups(LOGM) * SYG_R;
+		hipLaunchKernelGGL((k_synthesize_grid_transform<IFMT, LOGM>), dim3((unsigned)(a.n_times / grid_tile(LOGM))), dim3(GRID_THREADS), 0, s, a);
+		hipLaunchKernelGGL((k_synthesize_grid_filter<OFMT, LOGM>), dim3((unsigned)((a.nq + QT - 1) / QT)), dim3(GRID_THREADS), 0, s, a);
+	});
 }
 
 void launch_synthesize_grid(hipStream_t s, const SynthesizeGridArgs &a)

@@ -366,6 +366,15 @@ void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
 void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a);   // k_rechannelize.hip: launch_channelize's q > 1
 long long channelize_max_outputs(int q);
 void launch_channelize_grid(hipStream_t s, const ChannelizeArgs &a);    // k_channelize_grid.hip: a.grid != 0 (the callers choose)
+// log2 M of the grid's D = 2, 4 .. 512 (M = 2 D), for the front end, the synthesizer and the survey; D must be one of those powers of
+// two (channelize_grid_decim): any other D is rounded up to the next, which is not its transform
+constexpr int grid_logm(int D)
+{
+	int logm = 1;
+	while ((1 << logm) < 2 * D)
+		++logm;
+	return logm;
+}
 long long channelize_grid_max_outputs();
 // the grid front end at a ratio (k_channelize_grid_ratio.hip): a.grid == 2, p / q in lowest terms with p = 2^a 3^b 5^c
 // (not q = 1 with p a power of two: that is 4.19's kernel), M = 2 p; taps as launch_channelize_ratio reads them; tw: device, the M

@@ -4,6 +4,7 @@ in the model's header.  Input is full scale in sum: random values plus a tone on
 buffer starts exactly at the first position its rows need and ends at the last.  Each test prints its worst |got - P| / tol
 (profiles/survey_grid_parity.txt keeps them)."""
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -199,6 +200,54 @@ def test_identity_with_the_grid_front_end(rx, D):
     w = float(np.max(np.abs(got - Pc) / (tol + first_term)))
     print("survey_grid M %d against mean |channelize_grid|^2: worst |difference| / (tol + tol) %.4f" % (2 * D, w))
     assert w <= 1.0
+
+
+def _round_fp32(e):
+    """the fp32 nearest the rational e, ties to even: the better of the neighbours of a first guess, which lies within one step"""
+    c = np.float32(float(e))
+    cands = (c, np.nextafter(c, np.float32(np.inf)), np.nextafter(c, np.float32(-np.inf)))
+    return min(cands, key=lambda v: (abs(Fraction(float(v)) - e), int(v.view(np.uint32)) & 1))
+
+
+def _power_fp32_exact(y):
+    """fma(im, im, re re) as the kernel forms it: re re rounded to fp32, then im im + that formed exactly and rounded once (float64
+    would round twice)"""
+    rr = y[..., 0] * y[..., 0]
+    assert rr.dtype == np.float32
+    p = [_round_fp32(Fraction(im) * Fraction(im) + Fraction(a)) for im, a in zip(y[..., 1].ravel().tolist(), rr.ravel().tolist())]
+    return np.array(p, np.float32).reshape(rr.shape)
+
+
+@pytest.mark.parametrize("D", [2, 32, 128])
+def test_bytes_follow_from_the_grid_front_end(rx, D):
+    """the survey's steps 1 and 2 are the front end's code (grid_bank.h), so its rows are a function of the front end's bytes:
+    channelize_grid over all slots and survey_grid on one device buffer, then on the host |y|^2 = fma(im, im, re re), the fp32 chain
+    over the 8 times of a group, the fp32 chain over a row's groups and the product with fp32(1 / S), in the order section 4.21
+    fixes - byte for byte.  M = 4: lanes along the time axis in the transform; 64: one point per lane; 256: the instantiation with
+    the most registers"""
+    import torch
+    S, n_rows = tile(D) + 8, 3
+    pcm, first = _input(D, S, 0, n_rows, seed=13)
+    assert first == 0
+    n_out = S * n_rows
+    d_in = _dev(pcm)
+    out = torch.full((2 * D, n_out, 2), SENTINEL, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    rx.channelize_grid(d_in.data_ptr(), 0, 0, len(pcm), D, None, 0, n_out, out.data_ptr())
+    got = rx.survey_grid(d_in, 0, D, S, in_first=0, row_first=0, n_rows=n_rows).cpu().numpy()
+    rx.synchronize()
+    assert got.shape == (n_rows, 2 * D) and got.dtype == np.float32
+    p = _power_fp32_exact(out.cpu().numpy()).reshape(2 * D, n_rows, S // 8, 8)    # [slot][row][group][time]
+    grp = p[..., 0]
+    for t in range(1, 8):
+        grp = grp + p[..., t]
+    row = grp[..., 0]
+    for g in range(1, S // 8):
+        row = row + grp[..., g]
+    want = np.ascontiguousarray((row * np.float32(1.0 / S)).T)
+    assert want.dtype == np.float32
+    print("survey_grid M %d from channelize_grid's bytes: %d of %d values differ" % (2 * D, int((want.view(np.uint32) != got.view(np.uint32)).sum()), want.size))
+    assert want.tobytes() == got.tobytes()
 
 
 def test_refusals_leave_the_output_untouched(rx):
