@@ -66,7 +66,9 @@ extern "C" {
  *      a channel grid (a polyphase synthesis bank) - ofdmrx_util_synthesize_grid, ofdmrx_util_synthesize_grid_chunk; the grid
  *      survey (per-slot power from the filter bank) - ofdmrx_util_survey_grid, ofdmrx_util_find_slots; the wideband front end on a
  *      channel grid at any ratio P / Q (a mixed-radix filter bank) - ofdmrx_util_channelize_grid_ratio_taps,
- *      ofdmrx_util_grid_ratio_slots, ofdmrx_util_channelize_grid_ratio, ofdmrx_bank_begin_wideband_grid_ratio */
+ *      ofdmrx_util_grid_ratio_slots, ofdmrx_util_channelize_grid_ratio, ofdmrx_bank_begin_wideband_grid_ratio; the wideband
+ *      synthesizer on a channel grid at any ratio P / Q (a mixed-radix synthesis bank) - ofdmrx_util_synthesize_grid_ratio,
+ *      ofdmrx_util_synthesize_grid_ratio_chunk */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -767,6 +769,35 @@ int ofdmrx_util_synthesize_grid(ofdmrx_handle *h, const void *d_in, int in_forma
 	const int32_t *slots, const long long *start, const float *gain, size_t n_slots, long long out_first, size_t n_out,
 	void *d_out, int out_format);
 long long ofdmrx_util_synthesize_grid_chunk(int interp);
+
+/* Wideband synthesizer on a channel grid at any ratio P / Q (added within revision 1.9, detected by symbol), the mirror image of
+ * ofdmrx_util_channelize_grid_ratio: a mixed-radix synthesis bank.  DESIGN.md section 4.23 is the definition, held component by
+ * component to a float64 model.  p / q is reduced here; in lowest terms 1 <= q <= 16, 2 q <= p <= 512, p = 2^a 3^b 5^c - the limits of
+ * ofdmrx_util_channelize_grid_ratio.  The capture's rate is rate p / q, M = 2 p, and G[tn], tn = 0 .. 24 p, is the tap sequence of
+ * ofdmrx_util_synthesize_ratio (G[tn] = H[tn mod q][tn div q] over the table ofdmrx_util_channelize_grid_ratio_taps(p, q, .) writes;
+ * there is no new filter).  Row c belongs to slot k_c = slots[c] with -p <= k_c q < p (a host array of pairwise distinct slots; NULL
+ * with n_slots = n_all of ofdmrx_util_grid_ratio_slots: every slot in ascending k), centred at k_c rate / 2.  With m q = J p + beta
+ * (0 <= beta < p) at the absolute wideband index m:
+ *   output  w[m] = sum_c G_c e^{+2 pi i (k_c q m mod M) / M} sum_a G[beta + a p] x_c[J - a - start[c] q / p], a = 0 .. 23, and a = 24
+ *           where beta = 0; G_c = (p / q) gain[c] as in ofdmrx_util_synthesize_ratio; start[c] >= 0 in wideband samples, a MULTIPLE
+ *           OF p.
+ * This is ofdmrx_util_synthesize_ratio's output for the centres k_c rate / 2 (within the two tolerances and that entry's rounding of
+ * the phase increment), at a cost per output that does not grow with the number of rows, and it reaches p / q up to 512.  F32 and
+ * S16 output as ofdmrx_util_synthesize writes them: a zero always +0, never -32768.  No state: a capture made window by window has
+ * the bytes of one made in one call.  Through ofdmrx_util_channelize_grid_ratio at the same ratio and slot, sample j of row c comes
+ * out at index j + 24 + start[c] q / p.  With reduced q = 1 and p a power of two it is ofdmrx_util_synthesize_grid: the same bytes.
+ * Arguments, memory spaces, asynchrony and the ring of parameter sets (a ratio-grid set is never taken for a grid set or a plain one
+ * at the same p / q) are ofdmrx_util_synthesize_grid's.  The handle's scratch of at most 32 MiB holds 2 q complex values per output;
+ * a call is cut into chunks of ofdmrx_util_synthesize_grid_ratio_chunk(p, q) outputs, counted from out_first rounded down to a
+ * multiple of p; a seam changes no byte.
+ * OFDMRX_E_ARG, before any device call and with the output untouched: everything ofdmrx_util_synthesize_grid refuses except its rule
+ * that interp is a power of two; a ratio ofdmrx_util_channelize_grid_ratio refuses; a slot outside -p <= k q < p or given twice;
+ * n_slots outside 1 .. n_all; NULL slots with n_slots != n_all; a start that p does not divide; n_out above 2^41 - 1024.
+ * ofdmrx_util_synthesize_grid_ratio_chunk: host only; the outputs per chunk (a multiple of p), OFDMRX_E_ARG for such a ratio. */
+int ofdmrx_util_synthesize_grid_ratio(ofdmrx_handle *h, const void *d_in, int in_format, size_t in_stride, size_t n_in, int p, int q,
+	const int32_t *slots, const long long *start, const float *gain, size_t n_slots, long long out_first, size_t n_out,
+	void *d_out, int out_format);
+long long ofdmrx_util_synthesize_grid_ratio_chunk(int p, int q);
 
 /* Wideband survey (added within revision 1.9, detected by symbol): which bands of a wideband capture are occupied - the centres to
  * open the front end or a wideband bank on.  DESIGN.md section 4.16 is the definition, held bin by bin to a float64 model.

@@ -242,7 +242,7 @@ struct ofdmrx_handle {
 		std::vector<SynthChannel> ch;   // (the host copy the upload reads: it lives as long as the slot)
 		std::vector<float> taps;
 		int p = 0, q = 0;               // the reduced ratio the set was made for (q = 1: the integer synthesizer's interp); 0: none
-		bool grid = false;              // a grid set: inc spells the slot, the M / 2 roots stand behind the taps (at tw_at floats)
+		int grid = 0;                   // 1: a grid set: inc spells the slot, the M / 2 roots stand behind the taps (at tw_at floats); 2: a ratio-grid set (4.23)
 		size_t tw_at = 0;
 		hipEvent_t done = nullptr;
 		~SynSlot() { if (done) (void)hipEventDestroy(done); }

@@ -456,6 +456,39 @@ void launch_synthesize_grid(hipStream_t s, const SynthesizeGridArgs &a);
 int synthesize_grid_tile_times(int interp);     // input times per workgroup of the transform kernel
 int synthesize_grid_filter_times(int interp);   // output times per workgroup of the filter kernel
 
+// ---- the grid synthesizer at a ratio (k_synthesize_grid_ratio.hip): p / q in lowest terms with p = 2^a 3^b 5^c (not
+// q = 1 with p a power of two: that is 4.20's kernels), M = 2 p.  Row c is slot k_c with
+//   ch[c].start = sigma_c q, the absolute input time of its first sample (the caller's start is sigma_c p)
+//   ch[c].inc   = channelize_grid_ratio_row(plan, (-k_c) mod M) | (k_c mod 2) << 16
+//   ch[c].gain  = p / q x the caller's gain, rounded once
+// taps: 16-byte aligned, [p][RSY_ROW] as launch_synthesize_ratio reads them; tw: the M roots e^{-2 pi i j / M}, rounded once from
+// double.  One launch makes the chunk's outputs m_first .. m_first + n_m - 1, which lie inside out_first .. out_first + n_out - 1.
+// scratch: device, n_times M float2 - V of the absolute input times j_first .. j_first + n_times - 1 as [time][r]; j_first =
+// (m_first q) div p - 24, n_times a multiple of synthesize_grid_ratio_tile_times(p, q) that holds ((m_first + n_m - 1) q) div p - at
+// q = 1, where the filter's work items take synthesize_grid_ratio_filter_round(1) = 8 output times each, the chunk's number of output
+// times rounded up to 8, plus 24.
+struct SynthesizeGridRatioArgs {
+	const void *in;
+	int in_fmt, out_fmt;           // OFDMRX_FMT_S16 or OFDMRX_FMT_F32
+	int p, q;
+	long long in_stride, n_in;     // sample frames
+	const SynthChannel *ch;        // device, [n_channels]
+	const float *taps;
+	const float2 *tw;
+	int n_channels;
+	long long out_first, n_out;
+	void *out;
+	float2 *scratch;
+	long long j_first, m_first, n_m;
+	int n_times;
+	int m, nt;                     // the launcher fills these three in from channelize_grid_ratio_plan(p, q)
+	unsigned radices;
+};
+void launch_synthesize_grid_ratio(hipStream_t s, const SynthesizeGridRatioArgs &a);
+int synthesize_grid_ratio_tile_times(int p, int q);   // input times per workgroup of the transform kernel
+int synthesize_grid_ratio_filter_outputs(int p, int q);   // outputs per workgroup of the filter kernel
+int synthesize_grid_ratio_filter_round(int q);        // output times per work item of the filter kernel (q > 1: 1)
+
 // ---- the wideband survey (k_survey.hip): a Welch power spectrum of one wideband capture, n_rows rows of nfft bins.
 // in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); the caller has checked that every position the
 // rows need is there.  Row r (row_first .. row_first + n_rows - 1) averages the segs_per_row segments from r segs_per_row on, in

@@ -7,6 +7,10 @@
 // `synthesize --grid OUT.wav INTERP SLOT:START:GAIN_DB:IN.wav [...]`: the same through the grid synthesizer (DESIGN.md section 4.20,
 // ofdmrx_util_synthesize_grid): INTERP a power of two 2 .. 512, every IN.wav in a slot of its own, SLOT = -INTERP .. INTERP - 1 with
 // its centre at SLOT x rate / 2, START a multiple of INTERP: what `decode_stream --grid INTERP SLOTS OUTROOT OUT.wav` reads.
+// `synthesize --grid-ratio OUT.wav P/Q SLOT:START:GAIN_DB:IN.wav [...]`: the same at a ratio (DESIGN.md section 4.23,
+// ofdmrx_util_synthesize_grid_ratio): in lowest terms Q <= 16, 2 Q <= P <= 512, P with no prime factor other than 2, 3 and 5; SLOT with
+// -P <= SLOT x Q < P and given once, START a multiple of the reduced P; the rate x P / Q must be an integer: what `decode_stream --grid
+// P/Q SLOTS OUTROOT OUT.wav` reads.  The spelling `--grid OUT.wav P/Q` keeps its refusal: folding the two is left to a later change.
 // Exit status 0, or 1 on argument, WAV or library errors.
 #include "survey_cli.h"
 #include <hip/hip_runtime.h>
@@ -22,12 +26,15 @@ int main(int argc, char **argv)
 {
 	const char *program = argv[0];
 	const bool grid = argc > 1 && !std::strcmp(argv[1], "--grid");
-	if (grid) {
+	const bool grid_ratio = argc > 1 && !std::strcmp(argv[1], "--grid-ratio");
+	if (grid || grid_ratio) {
 		++argv;
 		--argc;
 	}
 	if (argc < 4) {
-		std::fprintf(stderr, "usage: %s OUT.wav INTERP CENTRE_HZ:START:GAIN_DB:IN.wav [...]\n       %s --grid OUT.wav INTERP SLOT:START:GAIN_DB:IN.wav [...]\n", program, program);
+		std::fprintf(stderr, "usage: %s OUT.wav INTERP CENTRE_HZ:START:GAIN_DB:IN.wav [...]\n       %s --grid OUT.wav INTERP SLOT:START:GAIN_DB:IN.wav [...]\n"
+			"       %s --grid-ratio OUT.wav P/Q SLOT:START:GAIN_DB:IN.wav [...]\n"
+			"(--grid takes a power of two and refuses a ratio P/Q; a grid capture at a ratio is --grid-ratio)\n", program, program, program);
 		return 1;
 	}
 	const char *output_name = argv[1];
@@ -41,7 +48,24 @@ int main(int argc, char **argv)
 		std::fprintf(stderr, "A grid capture takes an interpolation that is a power of two 2 .. 512 and 1 .. 2 INTERP channels.\n");
 		return 1;
 	}
-	if (!grid && (!interp.valid() || C > 65535)) {
+	// the ratio grid: the reduced P, its range of slots
+	int32_t k_first = 0;
+	size_t n_all = 0;
+	int red_p = interp.p;
+	if (grid_ratio) {
+		if (!interp.ratio || interp.p <= 0 || interp.q <= 0 || ofdmrx_util_grid_ratio_slots(interp.p, interp.q, &k_first, &n_all) || C > n_all) {
+			std::fprintf(stderr, "A ratio-grid capture takes a ratio P/Q - in lowest terms Q <= 16, 2 Q <= P <= 512, P = 2^a 3^b 5^c - and at most one channel per slot.\n");
+			return 1;
+		}
+		int a = interp.p, b = interp.q;
+		while (b) {
+			const int t = a % b;
+			a = b;
+			b = t;
+		}
+		red_p = interp.p / a;
+	}
+	if (!grid && !grid_ratio && (!interp.valid() || C > 65535)) {
 		std::fprintf(stderr, "A wideband capture takes an interpolation of 2 .. 32 (a ratio P/Q: Q <= 16) and 1 .. 65535 channels.\n");
 		return 1;
 	}
@@ -73,6 +97,21 @@ int main(int argc, char **argv)
 				std::find(slot.begin(), slot.begin() + (long)c, slot[c]) == slot.begin() + (long)c;
 			if (!fits) {
 				std::fprintf(stderr, "A grid channel is SLOT:START:GAIN_DB:IN.wav, SLOT = -INTERP .. INTERP - 1 and given once, START a multiple of INTERP.\n");
+				return 1;
+			}
+		}
+		if (grid_ratio && ok) {
+			slot[c] = (int32_t)std::lrint(centre[c]);
+			if (centre[c] != (double)slot[c] || slot[c] < k_first || slot[c] > k_first + (int32_t)n_all - 1) {
+				std::fprintf(stderr, "A ratio-grid channel's slot is a whole number %d .. %d (-P <= SLOT x Q < P): %s\n", k_first, k_first + (int)n_all - 1, argv[c + 3]);
+				return 1;
+			}
+			if (std::find(slot.begin(), slot.begin() + (long)c, slot[c]) != slot.begin() + (long)c) {
+				std::fprintf(stderr, "Slot %d is given twice.\n", slot[c]);
+				return 1;
+			}
+			if (start[c] % red_p) {
+				std::fprintf(stderr, "START %lld is not a multiple of P = %d.\n", start[c], red_p);
 				return 1;
 			}
 		}
@@ -145,7 +184,9 @@ int main(int argc, char **argv)
 	e = e == hipSuccess ? hipMalloc(&d_out, (size_t)bytes) : e;
 	e = e == hipSuccess ? hipMemcpy(d_in, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice) : e;
 	if (e == hipSuccess) {
-		r = grid ? ofdmrx_util_synthesize_grid(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, slot.data(), start.data(), gain.data(), C, 0,
+		r = grid_ratio ? ofdmrx_util_synthesize_grid_ratio(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, interp.q, slot.data(), start.data(),
+			gain.data(), C, 0, (size_t)n_out, d_out, OFDMRX_FMT_S16)
+			: grid ? ofdmrx_util_synthesize_grid(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, slot.data(), start.data(), gain.data(), C, 0,
 			(size_t)n_out, d_out, OFDMRX_FMT_S16)
 			: interp.ratio ? ofdmrx_util_synthesize_ratio(h, d_in, OFDMRX_FMT_F32, longest, longest, interp.p, interp.q, centre.data(), start.data(),
 			gain.data(), C, 0, (size_t)n_out, d_out, OFDMRX_FMT_S16)

@@ -43,6 +43,7 @@ EXPORTS = [
     "ofdmrx_util_survey_grid", "ofdmrx_util_find_slots",
     "ofdmrx_util_channelize_grid_ratio_taps", "ofdmrx_util_grid_ratio_slots", "ofdmrx_util_channelize_grid_ratio",
     "ofdmrx_bank_begin_wideband_grid_ratio",
+    "ofdmrx_util_synthesize_grid_ratio", "ofdmrx_util_synthesize_grid_ratio_chunk",
 ]
 
 
@@ -206,8 +207,16 @@ def synthesize_support(n_in, interp):
 
 def synthesize_grid_chunk(interp):
     """the outputs per host chunk of the grid synthesizer at interpolation interp (a power of two 2 .. 512), counted from out_first
-    rounded down to a multiple of interp: DESIGN.md section 4.20.  A seam changes no byte; the number is there for the curious"""
+    rounded down to a multiple of interp: DESIGN.md section 4.20.  A seam changes no byte; the number is there for the curious.
+    interp may be a ratio - a pair (p, q) or a fractions.Fraction: the outputs per chunk of the grid synthesizer at that ratio, counted
+    from out_first rounded down to a multiple of the reduced p (section 4.23)"""
     L = load_library()
+    interp, q = _ratio(interp)
+    if q is not None:
+        n = L.ofdmrx_util_synthesize_grid_ratio_chunk(interp, q) if interp > 0 and q > 0 else -1
+        if n <= 0:
+            raise OfdmRxError("synthesize_grid_chunk: in lowest terms q must be 1 .. 16, p 2 q .. 512 with no prime factor other than 2, 3 and 5")
+        return int(n)
     n = L.ofdmrx_util_synthesize_grid_chunk(int(interp))
     if n <= 0:
         raise OfdmRxError("synthesize_grid_chunk: interp must be a power of two 2 .. 512")
@@ -414,6 +423,10 @@ def load_library():
                                               C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
     L.ofdmrx_util_synthesize_grid_chunk.argtypes = [C.c_int]
     L.ofdmrx_util_synthesize_grid_chunk.restype = C.c_longlong
+    L.ofdmrx_util_synthesize_grid_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_int]
+    L.ofdmrx_util_synthesize_grid_ratio_chunk.argtypes = [C.c_int, C.c_int]
+    L.ofdmrx_util_synthesize_grid_ratio_chunk.restype = C.c_longlong
     L.ofdmrx_util_survey_window.argtypes = [C.c_int, C.c_void_p]
     L.ofdmrx_util_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_longlong, C.c_size_t,
                                      C.c_void_p]
@@ -837,12 +850,21 @@ class Receiver:
     def synthesize_grid(self, d_in, in_fmt, n_in, interp, slots, starts, gains, out_first, n_out, d_out, out_fmt, in_stride=None):
         """the grid synthesizer on device buffers (ints): as synthesize, for an interp that is a power of two
         2 .. 512 and rows on the raster rate / 2: row c belongs to slot slots[c] (-interp .. interp - 1, pairwise distinct; None: every
-        slot, ascending), centred at grid_centres(interp, rate, slots)[c]; starts are multiples of interp"""
-        k = _grid_slots(interp, slots)
+        slot, ascending), centred at grid_centres(interp, rate, slots)[c]; starts are multiples of interp.  interp may be a ratio - a
+        pair (p, q) or a fractions.Fraction (section 4.23): the slots are the k with -p <= k q < p, starts multiples of the reduced p"""
+        interp, q = _ratio(interp)
+        if q is not None:
+            p, q, k = _grid_ratio_slots(interp, q, slots)
+        else:
+            k = _grid_slots(interp, slots)
         s = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
         g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
         if not (k.size == s.size == g.size):
             raise OfdmRxError("synthesize_grid: slots, starts and gains must have one length")
+        if q is not None:
+            self._check(self._lib.ofdmrx_util_synthesize_grid_ratio(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, p, q,
+                                                                    _ptr(k), _ptr(s), _ptr(g), k.size, out_first, n_out, d_out, out_fmt))
+            return
         self._check(self._lib.ofdmrx_util_synthesize_grid(self._h, d_in, in_fmt, n_in if in_stride is None else in_stride, n_in, int(interp),
                                                           _ptr(k), _ptr(s), _ptr(g), k.size, out_first, n_out, d_out, out_fmt))
 
