@@ -68,7 +68,8 @@ extern "C" {
  *      channel grid at any ratio P / Q (a mixed-radix filter bank) - ofdmrx_util_channelize_grid_ratio_taps,
  *      ofdmrx_util_grid_ratio_slots, ofdmrx_util_channelize_grid_ratio, ofdmrx_bank_begin_wideband_grid_ratio; the wideband
  *      synthesizer on a channel grid at any ratio P / Q (a mixed-radix synthesis bank) - ofdmrx_util_synthesize_grid_ratio,
- *      ofdmrx_util_synthesize_grid_ratio_chunk */
+ *      ofdmrx_util_synthesize_grid_ratio_chunk; the grid survey at any ratio P / Q (per-slot power from the mixed-radix bank) -
+ *      ofdmrx_util_survey_grid_ratio, ofdmrx_util_find_slots_ratio */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -877,6 +878,47 @@ typedef struct ofdmrx_slot {
 int ofdmrx_util_survey_grid(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int decim,
 	int times_per_row, long long row_first, size_t n_rows, float *d_out);
 int ofdmrx_util_find_slots(const float *row, int decim, double rate, double thr_db, double sep_db, double abs_floor,
+	size_t max_slots, ofdmrx_slot *slots, size_t *n_slots, double *floor_out);
+
+/* Grid survey at any ratio P / Q (added within revision 1.9, detected by symbol): the survey above for the raster of the grid front
+ * end at a ratio - a capture at 48, 50, 250 or 300 kHz searched for the slots to open.  DESIGN.md section 4.24 is the definition,
+ * held slot by slot to a float64 model.  p / q is reduced inside; in lowest terms 1 <= q <= 16, 2 q <= p <= 512, p with no prime
+ * factor other than 2, 3 and 5.  With M = 2 p, the taps, the output times i_n = (n p) div q, q_n = (n p) mod q, the slots k_first ..
+ * k_first + n_all - 1 (ofdmrx_util_grid_ratio_slots) and y_k[n] of the grid front end at a ratio above at ABSOLUTE output times n (the
+ * capture zero at negative positions), and S = times_per_row, a multiple of 8 in 8 .. 65536:
+ *   row r   P[r][k - k_first] = (1 / S) sum_{n = r S .. r S + S - 1} |y_k[n]|^2: n_all floats in ASCENDING slot order, index i is
+ *           slot k_first + i at (k_first + i) rate / 2.  No further normalisation.
+ * Row r needs the wideband positions max(0, (r S p) div q - 24 p div q) .. (((r + 1) S - 1) p) div q.  The summation order is the
+ * grid survey's; there is no state, and a capture surveyed row by row, each call given only the positions its rows need, gives the
+ * same bytes as one call.  At reduced q = 1 with p a power of two the call IS ofdmrx_util_survey_grid at decim = p: its kernel, its
+ * bytes, rows of M = n_all values.  The table on the device is the ratio-grid table with every slot, under the front end's key: a
+ * survey between two front-end calls on other slots leaves their bytes unchanged, and the reverse.
+ * DEVICE buffers, asynchronous on the handle's stream; row r (row_first .. row_first + n_rows - 1) lands at d_out + (r - row_first)
+ * n_all floats.
+ * OFDMRX_E_ARG, before any device call and with the output untouched: NULL pointers or zero counts; a bad format; a ratio outside
+ * the set; S no multiple of 8 or outside 8 .. 65536; a negative in_first or row_first; a position the rows need that is not in the
+ * buffer - there is no zero padding other than below position 0; d_in off the sample-frame boundary, d_out off 4 bytes; d_out
+ * overlapping d_in; positions or counts above 2^50; n_rows (S / 8) n_all above 2^28; a handle with an open feed or bank.
+ * ofdmrx_util_find_slots_ratio: host only, float64; ofdmrx_util_find_slots on the n_all values of ONE row at the ratio p / q:
+ *   floor     abs_floor if that is > 0, else the median of the n_all values (an odd count: the middle value; an even count: the mean
+ *             of the two middle values)
+ *   occupied, shadowed: as above, but the neighbours are cyclic only where the slots tile the circle, n_all q = M (q = 1 or 2);
+ *             otherwise slot k_first and the last slot have one neighbour each - beyond them lies no whole slot.  With r = p mod q the
+ *             ends leave a gap of 2 r - q bins of M where r > q / 2 and OVERLAP by q - 2 r bins where r < q / 2: at 25/4 slot 6 and
+ *             slot -6 lie half a slot apart across the band edge and a signal in one reads in the other at nearly full strength.
+ *   the ends seen twice: where the centres of the last and the first slot lie half a slot apart or less (0 < 4 r <= q: 25/4, 9/4)
+ *             two signals cannot stand there side by side.  If both ends are occupied and unshadowed and lie within sep_db of each
+ *             other they are one signal: the louder is reported (a tie: k_first).  Further apart than sep_db both are reported -
+ *             neither shadows the other.  Ends that overlap by less (q < 4 r < 2 q, 10/3) are both reported.
+ * slot = k_first + i, centre_hz = slot rate / 2.  At q = 1 with p a power of two it returns what ofdmrx_util_find_slots returns.
+ * OFDMRX_E_ARG: NULL row, slots or n_slots; a ratio outside the set; a rate that is not finite or <= 0; thr_db, sep_db or abs_floor
+ * that is not finite or negative.
+ * Not built: pruning the transform to the 2 p / q slot bins; p beyond 512 or other primes; and, the rule's blind spot as above, a
+ * signal more than sep_db below a neighbour is not found; at a ratio whose ends overlap by less than half a slot one signal there
+ * may be reported in both ends. */
+int ofdmrx_util_survey_grid_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	int times_per_row, long long row_first, size_t n_rows, float *d_out);
+int ofdmrx_util_find_slots_ratio(const float *row, int p, int q, double rate, double thr_db, double sep_db, double abs_floor,
 	size_t max_slots, ofdmrx_slot *slots, size_t *n_slots, double *floor_out);
 
 /* ---- N2: the transmitter on the device (replaces Encoder<value,cmplx,rate>(pcm, inp, count=1, freq_off,

@@ -1,6 +1,7 @@
 // api_survey.cpp -- the wideband survey behind include/ofdmrx.h: the window, ofdmrx_util_survey, and the
 // band finder ofdmrx_util_find_bands (host only, float64); and the grid survey (section 4.21): ofdmrx_util_survey_grid and the slot
-// finder ofdmrx_util_find_slots.  Everything the kernels rely on is checked here, before any device call.
+// finder ofdmrx_util_find_slots; and the grid survey at a ratio (section 4.24): ofdmrx_util_survey_grid_ratio and
+// ofdmrx_util_find_slots_ratio.  Everything the kernels rely on is checked here, before any device call.
 #include "api_internal.h"
 
 namespace rx {
@@ -263,6 +264,149 @@ extern "C" int ofdmrx_util_find_slots(const float *row, int decim, double rate, 
 			s.centre_hz = (double)(i - M / 2) * rate / 2.0;
 			s.power = p;
 			s.level_db = (float)(10.0 * std::log10(p / floor));
+		}
+		++count;
+	}
+	*n_slots = count;
+	if (floor_out)
+		*floor_out = floor;
+	return 0;
+}
+
+// ---- the grid survey at a ratio: the same on the slots of the ratio grid front end's bank (4.22)
+
+extern "C" int ofdmrx_util_survey_grid_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	int times_per_row, long long row_first, size_t n_rows, float *d_out)
+{
+	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
+	if (channelize_grid_ratio(p, q))
+		return OFDMRX_E_ARG;
+	if (q == 1 && !channelize_grid_decim(p))                      // 4.21 itself: its kernel, its bytes
+		return ofdmrx_util_survey_grid(h, d_in, sample_format, in_first, n_in, p, times_per_row, row_first, n_rows, d_out);
+	if (!h || !d_in || !d_out || !n_in || !n_rows)
+		return OFDMRX_E_ARG;
+	if (times_per_row < SURVEY_GRID_G || times_per_row > 65536 || times_per_row % SURVEY_GRID_G)
+		return OFDMRX_E_ARG;
+	if (sample_format < OFDMRX_FMT_S16 || sample_format > OFDMRX_FMT_F32 || in_first < 0 || row_first < 0)
+		return OFDMRX_E_ARG;
+	if (in_first > FAR || row_first > FAR || n_in > (size_t)FAR || n_rows > (size_t)FAR)
+		return OFDMRX_E_ARG;
+	const size_t unit = 2 * sample_bytes(sample_format);
+	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float))
+		return OFDMRX_E_ARG;
+	int32_t k_first;
+	size_t n_all;
+	channelize_grid_ratio_range(p, q, k_first, n_all);
+	{
+		// a position the rows need is not in the buffer: there is no zero padding other than below position 0
+		const __int128 S = times_per_row, P = p, Q = q;
+		__int128 lo = (__int128)row_first * S * P / Q - 24 * P / Q;
+		lo = lo < 0 ? 0 : lo;
+		const __int128 hi = (((__int128)row_first + (__int128)n_rows) * S - 1) * P / Q;
+		if (lo < (__int128)in_first || hi > (__int128)in_first + (__int128)n_in - 1 || hi >= (__int128)FAR)
+			return OFDMRX_E_ARG;
+	}
+	const int n_groups = times_per_row / SURVEY_GRID_G;
+	if ((__int128)n_rows * n_groups * (__int128)n_all > (__int128)survey_max_partial_floats())   // what the handle's partial buffer may hold
+		return OFDMRX_E_ARG;
+	{
+		const char *a = (const char *)d_in, *b = (const char *)d_out;
+		if (a < b + n_rows * n_all * sizeof(float) && b < a + n_in * unit)
+			return OFDMRX_E_ARG;
+	}
+	if (h->busy_live())
+		return OFDMRX_E_ARG;
+	HIP_OK(hipSetDevice(h->cfg.device));
+	// the ratio-grid table of 4.22 with every slot, under the front end's key (which includes the slot list): a front-end call on other
+	// slots uploads its own again, and this call after it
+	std::vector<int32_t> all(n_all);
+	for (size_t j = 0; j < n_all; ++j)
+		all[j] = k_first + (int32_t)j;
+	int r = channelize_grid_ratio_setup(h, p, q, all);
+	r = r ? r : h->survey_part.ensure(n_rows * (size_t)n_groups * n_all * sizeof(float));
+	if (r)
+		return r;
+	ChannelizeArgs t{};
+	channelize_tables(h, t);
+	SurveyGridRatioArgs a{};
+	a.in = d_in;
+	a.fmt = sample_format;
+	a.p = p;
+	a.q = q;
+	a.in_first = in_first;
+	a.n_in = (long long)n_in;
+	a.taps = t.taps;
+	a.tw = t.tw;
+	a.inc = t.inc;
+	a.n_all = (int)n_all;
+	a.t_first = row_first * (long long)times_per_row;
+	a.n_times = (long long)n_rows * (long long)times_per_row;
+	a.n_groups = n_groups;
+	a.n_rows = (long long)n_rows;
+	a.part = h->survey_part.as<float>();
+	a.out = d_out;
+	HIP_OK(launch_survey_grid_ratio(h->stream, a, (float)(1.0 / (double)times_per_row)));
+	HIP_OK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int ofdmrx_util_find_slots_ratio(const float *row, int p, int q, double rate, double thr_db, double sep_db, double abs_floor,
+	size_t max_slots, ofdmrx_slot *slots, size_t *n_slots, double *floor_out)
+{
+	if (!row || !slots || !n_slots || channelize_grid_ratio(p, q))
+		return OFDMRX_E_ARG;
+	if (!std::isfinite(rate) || rate <= 0.0 || !std::isfinite(thr_db) || thr_db < 0.0 || !std::isfinite(sep_db) || sep_db < 0.0)
+		return OFDMRX_E_ARG;
+	if (!std::isfinite(abs_floor) || abs_floor < 0.0)
+		return OFDMRX_E_ARG;
+	int32_t k_first;
+	size_t n_all;
+	channelize_grid_ratio_range(p, q, k_first, n_all);
+	const int N = (int)n_all;
+	const bool cyclic = N * q == 2 * p;                           // the slots tile the circle: q = 1 or 2
+	double floor = abs_floor;
+	if (!(abs_floor > 0.0)) {
+		std::vector<double> v(row, row + N);
+		std::sort(v.begin(), v.end());
+		floor = N & 1 ? v[(size_t)N / 2] : 0.5 * (v[(size_t)N / 2 - 1] + v[(size_t)N / 2]);
+	}
+	const double level = floor * std::pow(10.0, thr_db / 10.0), sep = std::pow(10.0, sep_db / 10.0);
+	std::vector<char> keep((size_t)N, 0);
+	for (int i = 0; i < N; ++i) {
+		const double pw = (double)row[i];
+		if (!(pw > level && pw > 0.0))
+			continue;
+		// beyond the ends of an open range lies no whole slot: a gap, or an overlap of less than a slot
+		const double below = i > 0 ? (double)row[i - 1] : cyclic ? (double)row[N - 1] : 0.0;
+		const double above = i < N - 1 ? (double)row[i + 1] : cyclic ? (double)row[0] : 0.0;
+		if (below > pw * sep || above > pw * sep)                 // shadowed: a neighbour's edge through the filter's transition band
+			continue;
+		keep[(size_t)i] = 1;
+	}
+	// The ends seen twice.  With r = p mod q the centres of the last and the first slot lie 2 r bins apart across the band edge, a slot
+	// being q bins.  Where that is half a slot or less (0 < 4 r <= q: 25/4, 9/4) each centre lies inside the other slot's own band, so a
+	// signal that fits a slot reads in both at nearly the same level and two signals cannot stand there side by side: if both ends
+	// passed and lie within sep_db of each other they are one signal, and the louder is reported (a tie: k_first).  Further apart than
+	// sep_db they stay two, as the end rule says: neither shadows the other.
+	const int r = p % q;
+	if (!cyclic && r > 0 && 4 * r <= q && keep[0] && keep[(size_t)N - 1]) {
+		const double a = (double)row[0], b = (double)row[N - 1];
+		if (a >= b && !(a > b * sep))
+			keep[(size_t)N - 1] = 0;
+		else if (b > a && !(b > a * sep))
+			keep[0] = 0;
+	}
+	size_t count = 0;
+	for (int i = 0; i < N; ++i) {
+		if (!keep[(size_t)i])
+			continue;
+		const double pw = (double)row[i];
+		if (count < max_slots) {
+			ofdmrx_slot &s = slots[count];
+			s.slot = k_first + i;
+			s.centre_hz = (double)(k_first + i) * rate / 2.0;
+			s.power = pw;
+			s.level_db = (float)(10.0 * std::log10(pw / floor));
 		}
 		++count;
 	}

@@ -25,10 +25,13 @@
 // stderr first; the files and lines are those of --wideband.
 // `decode_stream --grid P/Q K1,K2,...|all OUTROOT WIDE.wav`: the grid front end at a ratio (DESIGN.md section 4.22,
 // ofdmrx_bank_begin_wideband_grid_ratio): the spelling with '/' - 6/1 is a 48 kHz capture at an 8 kHz handle; the slots are the K with
-// -P <= K Q < P.  A bare integer keeps the power-of-two rule.  `--grid P/Q auto` is refused: the grid survey at a ratio is not built.
+// -P <= K Q < P.  A bare integer keeps the power-of-two rule.  `--grid P/Q auto` is refused: under --grid the grid survey at a ratio is
+// not built; it is `--grid-ratio P/Q auto`, below.
 // `decode_stream --grid DECIM auto[:FLOOR_DB] OUTROOT WIDE.wav`: the capture is surveyed first (what `survey
 // --grid WIDE.wav DECIM [FLOOR_DB]` prints), the slots found are printed on stderr, and then exactly the form above runs with that
 // list.  The file is read twice, so `auto` does not take standard input; no slot found is an error.
+// `decode_stream --grid-ratio P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT WIDE.wav`: a list or `all` is `--grid P/Q` exactly; `auto`
+// surveys the capture first (what `survey --grid-ratio WIDE.wav P/Q [FLOOR_DB]` prints) and then runs that form.
 #include "survey_cli.h"
 #include <algorithm>
 #include <cstdlib>
@@ -336,8 +339,8 @@ static std::string survey_centres(const Decimation &decim, const char *input_nam
 }
 
 // the occupied slots of a grid capture, as the list run_wideband takes with grid = true ("" with a message: none, or an error).
-// how: `auto` or `auto:FLOOR_DB`
-static std::string survey_slots(const char *decim_arg, const char *how, const char *input_name)
+// how: `auto` or `auto:FLOOR_DB`; at_ratio: `--grid-ratio P/Q auto`
+static std::string survey_slots(const char *decim_arg, const char *how, const char *input_name, bool at_ratio = false)
 {
 	if (!std::strcmp(input_name, "-") || !std::strcmp(input_name, "/dev/stdin")) {
 		std::fprintf(stderr, "`auto` reads the capture twice: give a file, not standard input.\n");
@@ -345,11 +348,18 @@ static std::string survey_slots(const char *decim_arg, const char *how, const ch
 	}
 	const int decim = std::atoi(decim_arg);
 	double abs_floor = 0.0;
-	if (std::strchr(decim_arg, '/')) {
-		std::fprintf(stderr, "The grid survey at a ratio P/Q is not built: `--grid P/Q auto` is refused; name the slots or give `all`.\n");
+	const Decimation ratio(decim_arg);
+	if (!at_ratio && std::strchr(decim_arg, '/')) {
+		std::fprintf(stderr, "The grid survey at a ratio P/Q is not built under --grid: `--grid P/Q auto` is refused; use `--grid-ratio P/Q auto[:FLOOR_DB]`, name the slots or give `all`.\n");
 		return "";
 	}
-	if (!grid_decim_valid(decim)) {
+	int32_t k_first = 0;
+	size_t n_all = 0;
+	if (at_ratio && (!ratio.ratio || ratio.p <= 0 || ratio.q <= 0 || ofdmrx_util_grid_ratio_slots(ratio.p, ratio.q, &k_first, &n_all))) {
+		std::fprintf(stderr, "A grid bank at a ratio takes P/Q with, in lowest terms, Q 1 .. 16 and P 2 Q .. 512 with no prime factor other than 2, 3 and 5.\n");
+		return "";
+	}
+	if (!at_ratio && !grid_decim_valid(decim)) {
 		std::fprintf(stderr, "A grid bank takes a decimation that is a power of two 2 .. 512.\n");
 		return "";
 	}
@@ -366,17 +376,18 @@ static std::string survey_slots(const char *decim_arg, const char *how, const ch
 		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
 		return "";
 	}
-	if (w.rate % decim || !supported(2, w.rate / decim)) {
-		if (w.rate % decim)
+	const int rate = at_ratio ? ratio.rate_of(w.rate) : w.rate % decim ? 0 : w.rate / decim;
+	if (!rate || !supported(2, rate)) {
+		if (!rate)
 			std::fprintf(stderr, "Unsupported sample rate.\n");
 		return "";
 	}
-	ofdmrx_handle *h = create(w.rate / decim);
+	ofdmrx_handle *h = create(rate);
 	if (!h)
 		return "";
 	std::vector<ofdmrx_slot> slots;
 	double floor = 0.0;
-	const bool ok = survey_grid_capture(h, w, decim, abs_floor, slots, floor);
+	const bool ok = at_ratio ? survey_grid_ratio_capture(h, w, ratio.p, ratio.q, abs_floor, slots, floor) : survey_grid_capture(h, w, decim, abs_floor, slots, floor);
 	ofdmrx_destroy(h);
 	if (!ok)
 		return "";
@@ -527,14 +538,25 @@ int main(int argc, char **argv)
 	}
 	if (argc == 6 && !std::strcmp(argv[1], "--grid"))
 		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5], true);
+	if (argc == 6 && !std::strcmp(argv[1], "--grid-ratio")) {
+		if (!Decimation(argv[2]).ratio) {
+			std::fprintf(stderr, "--grid-ratio takes a ratio P/Q (the spelling with '/'); a power of two is `--grid DECIM`.\n");
+			return 1;
+		}
+		if (!std::strncmp(argv[3], "auto", 4) && (!argv[3][4] || argv[3][4] == ':')) {
+			const std::string found = survey_slots(argv[2], argv[3], argv[5], true);
+			return found.empty() ? 1 : run_wideband(Decimation(argv[2]), found.c_str(), argv[4], argv[5], true);
+		}
+		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5], true);
+	}
 	if (argc >= 5 && !std::strcmp(argv[1], "--live") && !std::strcmp(argv[2], "--batch"))
 		return run_live_batch(argv[3], argc - 4, argv + 4);
 	if (argc >= 4 && !std::strcmp(argv[1], "--batch"))
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM|P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
-			argv[0], argv[0], argv[0], argv[0]);
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM|P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n       %s --grid-ratio P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
+			argv[0], argv[0], argv[0], argv[0], argv[0]);
 		return 1;
 	}
 	const std::string outdir = argv[live ? 2 : 1];

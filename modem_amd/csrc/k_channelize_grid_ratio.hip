@@ -20,60 +20,21 @@
 //      NT neighbouring outputs of one slot row per NT lanes.
 // Contract on order: u_n[r] is one FMA chain per component, a ascending; a position outside [in_first, in_first + n_in) is never
 // loaded and enters as +0.  No state: a capture cut into blocks, each with the T - 1 samples before it, gives the bytes of one call.
+// Steps 1 and 2 stand in grid_ratio_bank.h, which the grid survey at a ratio (k_survey_grid_ratio.hip, section 4.24) shares.
 #include "dev_common.h"
 #include "grid_bank.h"
+#include "grid_ratio_bank.h"
 #include "kernels.h"
 
 namespace rx {
 
-constexpr int CGR_THREADS = 256;
-constexpr int CGR_HIST = 13;           // taps per branch at most: T <= 12 M + 1
 constexpr int CGR_LDS = 61440;         // bytes of a tile at most
-
-// grid_bank.h's multiply on a cf
-__device__ __forceinline__ cf cgr_mul(cf a, float2 w)
-{
-	const float2 v = grid_mul(make_float2(a.re, a.im), w);
-	return mk(v.x, v.y);
-}
-
-// one stage of radix R on blocks of N points, every time of the tile
-template <int R> __device__ __forceinline__ void cgr_stage(cf *u, const float2 *tw, int tid, int M, int N, int NT)
-{
-	const int NTS = NT + 1, L = N / R, step = M / N, nb = M / R;
-	for (int it = tid; it < nb * NT; it += CGR_THREADS) {
-		int b, t;
-		if (NT >= 32) {                                               // lanes along t where a tile has that many times
-			b = it / NT;
-			t = it - b * NT;
-		} else {
-			t = it / nb;
-			b = it - t * nb;
-		}
-		const int blk = b / L, j = b - blk * L;
-		cf *x = u + (blk * N + j) * NTS + t;
-		cf v[R];
-		#pragma unroll
-		for (int i = 0; i < R; ++i)
-			v[i] = x[i * L * NTS];
-		Bfly<R>::run(v);
-		if (L > 1) {
-			#pragma unroll
-			for (int i = 1; i < R; ++i)
-				v[i] = cgr_mul(v[i], tw[j * i * step]);
-		}
-		#pragma unroll
-		for (int i = 0; i < R; ++i)
-			x[i * L * NTS] = v[i];
-	}
-	__syncthreads();
-}
 
 template <int FMT, int CH>
 __global__ __launch_bounds__(CGR_THREADS) void k_channelize_grid_ratio(ChannelizeArgs a, GridRatioPlan pl)
 {
 	extern __shared__ float2 cgr_lds[];
-	const int M = pl.m, NT = pl.nt, NTS = NT + 1, T = pl.n_taps, Q = a.q, Q2 = 2 * a.q;
+	const int M = pl.m, NT = pl.nt, NTS = NT + 1, T = pl.n_taps, Q = a.q;
 	cf *u = (cf *)cgr_lds;                                        // [M][NTS]
 	int *imod = (int *)(cgr_lds + M * NTS);                       // [NT]: i_n mod M
 	const int tid = threadIdx.x;
@@ -84,74 +45,10 @@ __global__ __launch_bounds__(CGR_THREADS) void k_channelize_grid_ratio(Channeliz
 	if (tid < NT)
 		imod[tid] = (int)(((n0 + tid) * a.p / Q) % M);
 
-	// ---- 1. the branch sums.  Work item (r, e, g): branch r, the run of times t = tf + 2 Q s < NT, tf = e + 2 Q CH g (ns <= CH of
-	// them).  Time s stands at i_tf + M s with the phase of tf, so sample a of time s is x[i_tf - r - M (a - s)]: the run loads the
-	// samples j = a - s = -(ns - 1) .. na - 1 once each, newest first; sample j meets time s at tap a = j + s, and for a given s the taps
-	// still come in ascending a.  (The plan picks CH so that a small M still gives every thread a run.)
-	{
-		const int E = Q2 < NT ? Q2 : NT;
-		for (int w = tid; w < M * E * pl.groups; w += CGR_THREADS) {
-			const int eg = w / M, r = w - eg * M, g = eg / E, e = eg - g * E;
-			const int tf = e + Q2 * CH * g;                               // the run's first time
-			if (tf >= NT)
-				continue;
-			const long long un = (n0 + tf) * a.p, i0 = un / Q;
-			const int ph = (int)(un - i0 * Q);
-			const int na = r < T ? (T - 1 - r) / M + 1 : 0;           // the taps r + M a <= T - 1 of the branch
-			const int left = (NT - tf + Q2 - 1) / Q2, ns = left < CH ? left : CH;
-			float h[CGR_HIST];
-			#pragma unroll
-			for (int i = 0; i < CGR_HIST; ++i)
-				h[i] = i < na ? a.taps[(size_t)(r + M * i) * Q + ph] : 0.f;
-			float re[CH], im[CH];
-			#pragma unroll
-			for (int s = 0; s < CH; ++s)
-				re[s] = im[s] = 0.f;
-			const long long m0 = i0 - r - a.in_first;                 // sample j = 0 of the run, counted from the buffer's first
-			#pragma unroll
-			for (int j = -(CH - 1); j < CGR_HIST; ++j) {
-				if (j >= na || j + ns <= 0)
-					continue;
-				const long long m = m0 - (long long)M * j;
-				float2 x = make_float2(0.f, 0.f);
-				if (m >= 0 && m < a.n_in)
-					x = iq_sample<FMT>(a.in, (size_t)m);
-				#pragma unroll
-				for (int s = 0; s < CH; ++s) {
-					const int i = j + s;                                  // the tap
-					if (i < 0 || i >= CGR_HIST)
-						continue;
-					if (i < na && s < ns) {
-						re[s] = __builtin_fmaf(h[i], x.x, re[s]);
-						im[s] = __builtin_fmaf(h[i], x.y, im[s]);
-					}
-				}
-			}
-			#pragma unroll
-			for (int s = 0; s < CH; ++s)
-				if (s < ns)
-					u[r * NTS + tf + Q2 * s] = mk(re[s], im[s]);
-		}
-	}
+	// ---- 1. the branch sums, 2. the transform: grid_ratio_bank.h's
+	cgr_branch_sums<FMT, CH>(u, a, M, NT, T, pl.groups, n0, tid);
 	__syncthreads();
-
-	// ---- 2. the transform: the plan's radices, four bits each, first stage lowest
-	{
-		int N = M;
-		#pragma unroll
-		for (int s = 0; s < 8; ++s) {
-			const int R = (int)((pl.radices >> (4 * s)) & 15u);
-			if (R == 0)
-				break;
-			switch (R) {
-			case 5: cgr_stage<5>(u, a.tw, tid, M, N, NT); break;
-			case 3: cgr_stage<3>(u, a.tw, tid, M, N, NT); break;
-			case 4: cgr_stage<4>(u, a.tw, tid, M, N, NT); break;
-			default: cgr_stage<2>(u, a.tw, tid, M, N, NT); break;
-			}
-			N /= R;
-		}
-	}
+	cgr_transform(u, a.tw, pl.radices, tid, M, NT);
 
 	// ---- 3. the requested slots: inc[c] = the row of bin (-k Q) mod M | (k Q mod M) << 16
 	for (int it = tid; it < a.n_channels * NT; it += CGR_THREADS) {
@@ -163,6 +60,20 @@ __global__ __launch_bounds__(CGR_THREADS) void k_channelize_grid_ratio(Channeliz
 		float2 *dst = a.dst ? (float2 *)(uintptr_t)a.dst[c] : (float2 *)a.out + (size_t)c * (size_t)a.out_stride;
 		dst[j0 + t] = make_float2(v.re, v.im);
 	}
+}
+
+// the runs of the branch sums for the plan's tile: as long as a residue has times and a branch has taps (a longer one saves no load; 16
+// at most), halved until the tile has a run for every thread
+void channelize_grid_ratio_runs(GridRatioPlan &pl, int q)
+{
+	const int nt = pl.nt;
+	const int per = (nt + 2 * q - 1) / (2 * q), e = 2 * q < nt ? 2 * q : nt, na = (pl.n_taps + pl.m - 1) / pl.m;
+	pl.ch = 1;
+	while (pl.ch < per && pl.ch < 16 && pl.ch < na)
+		pl.ch *= 2;
+	while (pl.ch > 1 && pl.m * e * ((per + pl.ch - 1) / pl.ch) < CGR_THREADS)
+		pl.ch /= 2;
+	pl.groups = (per + pl.ch - 1) / pl.ch;
 }
 
 // the plan of M = 2 P = 2^a 3^b 5^c: c stages of radix 5, b of radix 3, a div 2 of radix 4, a mod 2 of radix 2.  A tile holds 4096
@@ -187,15 +98,7 @@ GridRatioPlan channelize_grid_ratio_plan(int p, int q)
 	nt = nt < fit ? nt : fit;
 	nt &= ~1;                                                     // rows of NT + 1: an odd stride in LDS
 	pl.nt = nt;
-	// the run: as long as a residue has times and a branch has taps (a longer one saves no load; 16 at most), halved until the tile
-	// has a run for every thread
-	const int per = (nt + 2 * q - 1) / (2 * q), e = 2 * q < nt ? 2 * q : nt, na = (pl.n_taps + pl.m - 1) / pl.m;
-	pl.ch = 1;
-	while (pl.ch < per && pl.ch < 16 && pl.ch < na)
-		pl.ch *= 2;
-	while (pl.ch > 1 && pl.m * e * ((per + pl.ch - 1) / pl.ch) < CGR_THREADS)
-		pl.ch /= 2;
-	pl.groups = (per + pl.ch - 1) / pl.ch;
+	channelize_grid_ratio_runs(pl, q);
 	pl.lds = (size_t)pl.m * (size_t)(nt + 1) * sizeof(float2) + (size_t)nt * sizeof(int);
 	return pl;
 }

@@ -388,6 +388,7 @@ struct GridRatioPlan {
 	size_t lds;                    // dynamic LDS in bytes
 };
 GridRatioPlan channelize_grid_ratio_plan(int p, int q);
+void channelize_grid_ratio_runs(GridRatioPlan &pl, int q);   // ch and groups for pl.nt, pl.m and pl.n_taps (the survey's tile differs)
 int channelize_grid_ratio_row(const GridRatioPlan &pl, int bin);   // where a bin stands behind the transform
 void launch_channelize_grid_ratio(hipStream_t s, const ChannelizeArgs &a);
 long long channelize_grid_ratio_max_outputs();
@@ -536,5 +537,31 @@ struct SurveyGridArgs {
 	float *out;
 };
 void launch_survey_grid(hipStream_t s, const SurveyGridArgs &a, float scale);
+
+// ---- the grid survey at a ratio (k_survey_grid_ratio.hip): the mean power of every slot of the ratio grid front
+// end's bank (4.22), n_rows rows of n_all slots, p / q in lowest terms with p = 2^a 3^b 5^c (not q = 1 with p a power of two: that is
+// 4.21's kernel).  in, in_first, n_in, t_first, n_times, n_groups, n_rows: as SurveyGridArgs.  taps, tw, inc: the ratio-grid table
+// of 4.22 with every slot in ascending order, inc[c] & 0xffff the LDS row of slot k_first + c.  k_survey_grid_ratio leaves the power
+// of group j at part + j n_all floats in slot order; k_survey_grid_ratio_rows sums a row's groups in ascending order, multiplies by
+// scale and writes row r at out + (r - row_first) n_all.
+struct SurveyGridRatioArgs {
+	const void *in;
+	int fmt;                       // OFDMRX_FMT_*
+	int p, q;
+	long long in_first, n_in;
+	const float *taps;             // device, [T][q]
+	const float2 *tw;              // device, the M roots e^{-2 pi i j / M}
+	const unsigned *inc;           // device, [n_all]
+	int n_all;
+	long long t_first, n_times;
+	int n_groups;                  // S / 8
+	long long n_rows;              // n_rows n_groups n_all <= survey_max_partial_floats()
+	float *part;                   // device, n_rows n_groups n_all floats
+	float *out;
+};
+// the front end's plan with the survey's own tile, a multiple of 8 (the tile enters no output)
+GridRatioPlan survey_grid_ratio_plan(int p, int q);
+// (an error only where the runtime refuses more than 64 KiB of dynamic LDS: the 8-time tile at M >= 960)
+hipError_t launch_survey_grid_ratio(hipStream_t s, const SurveyGridRatioArgs &a, float scale);
 
 }  // namespace rx

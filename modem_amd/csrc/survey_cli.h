@@ -1,7 +1,8 @@
 // survey_cli.h -- what `survey` and `decode_stream --wideband DECIM|P/Q auto` share: the decimation argument, and the occupied bands
 // of a whole wideband capture
 // (ofdmrx_util_survey + ofdmrx_util_find_bands) with the finder's default parameters; and what `survey --grid`
-// and `decode_stream --grid DECIM auto[:FLOOR_DB]` share: the occupied slots of a whole grid capture (section 4.21).
+// and `decode_stream --grid DECIM auto[:FLOOR_DB]` share: the occupied slots of a whole grid capture (section 4.21); and the same at a
+// ratio for `survey --grid-ratio` and `decode_stream --grid-ratio P/Q auto[:FLOOR_DB]` (section 4.24).
 #pragma once
 #include "wav_read.h"
 #include <hip/hip_runtime.h>
@@ -160,6 +161,71 @@ static bool survey_grid_capture(ofdmrx_handle *h, const Wav &w, int decim, doubl
 	r = ofdmrx_util_find_slots(peak.data(), decim, (double)w.rate / (double)decim, SURVEY_THR_DB, SURVEY_SEP_DB, abs_floor, slots.size(), slots.data(), &n, &floor);
 	if (r) {
 		std::fprintf(stderr, "ofdmrx_util_find_slots: %s\n", ofdmrx_strerror(r));
+		return false;
+	}
+	slots.resize(n);
+	return true;
+}
+
+// ---- the same at a ratio, for `survey --grid-ratio` and `decode_stream --grid-ratio P/Q auto[:FLOOR_DB]` (ofdmrx_util_survey_grid_ratio
+// + ofdmrx_util_find_slots_ratio).  p / q: any spelling of a ratio the grid front end at a ratio takes
+// (ofdmrx_util_grid_ratio_slots accepts it); w.rate q / p is the handle's rate.  Rows of 4096 output times, peak hold over the rows,
+// a trailing partial row dropped, abs_floor 0: the median.
+static bool survey_grid_ratio_capture(ofdmrx_handle *h, const Wav &w, int p, int q, double abs_floor, std::vector<ofdmrx_slot> &slots, double &floor)
+{
+	int32_t k_first = 0;
+	size_t N = 0;
+	if (p <= 0 || q <= 0 || ofdmrx_util_grid_ratio_slots(p, q, &k_first, &N)) {
+		std::fprintf(stderr, "A grid survey at a ratio takes P/Q with, in lowest terms, Q 1 .. 16 and P 2 Q .. 512 with no prime factor other than 2, 3 and 5.\n");
+		return false;
+	}
+	size_t g = (size_t)p, b = (size_t)q;
+	while (b) {
+		const size_t t = g % b;
+		g = b;
+		b = t;
+	}
+	const size_t P = (size_t)p / g, Q = (size_t)q / g, S = SURVEY_GRID_TIMES, H = 24 * P / Q;
+	// output time n ends inside the file where (n P) div Q <= frames - 1
+	const size_t times = w.frames ? (w.frames * Q - 1) / P + 1 : 0, n_rows = times / S;
+	if (!n_rows) {
+		std::fprintf(stderr, "The capture is shorter than one row of %zu output times (%zu samples).\n", S, (S - 1) * P / Q + 1);
+		return false;
+	}
+	const size_t unit = w.pcm.size() / w.frames, per_block = std::max<size_t>(1, 1024 * Q / P);
+	const size_t max_in = per_block * S * P / Q + H + 2;
+	void *d_in = nullptr, *d_out = nullptr;
+	std::vector<float> rows(per_block * N), peak(N, 0.f);
+	hipError_t e = hipMalloc(&d_in, max_in * unit);
+	e = e == hipSuccess ? hipMalloc(&d_out, rows.size() * sizeof(float)) : e;
+	int r = 0;
+	for (size_t r0 = 0; r0 < n_rows && e == hipSuccess && !r; r0 += per_block) {
+		const size_t nb = std::min(per_block, n_rows - r0);
+		const size_t at = r0 * S * P / Q, first = at > H ? at - H : 0, count = ((r0 + nb) * S - 1) * P / Q - first + 1;
+		e = hipMemcpy(d_in, w.pcm.data() + first * unit, count * unit, hipMemcpyHostToDevice);
+		if (e != hipSuccess)
+			break;
+		r = ofdmrx_util_survey_grid_ratio(h, d_in, w.fmt, (long long)first, count, p, q, (int)S, (long long)r0, nb, (float *)d_out);
+		r = r ? r : ofdmrx_synchronize(h);
+		if (r) {
+			std::fprintf(stderr, "ofdmrx_util_survey_grid_ratio: %s\n", ofdmrx_strerror(r));
+			break;
+		}
+		e = hipMemcpy(rows.data(), d_out, nb * N * sizeof(float), hipMemcpyDeviceToHost);
+		for (size_t j = 0; j < nb * N && e == hipSuccess; ++j)
+			peak[j % N] = std::max(peak[j % N], rows[j]);
+	}
+	if (e != hipSuccess)
+		std::fprintf(stderr, "survey: %s\n", hipGetErrorString(e));
+	(void)hipFree(d_in);
+	(void)hipFree(d_out);
+	if (r || e != hipSuccess)
+		return false;
+	size_t n = 0;
+	slots.resize(N);
+	r = ofdmrx_util_find_slots_ratio(peak.data(), p, q, (double)w.rate * (double)q / (double)p, SURVEY_THR_DB, SURVEY_SEP_DB, abs_floor, slots.size(), slots.data(), &n, &floor);
+	if (r) {
+		std::fprintf(stderr, "ofdmrx_util_find_slots_ratio: %s\n", ofdmrx_strerror(r));
 		return false;
 	}
 	slots.resize(n);

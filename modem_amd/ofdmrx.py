@@ -44,6 +44,7 @@ EXPORTS = [
     "ofdmrx_util_channelize_grid_ratio_taps", "ofdmrx_util_grid_ratio_slots", "ofdmrx_util_channelize_grid_ratio",
     "ofdmrx_bank_begin_wideband_grid_ratio",
     "ofdmrx_util_synthesize_grid_ratio", "ofdmrx_util_synthesize_grid_ratio_chunk",
+    "ofdmrx_util_survey_grid_ratio", "ofdmrx_util_find_slots_ratio",
 ]
 
 
@@ -263,11 +264,20 @@ class Slot(C.Structure):
 
 def survey_grid_span(decim, times_per_row, row_first, n_rows):
     """the wideband positions the rows row_first .. row_first + n_rows - 1 of the grid survey need -> (first position, count):
-    max(0, (row_first S - 24) D) .. ((row_first + n_rows) S - 1) D with S = times_per_row, D = decim"""
-    D, S, r0, n = int(decim), int(times_per_row), int(row_first), int(n_rows)
-    _grid_slots(D, None)
+    max(0, (row_first S - 24) D) .. ((row_first + n_rows) S - 1) D with S = times_per_row, D = decim.  decim may
+    be a ratio - a pair (p, q) or a fractions.Fraction: max(0, (row_first S p) // q - 24 p // q) .. (((row_first + n_rows) S - 1) p) // q
+    with p / q in lowest terms (section 4.24)"""
+    D, q = _ratio(decim)
+    S, r0, n = int(times_per_row), int(row_first), int(n_rows)
+    if q is not None:
+        p, q, _, _ = _grid_ratio(D, q)
+    else:
+        _grid_slots(D, None)
     if S < 8 or S > 65536 or S % 8 or r0 < 0 or n < 1:
         raise OfdmRxError("survey_grid_span: times_per_row a multiple of 8 in 8 .. 65536, row_first >= 0, n_rows >= 1")
+    if q is not None:
+        first = max(0, (r0 * S * p) // q - 24 * p // q)
+        return first, (((r0 + n) * S - 1) * p) // q - first + 1
     first = max(0, (r0 * S - 24) * D)
     return first, ((r0 + n) * S - 1) * D - first + 1
 
@@ -276,17 +286,27 @@ def find_slots(row, decim, rate, thr_db=6.0, sep_db=8.0, abs_floor=0.0, with_flo
     """the occupied slots of ONE grid survey row (fp32 [2 decim], ascending slot order, on the host or a device tensor) at the handle
     rate `rate` -> a list of dicts (slot, centre_hz, power, level_db) in ascending order; with_floor: -> (list, floor).  The floor is
     abs_floor where that is > 0, else the row's median; a slot more than sep_db below a cyclic neighbour is taken for that
-    neighbour's edge and dropped - so a real signal that far below a neighbouring one is not found"""
+    neighbour's edge and dropped - so a real signal that far below a neighbouring one is not found.  decim
+    may be a ratio - a pair (p, q) or a fractions.Fraction: the row then holds the n_all slots of the grid at that ratio, whose first
+    and last slot are neighbours only where the slots tile the circle (the reduced q is 1 or 2); where they lie half a slot apart or
+    less across the band edge and within sep_db of each other they are one signal and the louder is reported (section 4.24)"""
     if hasattr(row, "detach"):
         row = row.detach().cpu().numpy()
     row = np.ascontiguousarray(row, dtype=np.float32).reshape(-1)
-    decim = int(decim)
-    if decim < 2 or decim > 512 or decim & (decim - 1) or row.size != 2 * decim:
-        raise OfdmRxError("find_slots: decim must be a power of two 2 .. 512 and the row 2 decim values")
+    decim, q = _ratio(decim)
     L = load_library()
+    if q is not None:
+        p, q, _, n_all = _grid_ratio(decim, q)
+        if row.size != n_all:
+            raise OfdmRxError("find_slots: the row of the ratio %d/%d has %d values" % (p, q, n_all))
+    elif decim < 2 or decim > 512 or decim & (decim - 1) or row.size != 2 * decim:
+        raise OfdmRxError("find_slots: decim must be a power of two 2 .. 512 and the row 2 decim values")
     slots = (Slot * row.size)()
     n, floor = C.c_size_t(0), C.c_double(0.0)
-    r = L.ofdmrx_util_find_slots(_ptr(row), decim, rate, thr_db, sep_db, abs_floor, row.size, slots, C.byref(n), C.byref(floor))
+    if q is not None:
+        r = L.ofdmrx_util_find_slots_ratio(_ptr(row), p, q, rate, thr_db, sep_db, abs_floor, row.size, slots, C.byref(n), C.byref(floor))
+    else:
+        r = L.ofdmrx_util_find_slots(_ptr(row), decim, rate, thr_db, sep_db, abs_floor, row.size, slots, C.byref(n), C.byref(floor))
     if r != 0:
         raise OfdmRxError("find_slots: %s (%d)" % (L.ofdmrx_strerror(r).decode(), r))
     out = [{k: getattr(slots[i], k) for k, _ in Slot._fields_} for i in range(n.value)]
@@ -436,6 +456,10 @@ def load_library():
                                           C.c_size_t, C.c_void_p]
     L.ofdmrx_util_find_slots.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+    L.ofdmrx_util_survey_grid_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                C.c_longlong, C.c_size_t, C.c_void_p]
+    L.ofdmrx_util_find_slots_ratio.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
     L.ofdmrx_tx_frame_samples.restype = C.c_long
     L.ofdmrx_tx_frame_samples.argtypes = [C.c_int]
     L.ofdmrx_frame_samples.restype = C.c_long
@@ -898,10 +922,14 @@ class Receiver:
         end's bank, torch.float32 [n_rows, 2 decim] on the device in ascending slot order (index i: slot i - decim at (i - decim) rate
         / 2), rows row_first .. of times_per_row output times each (a multiple of 8).  times_per_row=None: one row over every whole
         group of 8 output times the buffer holds (its first 65536 times if it holds more); n_rows=None: every whole row from row_first
-        on that the buffer holds.  Waits for torch's current stream before the launch and for the handle's stream after it"""
+        on that the buffer holds.  decim may be a ratio - a pair (p, q) or a fractions.Fraction: the result is [n_rows, n_all], the slots
+        of the grid front end at that ratio in ascending order from k_first.  Waits for torch's current stream
+        before the launch and for the handle's stream after it"""
         import torch
         unit = {FMT_S16: 4, FMT_U8: 2, FMT_F32: 8}[sample_format]
-        decim = int(decim)
+        decim, q = _ratio(decim)
+        if q is not None:
+            return self._survey_grid_ratio(d_wide, sample_format, unit, decim, q, times_per_row, in_first, row_first, n_rows)
         n_in = d_wide.numel() * d_wide.element_size() // unit
         times = (in_first + n_in - 1) // max(decim, 1) + 1 if n_in else 0   # the output times 0 .. times - 1 end inside the buffer
         if times_per_row is None:
@@ -914,6 +942,26 @@ class Receiver:
         torch.cuda.current_stream(d_wide.device).synchronize()
         self._check(self._lib.ofdmrx_util_survey_grid(self._h, d_wide.data_ptr(), sample_format, in_first, n_in, decim, times_per_row,
                                                       row_first, max(n_rows, 0), out.data_ptr()))
+        self.synchronize()
+        return out
+
+    def _survey_grid_ratio(self, d_wide, sample_format, unit, p, q, times_per_row, in_first, row_first, n_rows):
+        """survey_grid at the ratio p / q -> [n_rows, n_all]: output time n ends inside the buffer where
+        (n p') // q' does, p' / q' the ratio in lowest terms"""
+        import torch
+        p, q, _, n_all = _grid_ratio(p, q)
+        n_in = d_wide.numel() * d_wide.element_size() // unit
+        times = ((in_first + n_in) * q - 1) // p + 1 if n_in else 0     # the n with (n p) // q <= in_first + n_in - 1
+        if times_per_row is None:
+            if in_first or row_first:
+                raise OfdmRxError("survey_grid: times_per_row=None surveys a buffer that starts at position 0, as row 0")
+            times_per_row, n_rows = min(times // 8 * 8, 65536), 1
+        if n_rows is None:
+            n_rows = times // max(times_per_row, 1) - row_first
+        out = torch.empty((max(n_rows, 0), n_all), dtype=torch.float32, device=d_wide.device)
+        torch.cuda.current_stream(d_wide.device).synchronize()
+        self._check(self._lib.ofdmrx_util_survey_grid_ratio(self._h, d_wide.data_ptr(), sample_format, in_first, n_in, p, q, times_per_row,
+                                                            row_first, max(n_rows, 0), out.data_ptr()))
         self.synchronize()
         return out
 
