@@ -69,7 +69,8 @@ extern "C" {
  *      ofdmrx_util_grid_ratio_slots, ofdmrx_util_channelize_grid_ratio, ofdmrx_bank_begin_wideband_grid_ratio; the wideband
  *      synthesizer on a channel grid at any ratio P / Q (a mixed-radix synthesis bank) - ofdmrx_util_synthesize_grid_ratio,
  *      ofdmrx_util_synthesize_grid_ratio_chunk; the grid survey at any ratio P / Q (per-slot power from the mixed-radix bank) -
- *      ofdmrx_util_survey_grid_ratio, ofdmrx_util_find_slots_ratio */
+ *      ofdmrx_util_survey_grid_ratio, ofdmrx_util_find_slots_ratio; the wideband front end for a real (one-channel) capture -
+ *      ofdmrx_util_channelize_real, ofdmrx_bank_begin_wideband_real */
 #define OFDMRX_ABI_MINOR 9
 
 #define OFDMRX_PAYLOAD_BYTES 5380     /* decode.cc:587  data_len = 43040/8 */
@@ -439,6 +440,15 @@ int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_channels, const 
  * outside 1..65535 in the place of its limits.  While it is open ofdmrx_util_channelize* (the grid entry too) and ofdmrx_bank_push
  * are refused. */
 int ofdmrx_bank_begin_wideband_grid(ofdmrx_handle *h, size_t n_slots, const int32_t *slots, int decim, int sample_format);
+/* ... of a REAL capture at p / q x the handle's rate, one value of sample_format per wideband position (added within revision 1.9,
+ * detected by symbol): the front end is ofdmrx_util_channelize_real below, q = 1 its integer decimation.
+ * ofdmrx_bank_push_wideband, ofdmrx_bank_end and the queries serve it unchanged: n_wide counts real samples (samples on the
+ * sample's boundary), after W of them every channel has been fed ceil(W q / p) samples, the tail kept between pushes is T - 1 samples,
+ * one copy and one launch per push whatever the number of channels, and the contract above holds with row c of
+ * ofdmrx_util_channelize_real.  OFDMRX_E_ARG: what ofdmrx_bank_begin_wideband_ratio refuses, with ofdmrx_util_channelize_real's rule
+ * for the centres in place of "outside +- rate p / q / 2".  The plain and the wideband entries refuse each other as above, and
+ * ofdmrx_util_channelize_real is refused while a feed or bank is open. */
+int ofdmrx_bank_begin_wideband_real(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int sample_format);
 
 int ofdmrx_synchronize(ofdmrx_handle *h);
 int ofdmrx_get_timing(ofdmrx_handle *h, ofdmrx_timing *t);
@@ -636,6 +646,34 @@ int ofdmrx_util_channelize(ofdmrx_handle *h, const void *d_in, int sample_format
  * the same bytes by construction. */
 int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps);
 int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
+
+/* Wideband front end for a real capture (added within revision 1.9, detected by symbol): a ONE-channel capture - a sound-card
+ * recording of a receiver's audio or IF, the real IF of a direct-sampling receiver - at Rw = rate p / q -> n_channels receiver
+ * channels at the handle's rate.  For a real x the mix-down and low-pass is itself the Hilbert step: the stop band removes the mirror
+ * image.  DESIGN.md section 4.25 is the definition, held component by component to a float64 model.  p / q is reduced by its gcd, with
+ * the limits of ofdmrx_util_channelize_ratio (1 <= q <= 16, 2 <= p / q <= 32; q = 1 is the integer decimation D = p); Rw, K, T, the
+ * taps (h at q = 1, else h_r[j]), the times i_n, q_n and the increment inc_c are those of ofdmrx_util_channelize and
+ * ofdmrx_util_channelize_ratio, unchanged: there is no new filter.
+ *   input   ONE value per wideband position, S16, U8 or F32, scaled as the decoder scales a mono sample; x zero at negative indices
+ *   output  y_c[n] = 2 sum_j h_{q_n}[j] x[i_n - j] e^{-2 pi i phase_c(i_n - j) / 2^32}, fp32 I/Q, no clip.  The 2 makes a real cosine
+ *           of amplitude A an analytic signal of amplitude A - what the mono decoder's own front end makes of it, and what the real
+ *           part of a synthesized capture needs for a unity round trip.
+ *   sums    those of ofdmrx_util_channelize (q = 1) or ofdmrx_util_channelize_ratio on the capture (x, +0) in the same order, with
+ *           the products by the zero component left out - one FMA chain per component - and the multiplication by 2 last.  The
+ *           output is, BYTE FOR BYTE, twice the output of those entries on the same samples with a +0 imaginary part.
+ * No state: a capture cut into blocks (each handed over with the T - 1 samples before it) gives the same bytes as one call.
+ * Centres: a real capture holds every signal at +f and its conjugate at -f, so the channel at centre f sees its mirror at distance
+ * 2 |f| (mod Rw).  The pass band is flat to rate / 4 on either side, so a centre with |f| < rate / 4 or |f| > Rw / 2 - rate / 4, where
+ * the mirror's pass band overlaps the channel's own, is refused.  From rate / 4 to about 0.35 rate (and as near Rw / 2) the mirror lies
+ * in the filter's transition band: it comes out attenuated and outside the modem's own band, and is NOT refused - the reference's
+ * default offset of 2000 Hz at 8 kHz is such a centre.  A negative centre is legal and gives the channel of the conjugate spectrum:
+ * that is how the inverted audio of a lower-sideband receiver is decoded.
+ * n_in counts samples and d_in must sit on the sample's boundary; every other argument, memory space, asynchrony and refusal is
+ * ofdmrx_util_channelize_ratio's, with the centre rule above (and a centre that is not finite) in place of "outside +- Rw / 2".
+ * OFDMRX_E_ARG comes before any device call and leaves the output untouched.  Not built: the real-input grid banks, the surveys of a
+ * real capture, a synthesizer that writes one channel. */
+int ofdmrx_util_channelize_real(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride);
 
 /* Wideband front end on a channel grid (added within revision 1.9, detected by symbol): a polyphase filter bank for channels on a

@@ -13,7 +13,9 @@
 // the handle's rate, and "the new samples" of a push are made on the device - the wideband block is copied once behind the last
 // T - 1 wideband samples (kept on the host and sent with it), and ONE k_channelize launch writes every channel's new samples straight
 // into its window (a bank opened with ofdmrx_bank_begin_wideband_ratio, DESIGN.md 4.17: ONE k_rechannelize launch; with
-// ofdmrx_bank_begin_wideband_grid, DESIGN.md 4.19: ONE k_channelize_grid launch, the tail up to 24 x 512 samples).  Everything behind
+// ofdmrx_bank_begin_wideband_grid, DESIGN.md 4.19: ONE k_channelize_grid launch, the tail up to 24 x 512 samples; with
+// ofdmrx_bank_begin_wideband_real, DESIGN.md 4.25: a REAL capture, one value per wideband sample frame, ONE k_channelize_real or
+// k_rechannelize_real launch).  Everything behind
 // that step is the same code.
 // The windows of all channels live in one slab pair [n_channels][cap] with a common capacity; channel c's window begins at its own
 // base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch: it is handed the address position 0
@@ -58,7 +60,8 @@ struct ofdmrx_bank {
 	// a wideband bank: decimation, the format of the wideband samples, how many have been pushed, and the last min(wfed, T - 1) of them
 	// (decimation p / q in lowest terms: an integer decimation has q = 1 and runs k_channelize, any other k_rechannelize, DESIGN.md 4.17;
 	// a grid bank, DESIGN.md 4.19, has q = 1 and runs k_channelize_grid: the handle's table says so, which the open bank owns)
-	bool wide = false;
+	// (wreal: a real capture, DESIGN.md 4.25 - one value per wideband position, k_channelize_real / k_rechannelize_real)
+	bool wide = false, wreal = false;
 	int p = 0, q = 1, wfmt = 0;
 	long long wfed = 0;
 	std::vector<char> wtail;
@@ -80,6 +83,8 @@ Lens lens_of(int rate)
 	return Lens{};
 }
 size_t frame_bytes(const ofdmrx_bank &b) { return sample_bytes(b.fmt) * (size_t)b.channels; }
+// a wideband bank: bytes per wideband sample frame - I/Q, or the one value of a real capture
+size_t wide_bytes(const ofdmrx_bank &b) { return (b.wreal ? 1 : 2) * sample_bytes(b.wfmt); }
 
 // the per-channel arrays a call uploads in one copy, P = C + 1 values each
 // (the window move has three planes: raw samples, analytic signal, DC states; sources and destinations are addresses)
@@ -219,7 +224,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 	// ---- 2. the new samples, packed so that every share lies as its place in the window does modulo 16
 	size_t packed = 0;
 	long long pl_most = 0;
-	const size_t wunit = 2 * sample_bytes(b.wfmt);                // (a wideband bank: bytes per wideband sample frame)
+	const size_t wunit = wide_bytes(b);
 	try {
 		size_t total = b.wide ? b.wtail.size() + n_wide * wunit : 0;
 		for (size_t c = 0; c < C && add && !b.wide; ++c)
@@ -349,6 +354,7 @@ int bank_step(ofdmrx_handle *h, const char *samples, size_t stride, const size_t
 			a.out_first = o0;
 			a.n_out = o1 - o0;
 			a.dst = dpar + P_PL_DST * P;
+			a.real = b.wreal;
 			launch_channelize_any(s, a);
 			b.ops += 2;
 		}
@@ -715,19 +721,19 @@ extern "C" int ofdmrx_bank_push(ofdmrx_handle *h, const void *samples, size_t st
 
 // ---- a wideband bank: one wideband capture in, every channel made from it on the device at the reduced
 // decimation p / q (q = 1: the integer decimation p); push, end and the queries serve every ratio alike
-static int begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt)
+// real: the capture is real, one value per wideband position
+static int begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt, bool real = false)
 {
 	if (!h || !centre_hz || fmt < OFDMRX_FMT_S16 || fmt > OFDMRX_FMT_F32 || n_channels < 1 || n_channels > 65535)
 		return OFDMRX_E_ARG;
 	if (h->bank)
 		return OFDMRX_E_ARG;
-	for (size_t c = 0; c < n_channels; ++c)
-		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * ((double)h->rate * (double)p / (double)q))
-			return OFDMRX_E_ARG;
+	if (channelize_centres(h->rate, p, q, centre_hz, n_channels, real))
+		return OFDMRX_E_ARG;
 	int r = begin(h, n_channels, OFDMRX_FMT_F32, 2, false);
 	if (r)
 		return r;
-	if ((r = channelize_setup(h, p, q, centre_hz, n_channels))) {
+	if ((r = channelize_setup(h, p, q, centre_hz, n_channels, real))) {
 		bank_free(h);
 		return r;
 	}
@@ -735,6 +741,7 @@ static int begin_wideband(ofdmrx_handle *h, size_t n_channels, const double *cen
 	h->bank->p = p;
 	h->bank->q = q;
 	h->bank->wfmt = fmt;
+	h->bank->wreal = real;
 	return 0;
 }
 
@@ -750,6 +757,14 @@ extern "C" int ofdmrx_bank_begin_wideband_ratio(ofdmrx_handle *h, size_t n_chann
 	if (rechannelize_ratio(p, q))
 		return OFDMRX_E_ARG;
 	return begin_wideband(h, n_channels, centre_hz, p, q, fmt);
+}
+
+// a real capture: n_wide of ofdmrx_bank_push_wideband counts its samples, the kept tail is T - 1 of them
+extern "C" int ofdmrx_bank_begin_wideband_real(ofdmrx_handle *h, size_t n_channels, const double *centre_hz, int p, int q, int fmt)
+{
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	return begin_wideband(h, n_channels, centre_hz, p, q, fmt, true);
 }
 
 // the grid front end: channel j is slot slots[j] of the raster rate / 2 (slots = NULL with n_slots = 2 decim: all)
@@ -803,7 +818,7 @@ extern "C" int ofdmrx_bank_push_wideband(ofdmrx_handle *h, const void *samples, 
 	if (r || (max_records && (!record_channel || !record_index)) || !live(h, false) || !h->bank->wide)
 		return OFDMRX_E_ARG;
 	ofdmrx_bank &b = *h->bank;
-	const size_t wunit = 2 * sample_bytes(b.wfmt);
+	const size_t wunit = wide_bytes(b);
 	if (n_wide > ((size_t)1 << 26) || (n_wide && (!samples || (size_t)samples % wunit || b.ending || b.ch[0].ended)))
 		return OFDMRX_E_ARG;
 	HIP_OK(hipSetDevice(h->cfg.device));

@@ -1,7 +1,8 @@
 // api_channelize.cpp -- the wideband front end behind include/ofdmrx.h (DESIGN.md sections 4.14 and 4.17): the taps, the phase
 // increments, and one host path for every decimation p / q - ofdmrx_util_channelize is p = decim, q = 1 of what
-// ofdmrx_util_channelize_ratio does, and launch_channelize picks the kernel by q.  Everything the kernels rely on is checked here,
-// before any device call.
+// ofdmrx_util_channelize_ratio does, and launch_channelize picks the kernel by q.  ofdmrx_util_channelize_real (section 4.25) is the
+// same path with a flag: a real capture, one value per position, the same taps and increments, its own rule for the centres.
+// Everything the kernels rely on is checked here, before any device call.
 #include "api_internal.h"
 
 namespace rx {
@@ -133,15 +134,29 @@ static int channelize_upload(ofdmrx_handle *h, int p, int q, int grid, const std
 	return 0;
 }
 
-int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels)
+// the centres a front end at p / q takes: finite and inside +- Rw / 2.  real: a real capture holds every signal at
+// +f and its conjugate at -f, and the pass band is flat to rate / 4 on either side of a centre, so a centre with |f| < rate / 4 (the
+// mirror across 0) or |f| > Rw / 2 - rate / 4 (the mirror across Rw / 2) has the mirror's pass band over its own: refused
+int channelize_centres(int rate, int p, int q, const double *centre_hz, size_t n_channels, bool real)
 {
+	const double rw = (double)rate * (double)p / (double)q, edge = 0.25 * (double)rate;
+	for (size_t c = 0; c < n_channels; ++c) {
+		const double f = std::fabs(centre_hz[c]);
+		if (!std::isfinite(f) || f > 0.5 * rw || (real && (f < edge || f > 0.5 * rw - edge)))
+			return OFDMRX_E_ARG;
+	}
+	return 0;
+}
+
+// (a real capture's taps and increments are the analytic ones: the device tables do not know the kind of the capture)
+int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels, bool real)
+{
+	if (channelize_centres(h->rate, p, q, centre_hz, n_channels, real))
+		return OFDMRX_E_ARG;
 	const double rw = (double)h->rate * (double)p / (double)q;
 	std::vector<unsigned> inc(n_channels);
-	for (size_t c = 0; c < n_channels; ++c) {
-		if (!std::isfinite(centre_hz[c]) || std::fabs(centre_hz[c]) > 0.5 * rw)
-			return OFDMRX_E_ARG;
+	for (size_t c = 0; c < n_channels; ++c)
 		inc[c] = channelize_inc(centre_hz[c], rw);
-	}
 	return channelize_upload(h, p, q, 0, inc);
 }
 
@@ -227,7 +242,9 @@ int channelize_grid_ratio_setup(ofdmrx_handle *h, int p, int q, const std::vecto
 
 void launch_channelize_any(hipStream_t s, const ChannelizeArgs &a)
 {
-	if (a.grid == 2)
+	if (a.real)
+		launch_channelize_real(s, a);
+	else if (a.grid == 2)
 		launch_channelize_grid_ratio(s, a);
 	else if (a.grid)
 		launch_channelize_grid(s, a);
@@ -259,9 +276,10 @@ extern "C" int ofdmrx_util_channelize_ratio_taps(int p, int q, float *taps)
 
 // one call at the reduced ratio p / q (q = 1: the integer decimation p).  grid: the grid front end at decimation p / q, whose channels
 // are the slots (nullable: all of them) and not centres - section 4.19's where q = 1 and p is a power of two, else section 4.22's
+// real: d_in is a real capture, one value per wideband position (section 4.25; not with grid)
 static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
 	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride,
-	bool grid = false, const int32_t *slots = nullptr)
+	bool grid = false, const int32_t *slots = nullptr, bool real = false)
 {
 	constexpr long long FAR = 1LL << 50;                          // positions and counts stay far inside 64 bits
 	if (!h || !d_in || !d_out || (!grid && !centre_hz) || !n_in || !n_out || n_channels < 1 || n_channels > 65535)
@@ -270,7 +288,7 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 		return OFDMRX_E_ARG;
 	if (in_first > FAR || out_first > FAR || n_in > (size_t)FAR || n_out > (size_t)(!grid ? channelize_max_outputs(q) : is_plain_grid(p, q) ? channelize_grid_max_outputs() : channelize_grid_ratio_max_outputs()) || out_stride > (size_t)FAR / 65536)
 		return OFDMRX_E_ARG;
-	const size_t unit = 2 * sample_bytes(sample_format);
+	const size_t unit = (real ? 1 : 2) * sample_bytes(sample_format);
 	if ((size_t)d_in % unit || (size_t)d_out % sizeof(float2))
 		return OFDMRX_E_ARG;
 	const long long P = p, Q = q, T = 24 * P / Q + 1;
@@ -288,9 +306,11 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 	for (size_t c = 0; c < n_channels && !grid; ++c)
 		if (!std::isfinite(centre_hz[c]))
 			return OFDMRX_E_ARG;
+	if (real && channelize_centres(h->rate, p, q, centre_hz, n_channels, true))
+		return OFDMRX_E_ARG;
 	if (h->busy_live())                                           // (an open wideband bank owns the taps and increments on the device)
 		return OFDMRX_E_ARG;
-	int r = grid ? channelize_grid_ratio_setup(h, p, q, slot_list) : channelize_setup(h, p, q, centre_hz, n_channels);
+	int r = grid ? channelize_grid_ratio_setup(h, p, q, slot_list) : channelize_setup(h, p, q, centre_hz, n_channels, real);
 	if (r)
 		return r;
 	HIP_OK(hipSetDevice(h->cfg.device));
@@ -308,6 +328,7 @@ static int channelize_call(ofdmrx_handle *h, const void *d_in, int sample_format
 	a.out = d_out;
 	a.out_stride = (long long)out_stride;
 	a.dst = nullptr;
+	a.real = real;
 	launch_channelize_any(h->stream, a);
 	HIP_OK(hipGetLastError());
 	return 0;
@@ -327,6 +348,15 @@ extern "C" int ofdmrx_util_channelize_ratio(ofdmrx_handle *h, const void *d_in, 
 	if (rechannelize_ratio(p, q))
 		return OFDMRX_E_ARG;
 	return channelize_call(h, d_in, sample_format, in_first, n_in, p, q, centre_hz, n_channels, out_first, n_out, d_out, out_stride);
+}
+
+// the front end for a real capture: one entry for every ratio, q = 1 the integer decimation
+extern "C" int ofdmrx_util_channelize_real(ofdmrx_handle *h, const void *d_in, int sample_format, long long in_first, size_t n_in, int p, int q,
+	const double *centre_hz, size_t n_channels, long long out_first, size_t n_out, float *d_out, size_t out_stride)
+{
+	if (rechannelize_ratio(p, q))
+		return OFDMRX_E_ARG;
+	return channelize_call(h, d_in, sample_format, in_first, n_in, p, q, centre_hz, n_channels, out_first, n_out, d_out, out_stride, false, nullptr, true);
 }
 
 extern "C" int ofdmrx_util_channelize_grid_taps(int decim, float *taps)

@@ -305,7 +305,10 @@ int rechannelize_ratio(int &p, int &q);
 // the roots of a grid table: dst[2 j], dst[2 j + 1] = e^{+-i pi j / p}, j = 0 .. n - 1 (negative: the minus sign), made in double and
 // rounded once
 void grid_roots(int p, int n, bool negative, float *dst);
-int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels);   // (p / q reduced; q = 1: decimation p)
+// channelize_centres: OFDMRX_E_ARG for a centre that is not finite or outside +- Rw / 2 - real (a real capture): or
+// with |f| < rate / 4 or |f| > Rw / 2 - rate / 4; channelize_setup checks the same and sets the device tables up
+int channelize_centres(int rate, int p, int q, const double *centre_hz, size_t n_channels, bool real);
+int channelize_setup(ofdmrx_handle *h, int p, int q, const double *centre_hz, size_t n_channels, bool real = false);   // (p / q reduced; q = 1: decimation p)
 // the grid front end: decim a power of two 2 .. 512 (else OFDMRX_E_ARG); the slots of a grid table, -decim ..
 // decim - 1 each (slots = nullptr: all 2 decim in ascending order, n_slots must be 2 decim), and the table itself on the device
 int channelize_grid_decim(int decim);

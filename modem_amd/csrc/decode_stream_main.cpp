@@ -19,6 +19,11 @@
 // on stderr, and then exactly the form above runs with that list.  The file is read twice, so `auto` does not take standard input.
 // DECIM may be a ratio P/Q in both forms - it is one when it holds a '/' (Q <= 16, 2 <= P / Q <= 32): the
 // capture's rate x Q / P must be a supported rate, and the bank is opened with ofdmrx_bank_begin_wideband_ratio.
+// `decode_stream --wideband-real DECIM|P/Q F1,F2,... OUTROOT MONO.wav`: the same for a REAL capture (DESIGN.md section 4.25,
+// ofdmrx_bank_begin_wideband_real) - a ONE-channel file, a sound-card recording of a receiver's audio or IF - read in blocks of one
+// wideband second.  A centre with |F| < rate / 4 or |F| > capture rate / 2 - rate / 4 is refused by the library.  A two-channel file
+// is refused (that is `--wideband`), and so is `auto`: the survey of a real capture is not built.  The `--wideband` forms keep turning
+// a one-channel file away.
 // `decode_stream --grid DECIM K1,K2,...|all OUTROOT WIDE.wav`: the same through the grid front end (DESIGN.md section 4.19,
 // ofdmrx_bank_begin_wideband_grid): DECIM a power of two 2 .. 512, the capture's rate DECIM x a supported rate, channel i the slot Ki
 // (-DECIM .. DECIM - 1; `all`: every slot in ascending order) centred at Ki x rate / 2.  Every opened slot's centre is printed on
@@ -402,8 +407,10 @@ static std::string survey_slots(const char *decim_arg, const char *how, const ch
 	return list;
 }
 
-// one wideband capture block by block through a wideband bank (grid: through a grid bank - centre_list holds slot numbers, or `all`)
-static int run_wideband(const Decimation &decim, const char *centre_list, const std::string &outroot, const char *input_name, bool grid = false)
+// one wideband capture block by block through a wideband bank (grid: through a grid bank - centre_list holds slot numbers, or `all`;
+// real: a one-channel capture through the bank for a real capture, not with grid)
+static int run_wideband(const Decimation &decim, const char *centre_list, const std::string &outroot, const char *input_name, bool grid = false,
+	bool real = false)
 {
 	std::vector<double> centres;
 	std::vector<int32_t> slots;
@@ -461,7 +468,11 @@ static int run_wideband(const Decimation &decim, const char *centre_list, const 
 		std::fprintf(stderr, "Couldn't open file \"%s\" for reading.\n", input_name);
 		return 1;
 	}
-	if (w.channels != 2) {
+	if (real && w.channels != 1) {
+		std::fprintf(stderr, "--wideband-real takes a real capture (one channel); an analytic capture (two channels) is `--wideband`.\n");
+		return 1;
+	}
+	if (!real && w.channels != 2) {
 		std::fprintf(stderr, "A wideband capture is an analytic signal (two channels).\n");
 		return 1;
 	}
@@ -485,7 +496,8 @@ static int run_wideband(const Decimation &decim, const char *centre_list, const 
 		centres[i] = (double)slots[i] * 0.5 * (double)decim.rate_of(w.rate);
 		std::fprintf(stderr, "%zu: slot %d, centre %.17g Hz\n", i, (int)slots[i], centres[i]);
 	}
-	int r = grid && decim.ratio ? ofdmrx_bank_begin_wideband_grid_ratio(h, S, slots.data(), decim.p, decim.q, w.fmt)
+	int r = real ? ofdmrx_bank_begin_wideband_real(h, S, centres.data(), decim.p, decim.q, w.fmt)
+		: grid && decim.ratio ? ofdmrx_bank_begin_wideband_grid_ratio(h, S, slots.data(), decim.p, decim.q, w.fmt)
 		: grid ? ofdmrx_bank_begin_wideband_grid(h, S, slots.data(), decim.p, w.fmt)
 		: decim.ratio ? ofdmrx_bank_begin_wideband_ratio(h, S, centres.data(), decim.p, decim.q, w.fmt)
 		: ofdmrx_bank_begin_wideband(h, S, centres.data(), decim.p, w.fmt);
@@ -532,6 +544,13 @@ int main(int argc, char **argv)
 	}
 	if (argc == 6 && !std::strcmp(argv[1], "--wideband"))
 		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5]);
+	if (argc == 6 && !std::strcmp(argv[1], "--wideband-real")) {
+		if (!std::strncmp(argv[3], "auto", 4) && (!argv[3][4] || argv[3][4] == ':')) {
+			std::fprintf(stderr, "The survey of a real capture is not built: `--wideband-real DECIM auto` is refused; name the centre frequencies.\n");
+			return 1;
+		}
+		return run_wideband(Decimation(argv[2]), argv[3], argv[4], argv[5], false, true);
+	}
 	if (argc == 6 && !std::strcmp(argv[1], "--grid") && !std::strncmp(argv[3], "auto", 4) && (!argv[3][4] || argv[3][4] == ':')) {
 		const std::string found = survey_slots(argv[2], argv[3], argv[5]);
 		return found.empty() ? 1 : run_wideband(Decimation(argv[2]), found.c_str(), argv[4], argv[5], true);
@@ -555,8 +574,8 @@ int main(int argc, char **argv)
 		return run_batch(argv[2], argc - 3, argv + 3);
 	const bool live = argc == 4 && !std::strcmp(argv[1], "--live");
 	if (argc != 3 && !live) {
-		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --grid DECIM|P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n       %s --grid-ratio P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
-			argv[0], argv[0], argv[0], argv[0], argv[0]);
+		std::fprintf(stderr, "usage: %s [--live] OUTDIR INPUT\n       %s [--live] --batch OUTROOT INPUT...\n       %s --wideband DECIM|P/Q F1,F2,...|auto OUTROOT INPUT\n       %s --wideband-real DECIM|P/Q F1,F2,... OUTROOT MONO_INPUT\n       %s --grid DECIM|P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n       %s --grid-ratio P/Q K1,K2,...|all|auto[:FLOOR_DB] OUTROOT INPUT\n",
+			argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
 		return 1;
 	}
 	const std::string outdir = argv[live ? 2 : 1];

@@ -360,11 +360,17 @@ struct ChannelizeArgs {
 	// tw: device, the M / 2 roots e^{+2 pi i j / M}, rounded once from double
 	int grid;
 	const float2 *tw;
+	// a REAL capture (k_channelize_real.hip): real != 0, grid == 0; in holds ONE value of fmt per wideband position
+	int real;
 };
 // k_channelize where a.q == 1, k_rechannelize (launch_channelize_ratio) otherwise: each keeps its own summation order (see the files)
 void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
 void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a);   // k_rechannelize.hip: launch_channelize's q > 1
 long long channelize_max_outputs(int q);
+// a.real != 0 (the callers choose): k_channelize_real where a.q == 1, k_rechannelize_real otherwise - the sums of launch_channelize
+// on the capture (x, +0), doubled, byte for byte; its tiles (256 outputs at q = 1, q M of rechannelize_real_shape otherwise) are no
+// shorter than launch_channelize's, so channelize_max_outputs bounds n_out here too
+void launch_channelize_real(hipStream_t s, const ChannelizeArgs &a);
 void launch_channelize_grid(hipStream_t s, const ChannelizeArgs &a);    // k_channelize_grid.hip: a.grid != 0 (the callers choose)
 // log2 M of the grid's D = 2, 4 .. 512 (M = 2 D), for the front end, the synthesizer and the survey; D must be one of those powers of
 // two (channelize_grid_decim): any other D is rounded up to the next, which is not its transform
@@ -396,6 +402,8 @@ long long channelize_grid_ratio_max_outputs();
 // the rows of a plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
 struct RechannelizeShape { int n_taps, m, hist, rows, passes; size_t lds; };
 RechannelizeShape rechannelize_shape(int p, int q);
+// the same for k_rechannelize_real, whose span is float: the same rule for M and the slots per lane with twice the rows inside 64 KiB
+RechannelizeShape rechannelize_real_shape(int p, int q);
 // host: the taps of decimation D (T = 24 D + 1 of them; returns T) and the phase increment of a centre frequency at wideband rate rw
 int channelize_taps(int decim, float *taps);
 unsigned channelize_inc(double centre_hz, double rw);

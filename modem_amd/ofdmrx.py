@@ -45,6 +45,7 @@ EXPORTS = [
     "ofdmrx_bank_begin_wideband_grid_ratio",
     "ofdmrx_util_synthesize_grid_ratio", "ofdmrx_util_synthesize_grid_ratio_chunk",
     "ofdmrx_util_survey_grid_ratio", "ofdmrx_util_find_slots_ratio",
+    "ofdmrx_util_channelize_real", "ofdmrx_bank_begin_wideband_real",
 ]
 
 
@@ -424,6 +425,8 @@ def load_library():
     L.ofdmrx_util_channelize_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
                                                C.c_size_t, C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
     L.ofdmrx_bank_begin_wideband_ratio.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.ofdmrx_util_channelize_real.argtypes = L.ofdmrx_util_channelize_ratio.argtypes
+    L.ofdmrx_bank_begin_wideband_real.argtypes = L.ofdmrx_bank_begin_wideband_ratio.argtypes
     L.ofdmrx_util_channelize_grid_taps.argtypes = [C.c_int, C.c_void_p]
     L.ofdmrx_util_channelize_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                               C.c_longlong, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -601,6 +604,12 @@ class Receiver:
         the centre frequencies centres_hz: push the capture block by block.  decim: an int, or a ratio - a pair (p, q) or a
         fractions.Fraction"""
         return WidebandBank(self, centres_hz, decim, dtype, esn0_rows)
+
+    def wideband_real_bank(self, centres_hz, decim, dtype=np.int16, esn0_rows=False):
+        """open a bank whose channels are cut from one REAL wideband capture (decim x the handle's rate, one value of dtype per
+        position) at the centre frequencies centres_hz: push the capture as 1-D blocks.  decim: an int, a
+        pair (p, q) or a fractions.Fraction.  The centres obey Receiver.channelize_real's rule"""
+        return WidebandRealBank(self, centres_hz, decim, dtype, esn0_rows)
 
     def wideband_grid_bank(self, slots, decim, dtype=np.int16, esn0_rows=False):
         """open a bank whose channels are slots of the raster rate / 2 of one wideband I/Q capture at decim x the handle's rate (decim a
@@ -838,6 +847,17 @@ class Receiver:
             return
         self._check(self._lib.ofdmrx_util_channelize(self._h, d_in, fmt, in_first, n_in, decim, _ptr(f), f.size, out_first, n_out, d_out,
                                                      n_out if out_stride is None else out_stride))
+
+    def channelize_real(self, d_in, fmt, in_first, n_in, decim, centres_hz, out_first, n_out, d_out, out_stride=None):
+        """the wideband front end for a REAL capture on device buffers (ints): as channelize, but d_in holds
+        ONE value of fmt per wideband position and n_in counts samples; the output is twice what channelize gives for the same
+        samples with a zero imaginary part.  A centre with |f| < rate / 4 or |f| > decim rate / 2 - rate / 4 is refused (its mirror
+        image overlaps it); a negative centre gives the conjugate spectrum's channel.  decim: an int, a pair (p, q) or a
+        fractions.Fraction"""
+        f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
+        p, q = _ratio(decim)
+        self._check(self._lib.ofdmrx_util_channelize_real(self._h, d_in, fmt, in_first, n_in, p, 1 if q is None else q, _ptr(f), f.size,
+                                                          out_first, n_out, d_out, n_out if out_stride is None else out_stride))
 
     def channelize_grid(self, d_in, fmt, in_first, n_in, decim, slots, out_first, n_out, d_out, out_stride=None):
         """the grid front end on device buffers (ints): as channelize, for a decim that is a power of two 2 ..
@@ -1183,6 +1203,34 @@ class WidebandBank(Bank):
         """more wideband samples [k, 2] (k may be 0); end: every channel's stream is over after them -> (payloads, results,
         record_channel, record_index[, esn0 rows])"""
         pcm = np.ascontiguousarray(block, dtype=self.dtype).reshape(-1, 2)
+        n = pcm.shape[0]
+        return self._call(lambda first, cap, o, r, ch, ix, a, b: self._lib.ofdmrx_bank_push_wideband(
+            self._h, _ptr(pcm) if n and first else None, n if first else 0, 1 if end and first else 0, cap, o, r, ch, ix, a, b), max_records)
+
+
+class WidebandRealBank(WidebandBank):
+    """A wideband bank fed one REAL capture (ofdmrx_bank_begin_wideband_real): push(block) takes the next
+    samples as a 1-D block; end and the queries are WidebandBank's.  The records of channel c are what Receiver.decode_stream returns
+    for row c of Receiver.channelize_real over the whole capture, however it is cut."""
+
+    def __init__(self, rx, centres_hz, decim, dtype=np.int16, esn0_rows=False):
+        self._rx, self._lib, self._h = rx, rx._lib, rx._h
+        f = np.ascontiguousarray(centres_hz, dtype=np.float64).reshape(-1)
+        p, q = _ratio(decim)
+        self.centres_hz, self.decim = f, p if q is None else (p, q)
+        self.n_channels, self.channels, self.dtype, self._rows = f.size, 2, np.dtype(dtype), bool(esn0_rows)
+        rx._check(self._lib.ofdmrx_bank_begin_wideband_real(self._h, f.size, _ptr(f), p, 1 if q is None else q, rx._fmt(self.dtype)))
+        self.open = True
+        self.n_left = 0
+        self._ops = 0
+
+    def push(self, block, end=False, max_records=None):
+        """more real wideband samples, a 1-D block (it may be empty); end: every channel's stream is over after them -> what
+        WidebandBank.push returns"""
+        pcm = np.asarray(block)
+        if pcm.ndim != 1:
+            raise OfdmRxError("WidebandRealBank.push: a real capture arrives as a 1-D block, got shape %s" % (pcm.shape,))
+        pcm = np.ascontiguousarray(pcm, dtype=self.dtype)
         n = pcm.shape[0]
         return self._call(lambda first, cap, o, r, ch, ix, a, b: self._lib.ofdmrx_bank_push_wideband(
             self._h, _ptr(pcm) if n and first else None, n if first else 0, 1 if end and first else 0, cap, o, r, ch, ix, a, b), max_records)

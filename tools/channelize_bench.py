@@ -20,6 +20,10 @@ bank with those slots.
 k_channelize_grid_ratio.hip), with one slot (slot 0, or SLOTS) and with all slots, beside: the direct form
 (k_rechannelize / k_channelize) on the same centres in the same run where P / Q <= 32; k_channelize_grid at the next power of two
 >= P on the same samples, for Q = 1; k_awgn_tile on the same bytes.
+--real [P/Q] (repeatable; no value: D = 6, 16 and 32; a bare integer is that D) times the front end for a REAL capture
+(ofdmrx_util_channelize_real, k_channelize_real.hip) beside the analytic front end on the same number of
+wideband samples and the same centres in the same run, for 4 and 64 channels (--channels): each figure is the time of one launch
+from events round --inner launches, the median of --reps such groups with the least and the most beside it.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
 import argparse
 import ctypes as C
@@ -383,8 +387,69 @@ def child_grid_ratio(args):
     print(json.dumps({"tool": "channelize_bench", "samples": W, "grid_ratio_rows": rows}), flush=True)
 
 
+def child_real(args):
+    import numpy as np
+    import torch
+    import modem_amd
+
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(stream)
+    rx = modem_amd.Receiver(device=0, stream=stream.cuda_stream)
+    W = args.samples
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    d_iq = torch.randint(-20000, 20000, (W, 2), dtype=torch.int16, device=dev, generator=gen)
+    d_re = d_iq[:, 0].contiguous()
+
+    def timed(f):
+        """-> (median, least, most) ms per launch"""
+        ms = []
+        for k in range(args.warmup + args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            for _ in range(args.inner):
+                f()
+            b.record(stream)
+            b.synchronize()
+            if k >= args.warmup:
+                ms.append(a.elapsed_time(b) / args.inner)
+        return statistics.median(ms), min(ms), max(ms)
+
+    ratios = []
+    for r in args.real:
+        for t in (["6", "16", "32"] if r is None else [r]):
+            ratios.append(tuple(int(v) for v in t.split("/")) if "/" in t else (int(t), 1))
+    rows = []
+    for P, Q in ratios:
+        decim = P if Q == 1 else (P, Q)
+        rw = 8000.0 * P / Q
+        n_out = -(-W * Q // P)
+        for N in args.channels:
+            # inside the real front end's rule, rate / 4 <= |f| <= Rw / 2 - rate / 4, of alternating sign
+            f = np.linspace(2000.0 + 1.123, rw / 2 - 2000.0 - 1.123, N) * np.where(np.arange(N) % 2, -1.0, 1.0)
+            d_out = torch.empty((N, n_out, 2), dtype=torch.float32, device=dev)
+            real = timed(lambda: rx.channelize_real(d_re.data_ptr(), 0, 0, W, decim, f, 0, n_out, d_out.data_ptr()))
+            ana = timed(lambda: rx.channelize(d_iq.data_ptr(), 0, 0, W, decim, f, 0, n_out, d_out.data_ptr()))
+            rows.append(dict(ratio="%d/%d" % (P, Q), channels=N, n_out=n_out, real_ms=round(real[0], 4), real_min_ms=round(real[1], 4),
+                             real_max_ms=round(real[2], 4), analytic_ms=round(ana[0], 4), analytic_min_ms=round(ana[1], 4),
+                             analytic_max_ms=round(ana[2], 4), analytic_over_real=round(ana[0] / real[0], 2)))
+            del d_out
+    rx.close()
+    print("ratio   channels   n_out   real ms (least .. most)      analytic ms (least .. most)   analytic / real")
+    for r in rows:
+        print("%-7s %8d %7d %8.4f (%.4f .. %.4f) %10.4f (%.4f .. %.4f) %12.2f"
+              % (r["ratio"], r["channels"], r["n_out"], r["real_ms"], r["real_min_ms"], r["real_max_ms"], r["analytic_ms"], r["analytic_min_ms"],
+                 r["analytic_max_ms"], r["analytic_over_real"]))
+    print(json.dumps({"tool": "channelize_bench", "samples": W, "inner": args.inner, "reps": args.reps, "real_rows": rows}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--real", action="append", nargs="?", default=[], metavar="P/Q",
+                    help="time the front end for a real capture beside the analytic one at D = 6, 16, 32, or at this ratio or D (repeatable)")
+    ap.add_argument("--channels", type=int, nargs="+", default=[4, 64], help="channel counts of --real")
+    ap.add_argument("--inner", type=int, default=10, help="launches per timed group of --real")
     ap.add_argument("--grid", action="append", nargs="+", default=[], metavar="D", help="time the grid front end at decimation D, or at the ratio P/Q, [SLOTS] (repeatable)")
     ap.add_argument("--ratio", action="append", default=[], metavar="P/Q", help="time the front end at this rational decimation (repeatable)")
     ap.add_argument("--samples", type=int, default=1 << 20)
@@ -394,6 +459,8 @@ def main():
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
+        if args.real:
+            return child_real(args)
         if args.grid and any("/" in g[0] for g in args.grid):
             if not all("/" in g[0] for g in args.grid):
                 print("channelize_bench: --grid takes either ratios P/Q or powers of two in one run", file=sys.stderr)
@@ -403,6 +470,10 @@ def main():
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--samples", str(args.samples), "--reps", str(args.reps), "--warmup", str(args.warmup)]
     for r in args.ratio:
         cmd += ["--ratio", r]
+    for r in args.real:
+        cmd += ["--real"] + ([] if r is None else [r])
+    if args.real:
+        cmd += ["--inner", str(args.inner), "--channels"] + [str(n) for n in args.channels]
     for g in args.grid:
         cmd += ["--grid"] + g
     try:
