@@ -14,8 +14,8 @@
 // T - 1 wideband samples (kept on the host and sent with it), and ONE k_channelize launch writes every channel's new samples straight
 // into its window (a bank opened with ofdmrx_bank_begin_wideband_ratio, DESIGN.md 4.17: ONE k_rechannelize launch; with
 // ofdmrx_bank_begin_wideband_grid, DESIGN.md 4.19: ONE k_channelize_grid launch, the tail up to 24 x 512 samples; with
-// ofdmrx_bank_begin_wideband_real, DESIGN.md 4.25: a REAL capture, one value per wideband sample frame, ONE k_channelize_real or
-// k_rechannelize_real launch).  Everything behind
+// ofdmrx_bank_begin_wideband_real, DESIGN.md 4.25: a REAL capture, one value per wideband sample frame, ONE launch of the same
+// k_channelize or k_rechannelize instantiated for it).  Everything behind
 // that step is the same code.
 // The windows of all channels live in one slab pair [n_channels][cap] with a common capacity; channel c's window begins at its own
 // base[c].  Every kernel sees absolute positions of the channel it reads (kernels.h: WindowBatch: it is handed the address position 0
@@ -60,7 +60,7 @@ struct ofdmrx_bank {
 	// a wideband bank: decimation, the format of the wideband samples, how many have been pushed, and the last min(wfed, T - 1) of them
 	// (decimation p / q in lowest terms: an integer decimation has q = 1 and runs k_channelize, any other k_rechannelize, DESIGN.md 4.17;
 	// a grid bank, DESIGN.md 4.19, has q = 1 and runs k_channelize_grid: the handle's table says so, which the open bank owns)
-	// (wreal: a real capture, DESIGN.md 4.25 - one value per wideband position, k_channelize_real / k_rechannelize_real)
+	// (wreal: a real capture, DESIGN.md 4.25 - one value per wideband position, the same two kernels instantiated for it)
 	bool wide = false, wreal = false;
 	int p = 0, q = 1, wfmt = 0;
 	long long wfed = 0;

@@ -1,7 +1,8 @@
 // api_channelize.cpp -- the wideband front end behind include/ofdmrx.h (DESIGN.md sections 4.14 and 4.17): the taps, the phase
 // increments, and one host path for every decimation p / q - ofdmrx_util_channelize is p = decim, q = 1 of what
 // ofdmrx_util_channelize_ratio does, and launch_channelize picks the kernel by q.  ofdmrx_util_channelize_real (section 4.25) is the
-// same path with a flag: a real capture, one value per position, the same taps and increments, its own rule for the centres.
+// same path with a flag, down to launch_channelize: a real capture, one value per position, the same taps and increments, its own
+// rule for the centres.
 // Everything the kernels rely on is checked here, before any device call.
 #include "api_internal.h"
 
@@ -242,9 +243,7 @@ int channelize_grid_ratio_setup(ofdmrx_handle *h, int p, int q, const std::vecto
 
 void launch_channelize_any(hipStream_t s, const ChannelizeArgs &a)
 {
-	if (a.real)
-		launch_channelize_real(s, a);
-	else if (a.grid == 2)
+	if (a.grid == 2)
 		launch_channelize_grid_ratio(s, a);
 	else if (a.grid)
 		launch_channelize_grid(s, a);

@@ -166,6 +166,15 @@ template <int FMT> __device__ __forceinline__ float2 iq_sample(const void *in, s
 	}
 	return ((const float2 *)in)[i];
 }
+// value i of a one-channel capture as fp32, scaled as iq_sample scales a component.  The caller has checked the bounds
+template <int FMT> __device__ __forceinline__ float real_sample(const void *in, size_t i)
+{
+	if (FMT == 0)
+		return div_32767((float)((const short *)in)[i]);
+	if (FMT == 1)
+		return div_127((float)((int)((const uint8_t *)in)[i] - 128));
+	return ((const float *)in)[i];
+}
 
 // e^{2 pi i phase / 2^32}: the phase as a signed fraction of a turn, |x| <= 1/2 (the conversion is off by at most 2^-26 turns)
 __device__ __forceinline__ void phase_phasor(unsigned phase, float &cs, float &sn)

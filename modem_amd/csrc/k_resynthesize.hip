@@ -1,5 +1,5 @@
 // k_resynthesize.hip -- the wideband synthesizer at a rational interpolation P / Q, the mirror image of
-// k_rechannelize.hip: n_channels narrowband transmissions at the handle's rate -> one wideband I/Q capture at rate P / Q.  Like
+// k_rechannelize (k_channelize.hip): n_channels narrowband transmissions at the handle's rate -> one wideband I/Q capture at rate P / Q.  Like
 // k_synthesize every output is a closed form of absolute sample indices, so the kernel has no state and a capture cuts into windows
 // without changing a bit.  G[tn], tn = 0 .. 24 P, is the ratio front end's fp32 tap table read as one sequence on the grid of 1 / Q
 // wideband samples (G[tn] = H[tn mod Q][tn div Q]).  At absolute wideband index m, with r = m - start_c, nu = r Q, q0 = nu div P,

@@ -335,7 +335,7 @@ long front_end_stretch();
 void launch_bank_dc(hipStream_t s, int n_ch, long max_tiles, WindowBatch fb, FrontCoef co, double *tile_end, double *tile_in, double *ck);
 void launch_bank_front_end(hipStream_t s, int rate, int n_ch, long max_stretch, WindowBatch fb, MonoArgs ma, cf *z);
 
-// ---- the wideband front end (k_channelize.hip, k_rechannelize.hip): mix-down, FIR and decimation by p / q
+// ---- the wideband front end (k_channelize.hip): mix-down, FIR and decimation by p / q
 // (in lowest terms, 1 <= q <= 16, 2 <= p / q <= 32; q = 1: the integer decimation D = p) of one wideband capture into n_channels
 // channel rows.  in: wideband positions in_first .. in_first + n_in - 1 (interleaved I/Q of fmt); every position outside reads as
 // zero and is never loaded.  Output n of channel c (n = out_first .. out_first + n_out - 1) reads the wideband positions
@@ -360,17 +360,14 @@ struct ChannelizeArgs {
 	// tw: device, the M / 2 roots e^{+2 pi i j / M}, rounded once from double
 	int grid;
 	const float2 *tw;
-	// a REAL capture (k_channelize_real.hip): real != 0, grid == 0; in holds ONE value of fmt per wideband position
+	// a REAL capture: real != 0, grid == 0; in holds ONE value of fmt per wideband position
 	int real;
 };
-// k_channelize where a.q == 1, k_rechannelize (launch_channelize_ratio) otherwise: each keeps its own summation order (see the files)
+// a.grid == 0: k_channelize where a.q == 1, k_rechannelize otherwise - each keeps its own summation order (see the file) - for an
+// analytic capture or, a.real != 0, a real one: the same sums on the capture (x, +0), doubled, byte for byte.  A real capture's
+// tiles are no shorter than an analytic one's, so channelize_max_outputs bounds n_out for both
 void launch_channelize(hipStream_t s, const ChannelizeArgs &a);
-void launch_channelize_ratio(hipStream_t s, const ChannelizeArgs &a);   // k_rechannelize.hip: launch_channelize's q > 1
 long long channelize_max_outputs(int q);
-// a.real != 0 (the callers choose): k_channelize_real where a.q == 1, k_rechannelize_real otherwise - the sums of launch_channelize
-// on the capture (x, +0), doubled, byte for byte; its tiles (256 outputs at q = 1, q M of rechannelize_real_shape otherwise) are no
-// shorter than launch_channelize's, so channelize_max_outputs bounds n_out here too
-void launch_channelize_real(hipStream_t s, const ChannelizeArgs &a);
 void launch_channelize_grid(hipStream_t s, const ChannelizeArgs &a);    // k_channelize_grid.hip: a.grid != 0 (the callers choose)
 // log2 M of the grid's D = 2, 4 .. 512 (M = 2 D), for the front end, the synthesizer and the survey; D must be one of those powers of
 // two (channelize_grid_decim): any other D is rounded up to the next, which is not its transform
@@ -383,7 +380,7 @@ constexpr int grid_logm(int D)
 }
 long long channelize_grid_max_outputs();
 // the grid front end at a ratio (k_channelize_grid_ratio.hip): a.grid == 2, p / q in lowest terms with p = 2^a 3^b 5^c
-// (not q = 1 with p a power of two: that is 4.19's kernel), M = 2 p; taps as launch_channelize_ratio reads them; tw: device, the M
+// (not q = 1 with p a power of two: that is 4.19's kernel), M = 2 p; taps as k_rechannelize reads them; tw: device, the M
 // roots e^{-2 pi i j / M}, rounded once from double; channel c is slot k_c with
 // inc[c] = channelize_grid_ratio_row(plan, (-k_c q) mod M) | (k_c q mod M) << 16
 struct GridRatioPlan {
@@ -398,12 +395,6 @@ void channelize_grid_ratio_runs(GridRatioPlan &pl, int q);   // ch and groups fo
 int channelize_grid_ratio_row(const GridRatioPlan &pl, int bin);   // where a bin stands behind the transform
 void launch_channelize_grid_ratio(hipStream_t s, const ChannelizeArgs &a);
 long long channelize_grid_ratio_max_outputs();
-// what a workgroup's tile of k_rechannelize looks like: T, the outputs per residue M (a tile is q M outputs), the rows of history,
-// the rows of a plane in LDS, the slots per lane (64 passes >= q M), the dynamic LDS in bytes
-struct RechannelizeShape { int n_taps, m, hist, rows, passes; size_t lds; };
-RechannelizeShape rechannelize_shape(int p, int q);
-// the same for k_rechannelize_real, whose span is float: the same rule for M and the slots per lane with twice the rows inside 64 KiB
-RechannelizeShape rechannelize_real_shape(int p, int q);
 // host: the taps of decimation D (T = 24 D + 1 of them; returns T) and the phase increment of a centre frequency at wideband rate rw
 int channelize_taps(int decim, float *taps);
 unsigned channelize_inc(double centre_hz, double rw);

@@ -1,4 +1,4 @@
-"""float64 model of the wideband front end for a REAL capture (k_channelize_real.hip behind
+"""float64 model of the wideband front end for a REAL capture (k_channelize.hip behind
 ofdmrx_util_channelize_real), and the tolerance the device is held to.
 
 The definition.  Handle rate `rate`, ratio P / Q in lowest terms, 1 <= Q <= 16, 2 <= P / Q <= 32 (Q = 1: the integer decimation D =

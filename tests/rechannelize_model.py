@@ -1,4 +1,4 @@
-"""float64 model of the wideband front end at a rational decimation (k_rechannelize.hip behind
+"""float64 model of the wideband front end at a rational decimation (k_rechannelize in k_channelize.hip behind
 ofdmrx_util_channelize_ratio), and the tolerance the device is held to.
 
 The definition.  Handle rate `rate`, ratio P / Q in lowest terms, 1 <= Q <= 16, 2 <= P / Q <= 32.  D = P / Q and K = 12 D are real,

@@ -1,11 +1,12 @@
-"""The wideband front end for a real capture on the device (k_channelize_real.hip behind ofdmrx_util_channelize_real, DESIGN.md
-section 4.25) against the float64 model of channelize_real_model.py: |got - v| <= tol on every component of every output, nothing
-exempt; the tolerance is derived in the model's header.  And as bytes: against twice the analytic entries on the same samples with a
-+0 imaginary part, blocks against one call, calls in turn on one handle.  Every output buffer is filled with a sentinel first and has
-spare columns and a spare row, which must come back untouched.
+"""The wideband front end for a real capture on the device (k_channelize.hip's kernels instantiated for a real capture, behind
+ofdmrx_util_channelize_real) against the float64 model of channelize_real_model.py: |got - v| <= tol on every
+component of every output, nothing exempt; the tolerance is derived in the model's header.  And as bytes: against twice the analytic
+entries on the same samples with a +0 imaginary part, blocks against one call, calls in turn on one handle.  Every output buffer is
+filled with a sentinel first and has spare columns and a spare row, which must come back untouched.
 
-The launch has one shape at every integer D (a tile of 256 outputs; k_channelize_real.hip: chr_launch), so there is no D at which it
-changes: D = 16 and 17 are here because the ANALYTIC kernel the bytes are compared with changes its tile between them."""
+The launch has one shape at every integer D (a tile of 256 outputs; k_channelize.hip: channelize_outputs_per_lane), so there is no D
+at which it changes: D = 16 and 17 are here because the ANALYTIC instantiation the bytes are compared with changes its tile between
+them."""
 import ctypes as C
 import fractions
 
@@ -13,6 +14,7 @@ import numpy as np
 import pytest
 
 import channelize_real_model as XM
+import channelize_tile as CT
 
 pytestmark = pytest.mark.gpu
 
@@ -21,6 +23,7 @@ RATE = 8000
 INTEGER = ((2, 1), (6, 1), (16, 1), (17, 1), (32, 1))
 FRACTIONAL = ((25, 4), (64, 3), (125, 16))
 RATIOS = INTEGER + FRACTIONAL
+SLOT_RATIOS = ((49, 2), (472, 15))                                  # here 4 slots per lane, 3 and 1 in the analytic kernel compared with
 FMT = {np.dtype(np.int16): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2}
 
 
@@ -38,19 +41,9 @@ def _dev(a):
 
 
 def tile_of(P, Q):
-    """the outputs of one workgroup's tile: 256 at an integer D; at a ratio Q M (k_channelize_real.hip: rechannelize_real_shape), M as
-    many as leave four waves' phasors and the span [P][odd rows] of float inside 64 KiB, at most 64 NP / Q for NP slots per lane"""
-    if Q == 1:
-        return 256
-    T = 24 * P // Q + 1
-    hist = -(-(T - 1) // P)
-    rows = (65536 - 32 * T) // 4 // P
-    rows -= 1 - rows % 2
-    for passes in (4, 3, 2, 1):
-        m = min(64 * passes // Q, rows - hist)
-        if 100 * Q * m >= 85 * 64 * passes:
-            break
-    return Q * m
+    """the outputs of one workgroup's tile for a span of float: 256 at an integer D, Q M at a ratio (k_channelize.hip:
+    rechannelize_shape)"""
+    return CT.tile_shape(P, Q, 4)[0]
 
 
 def samples_for(n, P, Q):
@@ -105,13 +98,14 @@ def _check(rx, x, P, Q, centres, what, **kw):
 
 def test_tiles_of_the_tested_ratios():
     """(the sizes below are cut around these)"""
-    assert [tile_of(P, Q) for P, Q in RATIOS] == [256, 256, 256, 256, 256, 256, 255, 256]
+    assert [tile_of(P, Q) for P, Q in RATIOS + SLOT_RATIOS] == [256, 256, 256, 256, 256, 256, 255, 256, 256, 255]
 
 
 @pytest.mark.parametrize("n_channels", [1, 4, 5])
-@pytest.mark.parametrize("P,Q", RATIOS)
+@pytest.mark.parametrize("P,Q", RATIOS + SLOT_RATIOS)
 def test_shapes_match_model(rx, P, Q, n_channels):
-    """one output, a tile less one, a tile, a tile and one; one channel, four (a workgroup's waves), five (a second group of one)"""
+    """one output, a tile less one, a tile, a tile and one; one channel, four (a workgroup's waves), five (a second group of one).
+    At SLOT_RATIOS the bytes compared are those of the analytic kernel at 3 and at 1 slots per lane"""
     f = centres_for(P, Q, n_channels)
     tile = tile_of(P, Q)
     for n in (1, tile - 1, tile, tile + 1):

@@ -1,19 +1,21 @@
-"""The wideband front end at a rational decimation on the device (k_rechannelize.hip behind ofdmrx_util_channelize_ratio) against the
-float64 model of rechannelize_model.py: |got - v| <= tol on every component of every output, nothing
-exempt; the tolerance is derived in the model's header.  Every output buffer is filled with a sentinel first and has spare columns
-and a spare row, which must come back untouched.  Each test prints its worst |got - v| / tol (profiles/rechannelize_parity.txt
-keeps them)."""
+"""The wideband front end at a rational decimation on the device (k_rechannelize in k_channelize.hip, behind
+ofdmrx_util_channelize_ratio) against the float64 model of rechannelize_model.py: |got - v| <= tol on every
+component of every output, nothing exempt; the tolerance is derived in the model's header.  Every output buffer is filled with a
+sentinel first and has spare columns and a spare row, which must come back untouched.  Each test prints its worst |got - v| / tol
+(profiles/rechannelize_parity.txt keeps them)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import channelize_tile as CT
 import rechannelize_model as RM
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 12345.0
 RATIOS_8K = ((5, 2), (33, 16), (25, 4), (125, 4), (511, 16))
+SLOT_RATIOS = ((49, 2), (472, 15))                                  # k_rechannelize<.., NP> at NP = 3 and NP = 1: no ratio above selects them
 FMT = {np.dtype(np.int16): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2}
 
 
@@ -39,18 +41,8 @@ def _dev(a):
 
 
 def tile_of(P, Q):
-    """the outputs of one workgroup's tile (k_rechannelize.hip: rechannelize_shape): Q M, with M outputs per residue - as many as
-    leave the span [P][odd rows] and four waves' phasors inside 64 KiB of LDS, and at most 64 NP / Q for NP slots per lane, NP the
-    largest of 4 .. 1 at which 85 % of the slots hold an output"""
-    T = 24 * P // Q + 1
-    hist = -(-(T - 1) // P)
-    rows = (65536 - 32 * T) // 8 // P
-    rows -= 1 - rows % 2
-    for passes in (4, 3, 2, 1):
-        m = min(64 * passes // Q, rows - hist)
-        if 100 * Q * m >= 85 * 64 * passes:
-            break
-    return Q * m
+    """the outputs of one workgroup's tile (k_channelize.hip: rechannelize_shape), for a span of float2"""
+    return CT.tile_shape(P, Q, 8)[0]
 
 
 def samples_for(n, P, Q):
@@ -102,8 +94,8 @@ def sizes(P, Q):
 
 
 def test_tiles_of_the_tested_ratios():
-    """(the sizes below are cut around these; k_rechannelize.hip's header has the rule)"""
-    assert [tile_of(P, Q) for P, Q in RATIOS_8K + ((64, 3),)] == [256, 256, 256, 128, 112, 255]
+    """(the sizes below are cut around these; k_channelize.hip has the rule)"""
+    assert [tile_of(P, Q) for P, Q in RATIOS_8K + ((64, 3),) + SLOT_RATIOS] == [256, 256, 256, 128, 112, 255, 192, 60]
 
 
 @pytest.mark.parametrize("n_channels", [1, 3, 65])
@@ -129,6 +121,42 @@ def test_a_48_khz_handle(rx48, n_channels):
         pcm = RM.random_pcm(n_in, np.int16, seed=n_in)
         worst = max(worst, _check(rx48, pcm, P, Q, f, "48 kHz n_in %d" % n_in, rate=48000)[1])
     print("rechannelize %d/%d at 48 kHz, %d channels, all sizes: worst %.4f" % (P, Q, n_channels, worst))
+
+
+def test_slots_per_lane_of_the_tested_ratios():
+    """the k_rechannelize<.., NP> each ratio runs: 5/2 and 125/4 above at NP = 4 and 2, SLOT_RATIOS at NP = 3 and 1"""
+    assert [CT.tile_shape(P, Q, 8)[1] for P, Q in ((5, 2), (125, 4)) + SLOT_RATIOS] == [4, 2, 3, 1]
+
+
+@pytest.mark.parametrize("n_channels", [1, 5])
+@pytest.mark.parametrize("P,Q", SLOT_RATIOS)
+def test_three_and_one_slots_per_lane_match_model(rx, rx48, P, Q, n_channels):
+    """49/2 (NP = 3, a tile of 192) and 472/15 (NP = 1, a tile of 60; on the 48 kHz handle, where its wideband rate is a whole
+    number of hertz): a tile of outputs less one, exactly, plus one, three tiles and five; one channel and five (a second workgroup of
+    one).  Then the longest capture in two blocks, cut inside its second tile, against the one call as bytes"""
+    import torch
+    r, rate = (rx48, 48000) if Q == 15 else (rx, 8000)
+    T, tile = 24 * P // Q + 1, tile_of(P, Q)
+    f = centres_for(P, Q, n_channels, rate=rate, seed=6)
+    for n in (tile - 1, tile, tile + 1, 3 * tile + 5):
+        pcm = RM.random_pcm(samples_for(n, P, Q), np.int16, seed=n)
+        whole, _ = _check(r, pcm, P, Q, f, "%d outputs" % n, rate=rate)
+    W, n_all = len(pcm), 3 * tile + 5
+    assert whole.shape[1] == n_all
+    d_in = _dev(pcm)
+    out = torch.full((n_channels, n_all + 2, 2), SENTINEL, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    fed = 0
+    for new in (samples_for(tile + tile // 3, P, Q), W):
+        o0, o1 = RM.n_outputs(fed, P, Q), RM.n_outputs(new, P, Q)
+        fed = new
+        assert o1 > o0
+        i0 = max(0, o0 * P // Q - (T - 1))
+        r.channelize(d_in.data_ptr() + 4 * i0, 0, i0, fed - i0, (P, Q), f, o0, o1 - o0, out.data_ptr() + 8 * o0, n_all + 2)
+    r.synchronize()
+    got = out.cpu().numpy()
+    assert (got[:, n_all:] == SENTINEL).all()
+    assert got[:, :n_all].tobytes() == whole.tobytes()
 
 
 @pytest.mark.parametrize("P,Q", RATIOS_8K)

@@ -7,7 +7,7 @@ For 1, 16 and 256 channels at D = 6 and D = 24, with hipEvents on the handle's s
   N n_out T 4 FMAs at DESIGN.md section 6's 0.86 ns per wave64 FMA and SIMD (1024 SIMDs), and which of the two is nearer.
 Then one wideband-bank push of one second x 64 channels against ofdmrx_util_channelize + copy to host + ofdmrx_bank_push of the same
 data (host wall time: these calls block).
---ratio P/Q (repeatable) times the front end at a rational decimation instead (ofdmrx_util_channelize_ratio, k_rechannelize.hip;
+--ratio P/Q (repeatable) times the front end at a rational decimation instead (ofdmrx_util_channelize_ratio, k_rechannelize;
 DESIGN.md section 4.17): for 1, 16 and 256 channels, beside k_channelize at the neighbouring integer D on the same bytes, beside
 k_awgn_tile and the arithmetic floor N n_out T 4 FMAs, with the time per FMA relative to k_channelize's; then one wideband second x
 64 channels through the ratio bank.
@@ -21,7 +21,7 @@ k_channelize_grid_ratio.hip), with one slot (slot 0, or 
 (k_rechannelize / k_channelize) on the same centres in the same run where P / Q <= 32; k_channelize_grid at the next power of two
 >= P on the same samples, for Q = 1; k_awgn_tile on the same bytes.
 --real [P/Q] (repeatable; no value: D = 6, 16 and 32; a bare integer is that D) times the front end for a REAL capture
-(ofdmrx_util_channelize_real, k_channelize_real.hip) beside the analytic front end on the same number of
+(ofdmrx_util_channelize_real, k_channelize.hip) beside the analytic front end on the same number of
 wideband samples and the same centres in the same run, for 4 and 64 channels (--channels): each figure is the time of one launch
 from events round --inner launches, the median of --reps such groups with the least and the most beside it.
 The GPU work runs in a child process under a time limit; the parent never opens the GPU.  Prints a table and one JSON line."""
